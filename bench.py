@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py - utterances/s of one contrastive train step (frozen-HuBERT parallel-base recipe) on N MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and prints the result line.
+Everything else it can measure (the fields marked [--full] below, the `forward` / `kernels` / `recall` / `recipes` objects and the
+one-stream and N > 1 collective diagnostics) runs only with --full.
+
+--dump-outputs DIR: right after the timed steps, what the last timed step computed, as a caller of the train step receives it:
+DIR/loss.npy (float64 scalar), DIR/grads.npy and DIR/params.npy (float32: the optimiser's flat gradient and parameter buffers
+after that step; a fixed seeded sample of the same indices in both when the two together would exceed 64 MB).  Inputs and
+weights are seeded, so two builds given the same arguments can be compared output for output.
 
 N > 1: either launched by torch.distributed.run (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the
 environment), or started plainly - then this process, BEFORE any GPU call, starts the N ranks as a child
@@ -13,10 +22,10 @@ Workload (BASELINE.json configs[1]): Parallel SpeechCLIP base, bf16, batch 64 pe
 forward/backward + global-batch InfoNCE forward/backward + clip + Adam; weak scaling (per-GPU batch fixed),
 RCCL all-gather of the pooled embeddings + all-reduce of the flat gradient for N > 1.
 Prints ONE JSON line on rank 0 with the contract fields plus
-  "roofline":     the dominant kernel (the bf16 MFMA GEMM variant with the largest share of the step): algorithmic
+  "roofline":     [--full] the dominant kernel (the bf16 MFMA GEMM variant with the largest share of the step): algorithmic
                   TFLOP/s from a HIP-event pair around every launch (recorded on the launch stream) over the same K
                   steps, against the 2.5 PFLOP/s dense bf16 peak
-  "cpu_baseline": the CPU oracle (torch fp32 restatement of the reference maths) timed on the host cores of
+  "cpu_baseline": [--full] the CPU oracle (torch fp32 restatement of the reference maths) timed on the host cores of
                   rank 0 on a bounded sample of the same workload (N = 1 only).
 """
 import argparse
@@ -34,6 +43,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 MFMA_BF16_DENSE_PEAK_TFLOPS = 2500.0       # MI355X_MICROARCH.md: ~2.5 PF dense bf16
+FULL_ONLY_FIELDS = ("one_stream_ms_per_step", "collectives", "roofline", "kernels", "cpu_baseline", "forward", "forward_train_mode", "recall")
+DUMP_BUDGET_BYTES = 64_000_000              # --dump-outputs: 64 MB for all files together
 
 
 def main():
@@ -41,6 +52,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="besides the headline figure, everything else this script measures: roofline "
+                    "and per-kernel timings, the one-stream schedule, forward-only rates, CPU baseline, recall parity, the `recipes` "
+                    "object and the counter / RCCL child runs of the default N = 1 run, the N > 1 collective brackets (the --no-* and "
+                    "--cpu-* switches below trim this further)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last timed step's loss, gradients and "
+                    "parameters as DIR/<name>.npy (see the module doc-string)")
     ap.add_argument("--batch", type=int, default=64, help="utterances per GPU")
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--ragged", action="store_true", help="SURVEY 8d's variable-length run: utterance lengths U{32000 .. --seconds * 16000} "
@@ -82,7 +99,7 @@ def main():
     default_run = (world == 1 and args.model == "base" and not args.ragged and not args.unfreeze and not args.trainable
                    and not args.no_dropout and abs(args.seconds - 10.0) < 1e-9 and args.batch == 64)
     live_traffic = rccl_rehearsal = None
-    if default_run and not args.no_recipes and not args.pmc_child and os.environ.get("SC_FORCE_COLLECTIVES", "0") != "1":
+    if args.full and default_run and not args.no_recipes and not args.pmc_child and os.environ.get("SC_FORCE_COLLECTIVES", "0") != "1":
         # child processes, run to completion BEFORE this process makes its first GPU call
         if not args.no_pmc:
             live_traffic = live_pmc_traffic()
@@ -133,42 +150,43 @@ def main():
         loss = trainer.step(batch)
     sync()
     elapsed = time.perf_counter() - t0
-    # ---- the same K steps again with a HIP-event pair around every GEMM / attention launch (recorded on the
-    # launch stream): per-launch durations of the dominant kernel for the roofline object -------------------
-    timer = None
-    if not args.no_kernel_timer and rank == 0:
-        timer = ops.KernelTimer()
-    ops.set_timer(timer)
-    for _ in range(args.steps):
-        trainer.step(batch)
-    torch.cuda.synchronize()
-    ops.set_timer(None)
-    # ---- the one-stream schedule beside the overlapped one: 2 + 5 more steps with the switch off, same process --
-    one_stream_ms = None
-    if getattr(model.audio_encoder, "enc_overlap", False) and not args.trainable:
-        model.audio_encoder.enc_overlap = False
-        for _ in range(4):                               # (the first steps after the switch absorb one-off costs: with a process group a 20 ms outlier was seen once)
-            trainer.step(batch)
-        sync()
-        t1 = time.perf_counter()
-        for _ in range(5):
-            trainer.step(batch)
-        sync()
-        one_stream_ms = (time.perf_counter() - t1) / 5 * 1e3
-        model.audio_encoder.enc_overlap = True
-        trainer.step(batch)
-        torch.cuda.synchronize()
-    # ---- N > 1: K more steps with brackets around the collectives (every rank), so that a scaling record explains itself ---------
-    collectives = None
-    if dist is not None:
-        collectives = collective_report(dist, dev, args.steps, elapsed / args.steps * 1e3, lambda: trainer.step(batch))
-    # ---- forward only (north_star: fraction of the MFMA bf16 peak on the HuBERT + attention-pool forward) ---------
+    if args.dump_outputs and rank == 0:                 # before anything below steps the model again
+        dump_outputs(args.dump_outputs, loss, trainer)
+    timer = one_stream_ms = collectives = None
     fwd_ms = fwd_train_ms = conv_ms = conv_train_ms = None
-    if rank == 0 and args.model == "base":
-        fwd_train_ms, conv_train_ms = time_forward(model, batch, args.steps)     # as the train step runs it: HuBERT + head dropout live
-        model.eval()                                                             # inference forward: no dropout
-        fwd_ms, conv_ms = time_forward(model, batch, args.steps)
-        model.train()
+    if args.full:
+        # ---- the same K steps again with a HIP-event pair around every GEMM / attention launch (recorded on the
+        # launch stream): per-launch durations of the dominant kernel for the roofline object -------------------
+        if not args.no_kernel_timer and rank == 0:
+            timer = ops.KernelTimer()
+        ops.set_timer(timer)
+        for _ in range(args.steps):
+            trainer.step(batch)
+        torch.cuda.synchronize()
+        ops.set_timer(None)
+        # ---- the one-stream schedule beside the overlapped one: 2 + 5 more steps with the switch off, same process --
+        if getattr(model.audio_encoder, "enc_overlap", False) and not args.trainable:
+            model.audio_encoder.enc_overlap = False
+            for _ in range(4):                               # (the first steps after the switch absorb one-off costs: with a process group a 20 ms outlier was seen once)
+                trainer.step(batch)
+            sync()
+            t1 = time.perf_counter()
+            for _ in range(5):
+                trainer.step(batch)
+            sync()
+            one_stream_ms = (time.perf_counter() - t1) / 5 * 1e3
+            model.audio_encoder.enc_overlap = True
+            trainer.step(batch)
+            torch.cuda.synchronize()
+        # ---- N > 1: K more steps with brackets around the collectives (every rank), so that a scaling record explains itself ---------
+        if dist is not None:
+            collectives = collective_report(dist, dev, args.steps, elapsed / args.steps * 1e3, lambda: trainer.step(batch))
+        # ---- forward only (north_star: fraction of the MFMA bf16 peak on the HuBERT + attention-pool forward) ---------
+        if rank == 0 and args.model == "base":
+            fwd_train_ms, conv_train_ms = time_forward(model, batch, args.steps)     # as the train step runs it: HuBERT + head dropout live
+            model.eval()                                                             # inference forward: no dropout
+            fwd_ms, conv_ms = time_forward(model, batch, args.steps)
+            model.train()
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -210,10 +228,10 @@ def main():
                 extra[k] = {"ms_per_step": round(v["ms"] / args.steps, 3),
                             "alg_tflops": round(v["work"] / (v["ms"] * 1e-3) / 1e12, 1) if v["ms"] > 0 else None}
         cpu = None
-        if world == 1 and args.cpu_utts > 0 and args.model == "base":
+        if args.full and world == 1 and args.cpu_utts > 0 and args.model == "base":
             cpu = cpu_baseline(sd, model, args.cpu_utts, L, args.cpu_iters, args.cpu_full)
         recall = None
-        if world == 1 and args.model == "base" and not args.no_recall:
+        if args.full and world == 1 and args.model == "base" and not args.no_recall:
             recall = recall_parity(dev)
         result = {
             "metric": "utterances/sec (train step)", "value": round(B * world * args.steps / elapsed, 2),
@@ -254,7 +272,10 @@ def main():
                                                                                     conv_train_ms),
             "recall": recall,
         }
-        if default_run and not args.no_recipes:
+        if not args.full:                                # a plain run reports what it measured: the headline step
+            for k in FULL_ONLY_FIELDS:
+                del result[k]
+        if args.full and default_run and not args.no_recipes:
             del trainer, model, batch
             torch.cuda.empty_cache()
             result["recipes"] = run_recipes(args, dev)
@@ -310,6 +331,24 @@ def make_workload(kind, B, L, ragged, rank, dev, unfreeze=0, trainable=False, no
     ids = (torch.arange(B) + rank * B) // 5            # Flickr8k shape: 5 captions per image id
     batch = {"wav": wav, "wav_len": wav_len, "image": img, "id": ids.to(dev)}
     return model, trainer, batch, sd, wav_len
+
+
+def dump_outputs(out_dir, loss, trainer):
+    """--dump-outputs: what the last timed step computed, as its caller receives it - the loss it returned and the state it left in
+    the optimiser's flat buffers (that step's gradients, the parameters after its update).  The loss in float64, the buffers in
+    float32; when the two buffers together exceed DUMP_BUDGET_BYTES, the same fixed seeded sample of indices (ascending) from both."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    opt = trainer.opt
+    bufs = {"grads": opt.flat_g, "params": opt.flat_p}
+    n = opt.size
+    k = min(n, (DUMP_BUDGET_BYTES - 4096) // (4 * len(bufs)))          # (4096: the .npy headers and the loss)
+    idx = None
+    if k < n:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(7122))[:k].sort().values.to(opt.flat_p.device)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray(float(loss.item()), dtype=np.float64))
+    for name, buf in bufs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), (buf if idx is None else buf[idx]).float().cpu().numpy())
 
 
 def time_forward(model, batch, steps):
@@ -641,7 +680,7 @@ def rccl_one_rank_rehearsal(args):
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, SC_FORCE_COLLECTIVES="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "3", "--cpu-utts", "0", "--no-recall", "--no-recipes",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "10", "--warmup", "3", "--cpu-utts", "0", "--no-recall", "--no-recipes",
            "--no-pmc", "--no-kernel-timer", "--batch", str(args.batch), "--seconds", str(args.seconds)]
     try:
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)

@@ -222,10 +222,28 @@ def test_recall_eval_generators_draw_the_oracles_streams():
     assert 20000 <= len(w0) <= 40000 and len(w0) % 320 == 0 and torch.equal(w0, recall_eval.utterance(3, 1))
 
 
+def _flat(c, pre=""):
+    out = {}
+    for k, v in c.items():
+        if hasattr(v, "items"):
+            out.update(_flat(v, pre + k + "."))
+        else:
+            out[pre + k] = v
+    return out
+
+
+def _reference_recipes():
+    """tests/golden/recipes.json (make_recipe_fixture.py): per yaml recipe of the reference's config/, the values load_config gives the
+    keys the built-in configs hold; the reduced-vocabulary table as {"path": as the yaml writes it, "rows": the shipped table's length}."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "recipes.json")) as f:
+        return json.load(f)
+
+
 def test_reference_yaml_recipes_parse_unchanged():
-    """Every yaml under the reference's config/ (present in the build container only) loads through load_config with the keys
-    the model reads; a recipe-shaped yaml text of our own covers the same code on any box."""
-    import glob
+    """Every recipe under the reference's config/ (its values stored in tests/golden/recipes.json) loads through load_config with the
+    keys the model reads, and the synthetic vocabulary substituted on random weights has the shipped table's size; a recipe-shaped
+    yaml text of our own covers the yaml path of the same code."""
     from speechclip_plus_amd import load_config
     text = """
 model_settings: {cascaded_objective_weight: 0.0, parallel_objective_weight: 1.0,
@@ -241,45 +259,46 @@ audio_encoder: {type: FairseqHubert, name: hubert_large_ll60k, trainable: false,
     cfg = load_config(text, allow_synthetic_vocab=True)
     assert cfg.clip.embed_dim == 768 and cfg.clip.reduce_subword_embbedding.numel() == 19787
     assert cfg.retrieval.recall_at == [1, 5, 10] and cfg.audio_encoder.optim.args.lr == 1e-4
-    files = glob.glob("/root/reference/config/*/*/*.yaml") + glob.glob("/root/reference/config/*/*/*/*.yaml")
-    for f in files:
-        c = load_config(f, reference_root="/root/reference")
-        assert c.audio_encoder.type == "FairseqHubert" and c.cl_loss.type == "MaskedContrastiveLoss"
-        assert c.clip.embed_dim in (512, 768)
+    recipes = _reference_recipes()
+    assert len(recipes) == 15, sorted(recipes)
+    for rel, rec in recipes.items():
+        nested = {}
+        for k, v in rec.items():
+            *path, leaf = k.split(".")
+            node = nested
+            for p in path:
+                node = node.setdefault(p, {})
+            node[leaf] = v["path"] if isinstance(v, dict) else v
+        vocab = rec.get("clip.reduce_subword_embbedding")
+        if vocab is not None:
+            with pytest.raises(FileNotFoundError):
+                load_config(nested, reference_root=os.path.join(ROOT, "tests", "golden"))
+        c = load_config(nested, allow_synthetic_vocab=True)
+        assert c.audio_encoder.type == "FairseqHubert" and c.cl_loss.type == "MaskedContrastiveLoss", rel
+        assert c.clip.embed_dim in (512, 768), rel
+        if vocab is not None:
+            assert c.clip.reduce_subword_embbedding.numel() == vocab["rows"], (rel, vocab)
 
 
 def test_builtin_configs_equal_the_reference_yamls():
     """every built-in recipe against load_config(<the reference's yaml>) on EVERY key the built-in holds (= the
-    keys the path reads).  A key the yaml does not have must carry the reference's default, listed here with its source.  Runs in
-    the build container only (the yamls do not travel)."""
-    from speechclip_plus_amd import (base_parallel_config, cascaded_plus_base_config, hybrid_plus_large_config, large_parallel_config,
-                                     load_config)
-    ref = "/root/reference/config"
-    if not os.path.isdir(ref):
-        pytest.skip("the reference's yaml recipes exist in the build container only")
+    keys the path reads; the yaml's values stored in tests/golden/recipes.json).  A key the yaml does not have must carry the
+    reference's default, listed here with its source."""
+    from speechclip_plus_amd import base_parallel_config, cascaded_plus_base_config, hybrid_plus_large_config, large_parallel_config
+    recipes = _reference_recipes()
     defaults = {"audio_encoder.normalize_hiddenstates": False,                 # speech_encoder_plus.py:350
                 "model_settings.parallel_branch.need_projection": True,       # the plus yamls do not configure a separate parallel head:
                 "model_settings.parallel_branch.transformer_type": "TransformerEncoder",    # inherited, unused (hybrid's CLS row shares the block)
                 "trainer.accumulate_grad_batches": 1}                         # pytorch_lightning.Trainer default
 
-    def flat(c, pre=""):
-        out = {}
-        for k, v in c.items():
-            if hasattr(v, "items"):
-                out.update(flat(v, pre + k + "."))
-            else:
-                out[pre + k] = v
-        return out
-
     for builtin, rel in ((base_parallel_config(), "speechCLIP/model_base/spchclp_p.yaml"),
                          (large_parallel_config(), "speechCLIP/model_large/flickr/spchclp_p.yaml"),
                          (cascaded_plus_base_config(), "speechCLIP+/model_base/spchclip_c+.yaml"),
                          (hybrid_plus_large_config(), "speechCLIP+/model_large/coco/spchclip_h+.yaml")):
-        fy = flat(load_config(os.path.join(ref, rel), reference_root="/root/reference", allow_synthetic_vocab=True))
-        for k, v in flat(builtin).items():
+        fy = recipes[rel]
+        for k, v in _flat(builtin).items():
             if isinstance(v, torch.Tensor):                                    # the reduced vocabulary: same size as the yaml's table
-                table = np.load(fy[k]) if isinstance(fy[k], str) else fy[k]
-                assert v.numel() == len(table), (rel, k, v.numel(), len(table))
+                assert v.numel() == fy[k]["rows"], (rel, k, v.numel(), fy[k])
             elif k in fy:
                 assert v == fy[k], (rel, k, v, fy[k])
             else:
@@ -312,6 +331,32 @@ def test_bench_host_helpers():
     assert t["traffic_write_bytes"] == round(180.0 * 1024.0 / 3) and t["traffic_source"].startswith("live:")
     assert bench.traffic_from_live("rocprofv3 not found", "gemm256_kernel<0,") is None
     assert bench.traffic_from_live({"gemm256_kernel<0, x>": {"fetch_kib": [1.0], "write_kib": [1.0, 2.0]}}, "gemm256_kernel<0,") is None
+
+
+def test_bench_dump_outputs_fit_the_budget(tmp_path):
+    """bench.py --dump-outputs: the loss in float64, the optimiser's flat gradient and parameter buffers in float32, whole while they
+    fit in 64 MB, past that the same seeded sample of indices from both - identical from run to run, 64 MB at most in all."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    def dump(n, name):
+        g = torch.arange(n, dtype=torch.float32)
+        trainer = types.SimpleNamespace(opt=types.SimpleNamespace(size=n, flat_g=g, flat_p=-g))
+        d = tmp_path / name
+        bench.dump_outputs(str(d), torch.tensor(1.25), trainer)
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64_000_000
+        return {f.stem: np.load(f) for f in d.iterdir()}
+
+    small = dump(1000, "small")
+    assert set(small) == {"loss", "grads", "params"} and small["loss"].dtype == np.float64 and float(small["loss"]) == 1.25
+    assert small["grads"].dtype == np.float32 and np.array_equal(small["grads"], np.arange(1000, dtype=np.float32))
+    assert np.array_equal(small["params"], -small["grads"])
+    big, again = dump(9_000_000, "big"), dump(9_000_000, "again")          # 72 MB of buffers: sampled
+    assert 0 < len(big["grads"]) < 9_000_000 and np.all(np.diff(big["grads"]) > 0)
+    assert np.array_equal(big["params"], -big["grads"]) and all(np.array_equal(big[k], again[k]) for k in big)
 
 
 @pytest.mark.parametrize("suffix", ["", "_b"])

@@ -4,7 +4,7 @@
 var=$1; rounds=$2; shift 2
 for r in $(seq 1 $rounds); do
   for v in 0 1; do
-    env $var=$v python bench.py --cpu-utts 0 --no-recall --no-recipes --no-kernel-timer --steps 20 --warmup 5 "$@" 2>/dev/null | python -c "
+    env $var=$v python bench.py --full --cpu-utts 0 --no-recall --no-recipes --no-kernel-timer --steps 20 --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('$var=$v', d['ms_per_step'], d['one_stream_ms_per_step'])"
   done

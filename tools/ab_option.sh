@@ -5,7 +5,7 @@ key=$1; val=$2; rounds=${3:-3}; shift; shift; shift || true
 out=$PWD/gpurun_out/ab_opt${key}.txt; : > $out
 for i in $(seq $rounds); do
   for v in 0 $val; do
-    python - "$key" "$v" --cpu-utts 0 --no-recall --no-recipes "$@" 2>/dev/null <<'PY' | python -c "
+    python - "$key" "$v" --full --cpu-utts 0 --no-recall --no-recipes "$@" 2>/dev/null <<'PY' | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 f=d.get('forward') or {}

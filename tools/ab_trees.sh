@@ -7,7 +7,8 @@ out=$PWD/gpurun_out/ab_$name.txt; : > $out
 for i in $(seq $rounds); do
   for t in old new; do
     if [ $t = old ]; then d=tools/_ab/$name; else d=.; fi
-    (cd $d && (python bench.py --cpu-utts 0 --no-recall --no-recipes "$@" 2>/dev/null || python bench.py --cpu-utts 0 --no-recall "$@" 2>/dev/null)) | python -c "
+    (cd $d && if grep -q '"--full"' bench.py; then python bench.py --full --cpu-utts 0 --no-recall --no-recipes "$@" 2>/dev/null
+             else python bench.py --cpu-utts 0 --no-recall --no-recipes "$@" 2>/dev/null || python bench.py --cpu-utts 0 --no-recall "$@" 2>/dev/null; fi) | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 f=d.get('forward') or {}

@@ -13,7 +13,7 @@ for r in $recipes; do
         *) args="--model $r" ;;
     esac
     rm -rf /tmp/p_$r
-    rocprofv3 --kernel-trace --stats -d /tmp/p_$r -o t -- python3 bench.py --steps 5 --warmup 2 --cpu-utts 0 --no-recall $args \
+    rocprofv3 --kernel-trace --stats -d /tmp/p_$r -o t -- python3 bench.py --full --steps 5 --warmup 2 --cpu-utts 0 --no-recall $args \
         > $out/${tag}_${r}_run.json 2> /tmp/p_$r.err
     db=$(find /tmp/p_$r -name "*.db" | head -1)
     python3 tools/rocpd_section.py "$db" --step 4 --top 60 > $out/${tag}_${r}_section.txt
