@@ -67,7 +67,7 @@ typedef struct {
  *       Conv1d becomes a GEMM: lda = stride*C_in, K = k*C_in)
  *   W   [N, K] bf16, row stride ldw   (torch Linear layout [out, in])
  *   C   [M, N] bf16 (or fp32 if out_f32), row stride ldc
- *   epilogue order:  acc -> +bias[n] -> act (0 none, 1 GELU-erf) -> dropout (train mode) -> +residual[m, n] -> store
+ *   epilogue order:  acc -> +bias[n] -> act (0 none, 1 GELU-erf, 2 QuickGELU) -> dropout (train mode) -> +residual[m, n] -> store
  *   dropout (fairseq dropout_input / the layers' residual dropouts, F.dropout semantics: keep with probability 1 - p, scale the
  *       kept values by 1 / (1 - p)): stateless counter-based mask - element (m, n) is kept iff the 16-bit lane of
  *       sc_hash32((m*N + n) / 2 ^ drop_seed) selected by (m*N + n) & 1 is >= round(p * 65536); not applied to Ct columns
@@ -84,7 +84,8 @@ typedef struct {
     int32_t M, N, K;
     const float* bias;            /* [N] fp32 or NULL */
     const sc_bf16* residual; int64_t ldr;   /* [M, N] bf16 or NULL */
-    int32_t act;                  /* 0 none, 1 gelu(erf) (fused epilogue of every tile family); 2 QuickGELU only with aux_mode */
+    int32_t act;                  /* 0 none, 1 gelu(erf), 2 QuickGELU u * sigmoid(1.702 u) (fused epilogue of every tile family;
+                                     act = 2 without dropout, LayerNorm folding or the diagnostic tile ids) */
     int32_t out_f32;              /* 0: C is bf16, 1: C is fp32 */
     sc_bf16* Ct; int32_t n_split; int32_t R; int32_t dh;   /* transposed-store region; n_split < 0 disables */
     int32_t nb1, nb2;             /* batch = nb1*nb2 (>= 1 each) */
@@ -693,7 +694,8 @@ int sc_rt_elem(const float* y, int64_t y_slice, int32_t ns, const float* bias, c
 typedef struct {
     const sc_bf16* x; sc_bf16* out;
     const int32_t* valid_len;                 /* [B] keys per utterance */
-    int32_t B, R, T, D, F, H, pre_ln, reserved;
+    int32_t B, R, T, D, F, H, pre_ln;
+    int32_t ffn_act;                          /* FC1 activation: 0 erf-GELU (HuBERT), 2 QuickGELU (CLIP ResidualAttentionBlock); 2 not with fused_ln */
     const sc_bf16 *qkv_w, *o_w, *fc1_w, *fc2_w;     /* [3D, D], [D, D], [F, D], [D, F] */
     const float *qkv_b, *o_b, *fc1_b, *fc2_b, *ln1_g, *ln1_b, *ln2_g, *ln2_b;
     float eps, p_attn, p_res;
@@ -720,6 +722,23 @@ int sc_hubert_layer_fwd(const sc_hubert_layer_args* args, void* stream);
 #define SC_WS_INFONCE 0       /* a = Bg */
 #define SC_WS_HUBERT_LAYER 1  /* a = B*R rows, b = D, c = F */
 int64_t sc_workspace_bytes(int32_t what, int64_t a, int64_t b, int64_t c);
+
+/* ------------------------------------------------------------------------------------------------
+ * Front of the frozen CLIP image tower (openai/CLIP VisionTransformer: conv1 patch embedding, class token, positional embedding,
+ * ln_pre), forward only.  Image rows use the ragged row layout (sc_segments): image b owns `pitch` rows at row0[b], pitch = tokens
+ * rounded up to SC_SEG_ROWS (tokens = 1 + g^2, g = S / P): row row0[b] is the class token, rows row0[b] + 1 .. + g^2 the patches in
+ * row-major (gy, gx) order, the rest pad rows.  The blocks then run as sc_hubert_layer_fwd(pre_ln = 1, ffn_act = 2, seg).
+ *   sc_vit_patchify_bf16: A [rows, Kp] bf16 <- the operand of the patch GEMM: patch row (b, gy, gx), column c P^2 + ky P + kx =
+ *       bf16(img[b, c, gy P + ky, gx P + kx]) (the flattening of conv1.weight [W, 3, P, P]); columns 3 P^2 .. Kp - 1, class and pad
+ *       rows are 0.  img: fp32 [B, 3, S, S], rows of S contiguous floats, strides (elements) sb / sc / sy; Kp = 3 P^2 rounded up to
+ *       64.  Every element of A is written.
+ *   sc_vit_embed_ln_bf16: X [rows, W] bf16 <- ln_pre(e) in fp32, e = cls + pos[0] on class rows, e = G[r] + pos[t] on patch row t
+ *       (G: [rows, W] fp32, the patch GEMM's output), 0 on pad rows.  pos [tokens, W], cls / gamma / beta [W] fp32; W % 4 == 0.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_vit_patchify_bf16(const float* img, int64_t sb, int64_t sc, int64_t sy, sc_bf16* A, int32_t Kp, const sc_segments* seg, int32_t S,
+                         int32_t P, void* stream);
+int sc_vit_embed_ln_bf16(const float* G, const float* cls, const float* pos, const float* gamma, const float* beta, sc_bf16* X,
+                         const sc_segments* seg, int32_t tokens, int32_t W, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimiser step on a flat fp32 parameter buffer: torch.optim.Adam semantics (L2 weight decay added to

@@ -89,7 +89,7 @@ class HubertLayerArgs(ctypes.Structure):
     """Mirror of ``sc_hubert_layer_args`` (include/speechclip_hip.h)."""
     _fields_ = [
         ("x", c_void_p), ("out", c_void_p), ("valid_len", c_void_p),
-        ("B", c_int), ("R", c_int), ("T", c_int), ("D", c_int), ("F", c_int), ("H", c_int), ("pre_ln", c_int), ("reserved", c_int),
+        ("B", c_int), ("R", c_int), ("T", c_int), ("D", c_int), ("F", c_int), ("H", c_int), ("pre_ln", c_int), ("ffn_act", c_int),
         ("qkv_w", c_void_p), ("o_w", c_void_p), ("fc1_w", c_void_p), ("fc2_w", c_void_p),
         ("qkv_b", c_void_p), ("o_b", c_void_p), ("fc1_b", c_void_p), ("fc2_b", c_void_p),
         ("ln1_g", c_void_p), ("ln1_b", c_void_p), ("ln2_g", c_void_p), ("ln2_b", c_void_p),
@@ -222,6 +222,9 @@ SIGNATURES = {
     "sc_prompt_assemble": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "sc_prompt_assemble_bwd": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "sc_rows_gather_bf16": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "sc_vit_patchify_bf16": [c_void_p, c_i64, c_i64, c_i64, c_void_p, c_int, ctypes.POINTER(Segments), c_int, c_int, c_void_p],
+    "sc_vit_embed_ln_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_float,
+                             c_void_p],
     "sc_rows_scatter_bf16": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "sc_cif_head_fwd": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, ctypes.c_uint32, c_float, ctypes.c_uint32, c_void_p],
     "sc_cif_head_bwd": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_float,

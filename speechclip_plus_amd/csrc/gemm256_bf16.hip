@@ -551,6 +551,10 @@ static int launch256(const sc_gemm_args& a, hipStream_t s) {
         if (a.aux_mode == 2) return launch256__<DIAG, BN, 4, 0, 0, 0>(a, s);      // act = 1, no residual / dropout / transposed store / LN)
         if (a.drop_p > 0.f) return a.act == 1 ? launch256_<DIAG, BN, 1, 1>(a, s) : launch256_<DIAG, BN, 0, 1>(a, s);
     }
+    if constexpr (DIAG == 0) {          // QuickGELU (act = 2, plain epilogue; sc_gemm_bf16 refuses it with dropout): its own instances,
+        if (a.act == 2)                 // never the no-activation ones.  No LayerNorm-folded form (launch256_ would add them to the diag build)
+            return a.residual ? launch256__<DIAG, BN, 2, 0, 1, 0>(a, s) : launch256__<DIAG, BN, 2, 0, 0, 0>(a, s);
+    }
     return a.act == 1 ? launch256_<DIAG, BN, 1, 0>(a, s) : launch256_<DIAG, BN, 0, 0>(a, s);
 }
 

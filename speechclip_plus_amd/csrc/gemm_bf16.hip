@@ -262,6 +262,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const sc_gemm_args p) {
             if (p.act == 1 && p.aux_mode == 0) {
                 const f32x2 g0 = gelu_bf2(f32x2{v[0], v[1]}), g1 = gelu_bf2(f32x2{v[2], v[3]});
                 v = f32x4{g0.x, g0.y, g1.x, g1.y};
+            } else if (p.act == 2 && p.aux_mode == 0) {
+                v = qgelu4(v);          // QuickGELU (sc_common.h): the same definition as the 256-row tiles' ACT = 2
             }
             if (transposed) {
                 *(f32x4*)(Cs + nl * BM + ml) = v;
@@ -389,7 +391,7 @@ extern "C" int sc_gemm_bf16(const sc_gemm_args* args, void* stream) {
     SC_CHECK(a.lda % 8 == 0 && a.ldw % 8 == 0 && a.ldc % 8 == 0, "sc_gemm_bf16: leading dims must be multiples of 8");
     SC_CHECK(((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.W % 16) == 0 && ((uintptr_t)a.C % 16) == 0,
              "sc_gemm_bf16: operands must be 16-byte aligned");
-    SC_CHECK(a.act == 0 || a.act == 1 || (a.act == 2 && a.aux_mode != 0), "sc_gemm_bf16: act=%d", a.act);
+    SC_CHECK(a.act == 0 || a.act == 1 || a.act == 2, "sc_gemm_bf16: act=%d", a.act);
     SC_CHECK(a.drop_p >= 0.f && a.drop_p < 1.f, "sc_gemm_bf16: drop_p=%f", (double)a.drop_p);
     SC_CHECK(a.tap_c == 0 || (a.tap_c > 0 && a.tap_c % 64 == 0 && a.K == 3 * a.tap_c),
              "sc_gemm_bf16: tap_c=%d needs tap_c %% 64 == 0 and K == 3 * tap_c (K=%d)", a.tap_c, a.K);
@@ -430,9 +432,13 @@ extern "C" int sc_gemm_bf16(const sc_gemm_args* args, void* stream) {
         SC_CHECK(a.tile == 0 || a.tile == 1 || a.tile == 3 || a.tile == 13 || a.tile == 14 || a.tile == 15 || ((a.tile == 2 || a.tile == 7 || a.tile == 8) && a.act == 1 && !a.residual),
                  "sc_gemm_bf16: aux_mode on the 256-row tiles needs act = 1 (erf-GELU) and no residual");
     } else {
-        SC_CHECK(a.act == 0 || a.act == 1, "sc_gemm_bf16: act=%d (2 = QuickGELU needs aux_mode)", a.act);
+        // act = 2 (QuickGELU) as a plain epilogue: every tile family (the 256-row tiles through their ACT = 2 instances); no dropout
+        // variant is built for it (the CLIP towers are frozen, eval-mode)
+        SC_CHECK(a.act != 2 || a.drop_p == 0.f, "sc_gemm_bf16: act = 2 (QuickGELU) has no dropout variant");
     }
     const bool ln = a.ln_stats || a.stats_out || a.res_stats;
+    SC_CHECK(a.act != 2 || (!ln && a.tile != 32 && a.tile != 34),
+             "sc_gemm_bf16: act = 2 (QuickGELU) is not built into the LayerNorm-folded or the diagnostic 256-row instances");
     const bool ln_self = a.ln_colsum && !a.ln_stats;            // LayerNorm in the prologue of the 128- / 64-row tiles (gemm_bf16_kernel)
     if (ln_self) {
         SC_CHECK(!a.stats_out && !a.res_stats && a.K <= 1024 && a.ln_eps > 0.f && a.tap_c == 0 && !a.tn && a.n_split < 0 && a.lda >= a.K &&

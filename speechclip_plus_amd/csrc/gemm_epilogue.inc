@@ -57,6 +57,7 @@
                                     const f32x2 g0 = gelu_bf2(f32x2{v[0], v[1]}), g1 = gelu_bf2(f32x2{v[2], v[3]});
                                     v = f32x4{g0.x, g0.y, g1.x, g1.y};
                                 }
+                                if (ACT == 2) v = qgelu4(v);
                                 const int ml = mi * 16 + (el & 15);
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) {
@@ -118,6 +119,7 @@
                                 const f32x2 g0 = gelu_bf2(f32x2{v[0], v[1]}), g1 = gelu_bf2(f32x2{v[2], v[3]});
                                 v = f32x4{g0.x, g0.y, g1.x, g1.y};
                             }
+                            if (ACT == 2) v = qgelu4(v);
                             const int ml = mi * 16 + (el & 15), ch = ni * 4 + (el >> 4);
                             *(f32x4*)(Cw + ml * 64 + ((ch ^ (ml & 15)) << 2)) = v;
                         }
@@ -276,6 +278,10 @@
                             Fv = f32x4{a0.x, a0.y, a1.x, a1.y};
                             Gv = f32x4{b0.x, b0.y, b1.x, b1.y};
                         }
+                        if (ACT == 2) {
+                            Fv = qgelu4(Fv);
+                            Gv = qgelu4(Gv);
+                        }
                         float v[8];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {    // odd lane-rows of F <-> even lane-rows of G
@@ -295,6 +301,10 @@
                             const f32x2 b0 = gelu_bf2(f32x2{Gv[0], Gv[1]}), b1 = gelu_bf2(f32x2{Gv[2], Gv[3]});
                             Fv = f32x4{a0.x, a0.y, a1.x, a1.y};
                             Gv = f32x4{b0.x, b0.y, b1.x, b1.y};
+                        }
+                        if (ACT == 2) {
+                            Fv = qgelu4(Fv);
+                            Gv = qgelu4(Gv);
                         }
                         float v[8];
 #pragma unroll

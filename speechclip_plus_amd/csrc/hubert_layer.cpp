@@ -3,6 +3,8 @@
 // (large) order, eval or train-mode dropout:
 //     QKV GEMM (V stored transposed per head) -> flash attention -> out_proj GEMM (+bias, dropout, +residual) -> LayerNorm
 //     -> FC1 GEMM (+bias, erf-GELU) -> FC2 GEMM (+bias, dropout, +residual) -> LayerNorm
+// ffn_act = 2: QuickGELU after FC1 instead of erf-GELU - the pre-LN block of CLIP's ResidualAttentionBlock (the image tower,
+// clip_image.py); everything else as above.
 // It only sequences the library's own entry points (no new arithmetic), so a binding does 1 FFI call per layer instead of 7.
 // sc_workspace_bytes reports the scratch a caller has to provide.
 #include <hip/hip_runtime.h>
@@ -41,6 +43,9 @@ extern "C" int64_t sc_workspace_bytes(int32_t what, int64_t a, int64_t b, int64_
 extern "C" int sc_hubert_layer_fwd(const sc_hubert_layer_args* p, void* stream) {
     SC_CHECK(p && p->x && p->out && p->valid_len && p->qk && p->vt && p->ctx && p->pre && (p->x1 || p->fused_ln) && p->ffn,
              "sc_hubert_layer_fwd: null pointer");
+    SC_CHECK(p->ffn_act == 0 || p->ffn_act == 2, "sc_hubert_layer_fwd: ffn_act=%d (0 erf-GELU, 2 QuickGELU)", p->ffn_act);
+    SC_CHECK(p->ffn_act == 0 || !p->fused_ln, "sc_hubert_layer_fwd: ffn_act = 2 is not built into the fused_ln form");
+    const int fc1_act = p->ffn_act == 2 ? 2 : 1;      // sc_gemm_args.act of FC1
     const sc_segments* seg = p->seg;
     if (seg) {
         SC_CHECK(seg->row0 && seg->chunk && seg->B > 0 && seg->rows > 0 && seg->rows % SC_SEG_ROWS == 0 && p->H > 0 && p->D == p->H * 64 && p->F > 0,
@@ -100,12 +105,12 @@ extern "C" int sc_hubert_layer_fwd(const sc_hubert_layer_args* p, void* stream) 
     if ((rc = gemm(p->ctx, D, p->o_w, D, p->pre, D, M, D, D, p->o_b, p->x, D, 0, p->p_res, p->seed_o, nullptr, -1, 0, 0, stream))) return rc;
     if (p->pre_ln) {                  // pre = x + attn ; x1 = LN2(pre) ; out = pre + ffn(x1)
         if ((rc = sc_layernorm_bf16(p->pre, D, p->ln2_g, p->ln2_b, p->x1, D, M, D, p->eps, 0, stream))) return rc;
-        if ((rc = gemm(p->x1, D, p->fc1_w, D, p->ffn, F, M, F, D, p->fc1_b, nullptr, 0, 1, 0.f, 0, nullptr, -1, 0, 0, stream))) return rc;
+        if ((rc = gemm(p->x1, D, p->fc1_w, D, p->ffn, F, M, F, D, p->fc1_b, nullptr, 0, fc1_act, 0.f, 0, nullptr, -1, 0, 0, stream))) return rc;
         return gemm(p->ffn, F, p->fc2_w, F, p->out, D, M, D, F, p->fc2_b, p->pre, D, 0, p->p_res, p->seed_fc2, nullptr, -1, 0, 0, stream);
     }
     // post-LN: x1 = LN1(x + attn) ; out = LN2(x1 + ffn(x1))
     if ((rc = sc_layernorm_bf16(p->pre, D, p->ln1_g, p->ln1_b, p->x1, D, M, D, p->eps, 0, stream))) return rc;
-    if ((rc = gemm(p->x1, D, p->fc1_w, D, p->ffn, F, M, F, D, p->fc1_b, nullptr, 0, 1, 0.f, 0, nullptr, -1, 0, 0, stream))) return rc;
+    if ((rc = gemm(p->x1, D, p->fc1_w, D, p->ffn, F, M, F, D, p->fc1_b, nullptr, 0, fc1_act, 0.f, 0, nullptr, -1, 0, 0, stream))) return rc;
     if ((rc = gemm(p->ffn, F, p->fc2_w, F, p->pre, D, M, D, F, p->fc2_b, p->x1, D, 0, p->p_res, p->seed_fc2, nullptr, -1, 0, 0, stream))) return rc;
     return sc_layernorm_bf16(p->pre, D, p->ln2_g, p->ln2_b, p->out, D, M, D, p->eps, 0, stream);
 }

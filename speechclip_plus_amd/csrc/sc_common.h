@@ -221,6 +221,26 @@ __device__ __forceinline__ f32x2 gelu_bf2(f32x2 x) {
 #endif
 }
 
+// QuickGELU (CLIP MLP) of the plain GEMM epilogues (sc_gemm_args.act = 2, aux_mode = 0), two elements at a time: act_fwd's
+// u * sigmoid(1.702 u) = u / (1 + exp(-1.702 u)) as ONE logistic term in gelu_bf2's form - the exponent of 2 and the final product as
+// packed fp32 ops, v_exp / v_rcp per element: 3 packed ops + 2 v_exp + 2 v_rcp per pair against gelu_bf2's 9 + 2 + 2.  The reciprocal
+// is the hardware one (1 ulp fp32) where act_fwd divides exactly; a bf16 store rounds by 2^-9.  Every tile family calls this one
+// definition, so the result does not depend on the tile.  Saturates without NaN: exp2 -> inf / 0, rcp -> 0 / 1, out -> -0 / u.
+__device__ __forceinline__ f32x2 qgelu2(f32x2 u) {
+#pragma clang fp contract(off)
+    const f32x2 w = u * -2.4554669595930156f;                  // -1.702 log2(e)
+    f32x2 e;
+    e.x = __builtin_amdgcn_exp2f(w.x); e.y = __builtin_amdgcn_exp2f(w.y);
+    const f32x2 d = e + 1.0f;
+    f32x2 r;
+    r.x = __builtin_amdgcn_rcpf(d.x); r.y = __builtin_amdgcn_rcpf(d.y);
+    return u * r;
+}
+__device__ __forceinline__ f32x4 qgelu4(f32x4 v) {
+    const f32x2 a = qgelu2(f32x2{v[0], v[1]}), b = qgelu2(f32x2{v[2], v[3]});
+    return f32x4{a.x, a.y, b.x, b.y};
+}
+
 // gelu_grad_as on two elements: the polynomial, squarings and products as packed fp32 ops, rcp / exp per element.  Same operation order
 // as gelu_grad_as => the same bits.
 __device__ __forceinline__ f32x2 gelu_grad_as2(f32x2 x) {

@@ -6,9 +6,10 @@ Kept API: ``forward(batch) -> (losses, log_metrics, others)`` with t
 ``training_step`` / ``training_step_end`` semantics (:145-193) so it drops into the existing
 PyTorch-Lightning loop (it is a plain ``nn.Module``; pytorch_lightning is not installed here).
 
-Out of scope here: the frozen CLIP towers (the ``clip`` package and its weights are not available offline).
-``batch["image"]`` may already hold the CLIP image embeddings (B, E); for pixel input pass an
-``image_encoder`` callable (frozen, no grad) to the constructor.
+``batch["image"]`` may already hold the CLIP image embeddings (B, E).  For pixel input (the reference's ``load_image: true``
+recipes) pass ``image_encoder="clip"``: the frozen CLIP image tower of ``config.clip.name`` on the library's kernels
+(clip_image.ClipImageEncoder, weights from a reference checkpoint's ``clip.model.visual.*`` keys through
+``from_reference_checkpoint``), or any frozen callable of your own.
 """
 import logging
 from typing import Callable, List, Optional, Tuple, Union
@@ -17,6 +18,7 @@ import torch
 from torch import nn
 
 from . import losses
+from .clip_image import ClipImageEncoder
 from .clip_text import ClipModel
 from .head_tail import unit_rows
 from .kw_branches import KW_CascadedBranchPlus, KW_HybridBranchPlus, KW_ParallelBranch
@@ -156,7 +158,7 @@ def set_dropout(model: nn.Module, enabled: bool) -> nn.Module:
 
 
 class KWClip_GeneralTransformer(nn.Module):
-    def __init__(self, config, image_encoder: Optional[Callable] = None, device: str = "cuda", hubert_state_dict=None,
+    def __init__(self, config, image_encoder: Optional[Union[Callable, str]] = None, device: str = "cuda", hubert_state_dict=None,
                  hubert_arch=None):
         super().__init__()
         if isinstance(config, str):                   # path of a reference yaml recipe (config/**/*.yaml parse unchanged)
@@ -164,6 +166,12 @@ class KWClip_GeneralTransformer(nn.Module):
         self.config = config if isinstance(config, Config) else load_config(config)
         config = self.config
         self._device = torch.device(device)
+        if isinstance(image_encoder, str):
+            if image_encoder != "clip":
+                raise ValueError(f"image_encoder={image_encoder!r}: 'clip' (the frozen CLIP image tower), a callable or None")
+            # frozen submodule (state-dict keys image_encoder.*); getTrainableParams lists modules by name and never includes it
+            image_encoder = ClipImageEncoder(config.clip.get("name", "ViT-B/32"),
+                                             image_encoder_trainable=bool(config.clip.get("image_encoder_trainable", False)))
         self.audio_encoder_type = config.audio_encoder.type
         if self.audio_encoder_type != "FairseqHubert":
             raise NotImplementedError(f"audio_encoder.type = {self.audio_encoder_type}: only FairseqHubert is built "
@@ -255,8 +263,8 @@ class KWClip_GeneralTransformer(nn.Module):
         if isinstance(images, torch.Tensor) and images.dim() == 2:
             return images.to(self._device)                     # pre-computed (frozen) CLIP image embeddings
         if self.image_encoder is None:
-            raise RuntimeError("pixel input needs an image_encoder callable (the CLIP image tower is frozen and out of "
-                               "scope); pass CLIP embeddings (B, E) in batch['image'] instead")
+            raise RuntimeError("pixel input needs an image encoder: construct with image_encoder=\"clip\" (the frozen CLIP image "
+                               "tower) or a callable, or pass CLIP embeddings (B, E) in batch['image'] instead")
         if isinstance(images, torch.Tensor) and (images.dim() != 4 or images.shape[1] != 3):
             raise ValueError(f"Incorrect image tensor shape {images.shape}")
         with torch.no_grad():
@@ -443,14 +451,22 @@ class KWClip_GeneralTransformer(nn.Module):
     @classmethod
     def from_reference_checkpoint(cls, config, state_dict: dict, **kw):
         """Build the model on the reference's weights: the HuBERT part is converted by the encoder's loader (fairseq key names,
-        weight-normed pos_conv accepted), everything else loads by name (non-strict for keys this build does not hold)."""
+        weight-normed pos_conv accepted), everything else loads by name (non-strict for keys this build does not hold).  With
+        ``image_encoder="clip"`` the ``clip.model.visual.*`` keys load into the image tower as well (strict)."""
         hubert, rest = cls.split_reference_state_dict(state_dict)
         model = cls(config, hubert_state_dict=hubert if hubert else None, **kw)
         own = model.state_dict()
         loadable = {k: v for k, v in rest.items() if k in own and tuple(own[k].shape) == tuple(v.shape)}
-        missing = [k for k in own if k not in loadable and not k.startswith("audio_encoder.train_layers.")]
+        visual = {}
+        if kw.get("image_encoder") == "clip":
+            pre = "clip.model.visual."
+            visual = {k: v for k, v in state_dict.items() if k.startswith(pre)}
+            if visual:
+                model.image_encoder.load_reference_state_dict({k[len(pre):]: v for k, v in visual.items()})
+        missing = [k for k in own if k not in loadable and not k.startswith("audio_encoder.train_layers.")
+                   and not (visual and k.startswith("image_encoder."))]
         model.load_state_dict(loadable, strict=False)
-        model._reference_load_report = {"loaded": sorted(loadable), "not_in_checkpoint": missing,
+        model._reference_load_report = {"loaded": sorted(list(loadable) + list(visual)), "not_in_checkpoint": missing,
                                         "ignored": sorted(k for k in rest if k not in loadable)}
         return model
 

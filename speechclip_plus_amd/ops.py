@@ -207,12 +207,14 @@ def gemm_raw(A: torch.Tensor, lda: int, W: torch.Tensor, ldw: int, C: torch.Tens
 
 def hubert_layer_fwd(x: torch.Tensor, out: torch.Tensor, valid_len: torch.Tensor, w: dict, i: int, pl, B: int, R: int, T: int, D: int,
                      F_: int, H: int, pre_ln: bool, p_attn: float = 0.0, p_res: float = 0.0, seeds=(0, 0, 0), fused=None,
-                     seg: Optional["RowSegments"] = None) -> None:
+                     seg: Optional["RowSegments"] = None, ffn_act: int = 0) -> None:
     """One frozen HuBERT encoder layer in ONE C-ABI call (sc_hubert_layer_fwd: QKV -> attention -> out_proj -> LN -> FC1 -> FC2 ->
     LN on the caller's stream).  ``w``: the encoder's weight dict (keys l{i}_*), ``pl``: its plan (scratch buffers).
     ``fused`` = (x_stats or None, x_ns, out_stats): the LayerNorm-free form (the LayerNorms folded into the GEMMs; ``out`` receives
-    raw rows + statistics); x_stats None = ``x`` is an ordinary, materialised input (layer 0)."""
+    raw rows + statistics); x_stats None = ``x`` is an ordinary, materialised input (layer 0).  ``ffn_act``: FC1 activation, 0 erf-GELU,
+    2 QuickGELU (the CLIP image tower's blocks, clip_image.py)."""
     a = HubertLayerArgs()
+    a.ffn_act = int(ffn_act)
     a.x, a.out, a.valid_len = _p(x), _p(out), _p(valid_len)
     a.B, a.R, a.T, a.D, a.F, a.H, a.pre_ln = B, R, T, D, F_, H, int(pre_ln)
     a.qkv_w, a.o_w, a.fc1_w, a.fc2_w = _p(w[f"l{i}_qkv_w"]), _p(w[f"l{i}_o_w"]), _p(w[f"l{i}_fc1_w"]), _p(w[f"l{i}_fc2_w"])
@@ -1511,6 +1513,35 @@ def rows_gather(X: torch.Tensor, row: torch.Tensor) -> torch.Tensor:
     assert X.dtype == torch.bfloat16 and X.is_contiguous() and row.dtype == torch.int32
     out = torch.empty(row.numel(), X.shape[1], device=X.device, dtype=torch.float32)
     check(lib().sc_rows_gather_bf16(_p(X), _p(row), _p(out), row.numel(), X.shape[1], _stream()), "sc_rows_gather_bf16")
+    return out
+
+
+def vit_patchify(images: torch.Tensor, seg: "RowSegments", P: int, Kp: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A [seg.rows, Kp] bf16: the patch GEMM's operand of CLIP's conv1 (sc_vit_patchify_bf16).  images: fp32 [B, 3, S, S] on the
+    device whose pixel rows are contiguous (any batch / channel / row stride); class, pad rows and columns >= 3 P^2 are zero."""
+    assert images.dtype == torch.float32 and images.dim() == 4 and images.shape[1] == 3 and images.stride(3) == 1
+    assert images.shape[0] == seg.B and images.shape[2] == images.shape[3]
+    if out is None:
+        out = torch.empty(seg.rows, Kp, device=images.device, dtype=torch.bfloat16)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (seg.rows, Kp)
+    sb, sc, sy, _ = images.stride()
+    check(lib().sc_vit_patchify_bf16(_p(images), sb, sc, sy, _p(out), Kp, seg.ref(), images.shape[2], P, _stream()), "sc_vit_patchify_bf16")
+    return out
+
+
+def vit_embed_ln(G: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, seg: "RowSegments",
+                 eps: float = 1e-5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """X [seg.rows, W] bf16 = ln_pre(class / patch embedding + positional embedding) (sc_vit_embed_ln_bf16); G = the patch GEMM's fp32
+    output [seg.rows, W], pos [tokens, W]; pad rows are zero."""
+    rows, W = G.shape
+    for t in (G, cls, pos, gamma, beta):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert rows == seg.rows and cls.numel() == W and pos.shape[1] == W and gamma.numel() == W and beta.numel() == W
+    if out is None:
+        out = torch.empty(rows, W, device=G.device, dtype=torch.bfloat16)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (rows, W)
+    check(lib().sc_vit_embed_ln_bf16(_p(G), _p(aligned16(cls)), _p(aligned16(pos)), _p(aligned16(gamma)), _p(aligned16(beta)), _p(out),
+                                     seg.ref(), pos.shape[0], W, float(eps), _stream()), "sc_vit_embed_ln_bf16")
     return out
 
 
