@@ -501,34 +501,83 @@ __global__ __launch_bounds__(256) void conv0_ln_gelu_stats_kernel(const float* _
 // Fully trainable encoder (avssl/module/speech_encoder_plus.py:556-562), "default" extractor: y = gelu(n), n = gamma (u - mu) / sigma + beta,
 // u[b, t, c] = sum_j W[c][j] x[b, 5t + j], statistics over t < T0 per (b, c).  The input is the waveform: no input gradient, only
 // dW [C, 10], dgamma, dbeta.  With dn = dy gelu'(n) everything follows from 12 time sums per (b, c) -
-//   A1 = sum_t dn,  A2 = sum_t dn n,  V_j = sum_t dn x[5t + j]  (j = 0..9)
+//   A1 = sum_t dn,  D = sum_t dn (u - mu),  V_j = sum_t dn x[5t + j]  (j = 0..9)
 // - and the forward's 10 x 10 Gram matrix G and sums S of the strided waveform (sc_conv0_stats):
-//   Q = sum_t dn uhat = (A2 - beta A1) / gamma ;  dgamma = sum_b Q ;  dbeta = sum_b A1 ;
+//   Q = sum_t dn uhat = D / sigma ;  dgamma = sum_b Q ;  dbeta = sum_b A1 ;
 //   dW[c][j] = sum_b (gamma / sigma) [V_j - (A1 / T0) S_j - (Q / T0) (sum_i W[c][i] G_ij - mu S_j) / sigma]
+// D is accumulated from the centred pre-activation itself (mu from the Gram statistics, rounded to fp32 once), not recovered as
+// (sum_t dn n - beta A1) / gamma: that quotient is 0 / 0 for a channel with gamma == 0 and loses log10(|beta| / |gamma|) digits to
+// cancellation when |gamma| << |beta| (tests/test_gpu_frontend.py, the gamma-edge cases).  The 1 / sigma is applied in fp64 by the
+// finalisation: the kernel holds one extra channel pair (mu) and keeps two waves per SIMD.
 // One pass over dy (u is recomputed from the waveform, 10 FMAs per element), then a per-utterance finalisation in fp64.
 // gelu_grad_as: sc_common.h
 constexpr int C0_NS = 12;
+
+// per-(b, c) statistics of conv 0 over t < T0 from the reduced Gram statistics st (65 entries: upper triangle of G, then S):
+// mu, 1 / sqrt(var + eps) and WG[j] = sum_i W[c][i] G_ij, in fp64 (the backward's kernel and its finalisation share this one form)
+__device__ __forceinline__ void conv0_gn_moments(const double* st, const float* __restrict__ w0c, int T0, float eps, double& mu, double& rs,
+                                                 double* WG) {
+    double w[10];
+#pragma unroll
+    for (int j = 0; j < 10; ++j) w[j] = (double)w0c[j];
+    // G is stored as its upper triangle (j <= k): e = index of (min, max)
+    double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) {
+        double t = 0.0;
+#pragma unroll
+        for (int i = 0; i < 10; ++i) {
+            const int lo = i < j ? i : j, hi = i < j ? j : i;
+            const int e = lo * 10 - lo * (lo - 1) / 2 + (hi - lo);
+            t += w[i] * st[e];
+        }
+        if (WG) WG[j] = t;                                               // sum_i W[c][i] G_ij
+        s1 += w[j] * st[55 + j];
+        s2 += w[j] * t;
+    }
+    const double T = (double)T0;
+    mu = s1 / T;
+    const double var = fmax(s2 / T - mu * mu, 0.0);
+    rs = 1.0 / sqrt(var + (double)eps);
+}
+
+// the nchunk partials of sc_conv0_stats for utterance b, added in fixed order into st[65]; ends with a barrier
+__device__ __forceinline__ void conv0_gn_reduce_stats(const double* __restrict__ stats, int nchunk, int b, double* st) {
+    if (threadIdx.x < 65) {
+        double sm = 0.0;
+        for (int c = 0; c < nchunk; ++c) sm += stats[((int64_t)b * nchunk + c) * SC_CONV0_NSTAT + threadIdx.x];
+        st[threadIdx.x] = sm;
+    }
+    __syncthreads();
+}
 // grid (nblk, B), 4 waves per block; wave chunk wc = blockIdx.x * 4 + wave owns rows [wc * rpw, min(T0, (wc + 1) * rpw)); a lane owns
 // 8 channels (C = 512).  partial[((b * nwc + wc) * 512 + c) * 12 + e]
 __global__ __launch_bounds__(256) void conv0_gn_bwd_kernel(const float* __restrict__ wav, int64_t ldw, const float* __restrict__ w0,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
+                                                           const double* __restrict__ stats, int nchunk, float eps,
                                                            const uint16_t* __restrict__ dy, int T0, int R0, int rpw, int nwc,
                                                            float* __restrict__ partial) {
     constexpr int C = 512;
+    __shared__ double st[SC_CONV0_NSTAT];
     const int b = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wc = blockIdx.x * 4 + wave;
     const float* x = wav + (int64_t)b * ldw;
     const int c0 = lane * 8;
+    conv0_gn_reduce_stats(stats, nchunk, b, st);
     // channel PAIRS in packed fp32 (v_pk_fma_f32), as the forward kernel: 4 pairs x (10 taps + 12 running sums) per row
-    f32x2 w[4][10], sc[4], sh[4], acc[4][C0_NS];
+    f32x2 w[4][10], sc[4], sh[4], mu[4], acc[4][C0_NS];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
         for (int j = 0; j < 10; ++j) w[i][j] = f32x2{w0[(c0 + 2 * i) * 10 + j], w0[(c0 + 2 * i + 1) * 10 + j]};
         sc[i] = *(const f32x2*)(scale + (int64_t)b * C + c0 + 2 * i);
         sh[i] = *(const f32x2*)(shift + (int64_t)b * C + c0 + 2 * i);
+        double m0, m1, r_;
+        conv0_gn_moments(st, w0 + (c0 + 2 * i) * 10, T0, eps, m0, r_, nullptr);
+        conv0_gn_moments(st, w0 + (c0 + 2 * i + 1) * 10, T0, eps, m1, r_, nullptr);
+        mu[i] = f32x2{(float)m0, (float)m1};
 #pragma unroll
         for (int e = 0; e < C0_NS; ++e) acc[i][e] = f32x2{0.f, 0.f};
     }
@@ -547,7 +596,7 @@ __global__ __launch_bounds__(256) void conv0_gn_bwd_kernel(const float* __restri
             const f32x2 n = __builtin_elementwise_fma(u, sc[i], sh[i]);
             const f32x2 dn = g[i] * gelu_grad_as2(n);
             acc[i][0] += dn;
-            acc[i][1] = __builtin_elementwise_fma(dn, n, acc[i][1]);
+            acc[i][1] = __builtin_elementwise_fma(dn, u - mu[i], acc[i][1]);           // dn (u - mu)
 #pragma unroll
             for (int j = 0; j < 10; ++j) acc[i][2 + j] = __builtin_elementwise_fma(dn, f32x2{v[j], v[j]}, acc[i][2 + j]);
         }
@@ -651,17 +700,11 @@ __global__ __launch_bounds__(256) void conv0_ln_bwd_kernel(const float* __restri
 // contrib[b][c][12] = (dW[c][0..9], dgamma, dbeta) of utterance b (summed over b by sc_colsum_f32)
 __global__ __launch_bounds__(256) void conv0_gn_bwd_finalize_kernel(const float* __restrict__ partial, int nwc, const double* __restrict__ stats,
                                                                     int nchunk, const float* __restrict__ w0, const float* __restrict__ gamma,
-                                                                    const float* __restrict__ beta, int T0, float eps,
-                                                                    float* __restrict__ contrib) {
+                                                                    int T0, float eps, float* __restrict__ contrib) {
     constexpr int C = 512;
     __shared__ double st[SC_CONV0_NSTAT];
     const int b = blockIdx.x;
-    if (threadIdx.x < 65) {
-        double sm = 0.0;
-        for (int c = 0; c < nchunk; ++c) sm += stats[((int64_t)b * nchunk + c) * SC_CONV0_NSTAT + threadIdx.x];
-        st[threadIdx.x] = sm;
-    }
-    __syncthreads();
+    conv0_gn_reduce_stats(stats, nchunk, b, st);
     for (int c = threadIdx.x; c < C; c += 256) {
         double a[C0_NS];
 #pragma unroll
@@ -671,30 +714,11 @@ __global__ __launch_bounds__(256) void conv0_gn_bwd_finalize_kernel(const float*
 #pragma unroll
             for (int e = 0; e < C0_NS; ++e) a[e] += (double)pp[e];
         }
-        double w[10], WG[10];
-#pragma unroll
-        for (int j = 0; j < 10; ++j) w[j] = (double)w0[c * 10 + j];
-        // G is stored as its upper triangle (j <= k): e = index of (min, max)
-        double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-        for (int j = 0; j < 10; ++j) {
-            double t = 0.0;
-#pragma unroll
-            for (int i = 0; i < 10; ++i) {
-                const int lo = i < j ? i : j, hi = i < j ? j : i;
-                const int e = lo * 10 - lo * (lo - 1) / 2 + (hi - lo);
-                t += w[i] * st[e];
-            }
-            WG[j] = t;                                                   // sum_i W[c][i] G_ij
-            s1 += w[j] * st[55 + j];
-            s2 += w[j] * t;
-        }
+        double mu, rs, WG[10];
+        conv0_gn_moments(st, w0 + c * 10, T0, eps, mu, rs, WG);
         const double T = (double)T0;
-        const double mu = s1 / T;
-        const double var = fmax(s2 / T - mu * mu, 0.0);
-        const double rs = 1.0 / sqrt(var + (double)eps);
-        const double g = (double)gamma[c], be = (double)beta[c];
-        const double A1 = a[0], Q = (a[1] - be * A1) / g;
+        const double g = (double)gamma[c];
+        const double A1 = a[0], Q = rs * a[1];
         float* out = contrib + ((int64_t)b * C + c) * C0_NS;
 #pragma unroll
         for (int j = 0; j < 10; ++j)
@@ -894,10 +918,10 @@ extern "C" int sc_conv0_gn_bwd(const float* wav, int64_t ldw, const float* w0, c
              "sc_conv0_gn_bwd: C must be 512 (got %d), nwc a multiple of 4", C);
     SC_CHECK(((uintptr_t)dy % 16) == 0 && ((uintptr_t)partial % 16) == 0, "sc_conv0_gn_bwd: alignment");
     const int rpw = (T0 + nwc - 1) / nwc;
-    hipLaunchKernelGGL(conv0_gn_bwd_kernel, dim3(nwc / 4, B), dim3(256), 0, (hipStream_t)stream, wav, ldw, w0, scale, shift, dy, T0, R0, rpw, nwc,
-                       partial);
+    hipLaunchKernelGGL(conv0_gn_bwd_kernel, dim3(nwc / 4, B), dim3(256), 0, (hipStream_t)stream, wav, ldw, w0, scale, shift, stats, nchunk, eps,
+                       (const uint16_t*)dy, T0, R0, rpw, nwc, partial);
     SC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(conv0_gn_bwd_finalize_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, partial, nwc, stats, nchunk, w0, gamma, beta, T0,
+    hipLaunchKernelGGL(conv0_gn_bwd_finalize_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, partial, nwc, stats, nchunk, w0, gamma, T0,
                        eps, contrib);
     SC_LAUNCH_CHECK();
     return 0;

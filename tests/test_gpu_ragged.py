@@ -31,6 +31,25 @@ def setup():
     return model, sd, oracle
 
 
+@pytest.fixture(scope="module")
+def setup_large():
+    """HuBERT-large at two layers (layer_norm extractor, conv bias, utterance-normalised waveform): the only end-to-end consumer of the
+    ragged layer_norm-mode conv 0 (sc_conv0_ln_gelu_seg) and of sc_wav_prep_seg with normalisation"""
+    import dataclasses
+    from speechclip_plus_amd import KWClip_GeneralTransformer, large_parallel_config, random_hubert_state_dict
+    from speechclip_plus_amd.speech_encoder import ARCHS
+    arch = dataclasses.replace(ARCHS["hubert_large_ll60k"], layers=2)
+    sd = random_hubert_state_dict(arch, seed=7123)
+    torch.manual_seed(7123)
+    cfg = large_parallel_config()
+    cfg.audio_encoder.max_audio_len = -1
+    model = KWClip_GeneralTransformer(cfg, device="cuda:0", hubert_state_dict=sd, hubert_arch=arch).eval()
+    with torch.no_grad():
+        model.audio_encoder.weightedsum_layer.weights.copy_(torch.tensor([0.3, -0.2, 0.5]))
+    assert arch.extractor_mode == "layer_norm" and arch.normalize_wav
+    return model
+
+
 # lengths that exercise: pitch 16 (a 10-frame utterance), short last attention blocks, a 128-multiple, the batch maximum,
 # feat_len > valid frames (round(len / 320) vs ceil(len / chunk)), feat_len == valid
 LENS = [48000, 3300, 20000, 30500, 40960, 9000, 47999, 16000, 25000]
@@ -67,6 +86,15 @@ def test_ragged_rows_are_bit_identical_to_the_padded_computation(setup):
     """weighted-sum features (what the head and the branches read) and the pooled embedding, ragged vs every utterance at the
     batch's padded length: equal bit for bit on the frames < feat_len (+ tail_rows), zero behind them."""
     model, sd, oracle = setup
+    _check_ragged_equals_padded(model)
+
+
+def test_ragged_rows_are_bit_identical_to_the_padded_computation_large(setup_large):
+    """the same on HuBERT-large: ragged layer_norm-mode conv 0 (closed-form statistics) on the normalised waveform"""
+    _check_ragged_equals_padded(setup_large)
+
+
+def _check_ragged_equals_padded(model):
     enc = model.audio_encoder
     wav, lens = _batch(LENS).cuda(), torch.tensor(LENS)
     out = {}
