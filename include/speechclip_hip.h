@@ -491,6 +491,25 @@ int sc_vq_soft_bwd(const float* x, int64_t ldx, const float* lse_t, const float*
 int sc_vq_norm_bwd_f32(const float* kw, int64_t ldk, const float* rnorm, const float* dy, int64_t ldy, float eps, float* dx, int64_t ldd,
                        int32_t Nk, int32_t Et, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Keyword detokenisation: per-row top-K over a score matrix (csrc/topk.hip).
+ *   replaces: torch.topk(kw_retrevial_score, K) on the CPU in extract_fixed_keyword_neighbors / extract_dynamic_keyword_neighbors
+ *             (avssl/util/model_utils.py:101, :230), called once per validation batch by kwClip.py:412-433; the scores it selects
+ *             from (F.cosine_similarity, model_utils.py:91-95 / :222-226) come from sc_split3_bf16 + sc_gemm_bf16 above.
+ *   sc_topk_rows_f32   scores [rows, ld] fp32 with V valid columns (ld >= V; columns >= V are padding and never candidates) ->
+ *                      vals [rows, k] fp32, idx [rows, k] int32, best first.  Order: larger value first, lower column first among
+ *                      equal values (a stable descending sort; -0 == +0), NaN above every number (torch.topk), lower column first
+ *                      among NaNs.  1 <= k <= 32; V < k: the tail is -inf / -1; rows == 0: no-op.  Deterministic (no atomics).
+ *                      16-byte loads when ``scores`` is 16-byte aligned and ld % 4 == 0, element loads otherwise.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_topk_rows_f32(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, float* vals, int32_t* idx, void* stream);
+/* vals[row, r] = cosine of kw[row, :E] and table[idx[row, r], :E] (each norm clamped at eps, F.cosine_similarity) with the three sums
+ * accumulated in fp64 and rounded once; idx < 0 (no such neighbour): -inf.  idx must hold indices < V (what sc_topk_rows_f32 wrote).
+ * The fp32 score matrix the selection reads carries the accumulation error of 6 E products (up to 3e-6 at a score of 1); the values
+ * reported next to the tokens do not. */
+int sc_topk_rescore_cos_f32(const float* kw, int64_t ldk, const float* table, int64_t ldt, int32_t V, int32_t E, float eps,
+                            const int32_t* idx, int32_t rows, int32_t k, float* vals, void* stream);
+
 /* Keyword BatchNorm: nn.BatchNorm1d over the keyword positions (avssl/module/speechclip_c_modules/kw_bn.py:167-228).
  *   x [N, E] fp32 (N = batch x keyword slots), per-channel statistics.  training: batch statistics (biased variance for the
  *   normalisation, unbiased for the running estimate; run_mean / run_var updated in place with `momentum`), save_mean / save_rstd

@@ -394,6 +394,8 @@ class KWClip_GeneralTransformer(nn.Module):
         """kwClip.py:195-246: ``{"loss_feats", "log_metrics", "others"}`` (the reference's keys)."""
         with torch.no_grad():
             losses_, log_metrics, others = self.forward(batch)
+        if self._detokenize_enabled() and "text" in batch:
+            others["gold_text"] = batch["text"]                 # kwClip.py:237: the captions the keywords are written next to
         return {"loss_feats": losses_, "log_metrics": log_metrics, "others": others}
 
     def validation_step_end(self, outputs: dict) -> dict:
@@ -428,8 +430,152 @@ class KWClip_GeneralTransformer(nn.Module):
         order = torch.argsort(first)
         img_ids, img_feats = uniq[order], imgs[last[order]]
         score_per_audio = audio @ img_feats.t()
-        return mutualRetrieval(score_per_A=score_per_audio, score_per_B=score_per_audio.t(), AB_answers=ids, BA_answers=img_ids,
-                               recall_at=self.recall_at)
+        result = mutualRetrieval(score_per_A=score_per_audio, score_per_B=score_per_audio.t(), AB_answers=ids, BA_answers=img_ids,
+                                 recall_at=self.recall_at)
+        if self._detokenize_enabled() and outputs and outputs[0].get("keywords", None) is not None:
+            every = int(self.config.log_setting.get("log_detokenize_results_every_n_epoch", 1) or 1)
+            if int(getattr(self, "current_epoch", 0)) % every == 0:
+                self._log_detokenized(outputs)
+        return result
+
+    # --------------------------------------------------------------------------------------------- keyword detokenisation
+    def _detokenize_enabled(self) -> bool:
+        """``log_setting.log_detokenize_results`` (kwClip.py:87-89).  The reference defaults to True; here a config without the key -
+        or without ``log_setting`` - keeps validation exactly as it was."""
+        ls = self.config.get("log_setting", None)
+        return bool(ls.get("log_detokenize_results", False)) if ls is not None else False
+
+    def _token_table(self) -> torch.Tensor:
+        if self.clip is None:
+            raise RuntimeError("keyword detokenisation needs a keyword branch (cascaded+ / hybrid+ recipe): this model has no CLIP text side")
+        return self.clip.model.token_embedding.weight
+
+    def _reduced_to_original(self) -> Optional[torch.Tensor]:
+        """[V] original CLIP token id of every reduced index, on the device (None: full vocabulary)."""
+        ids = self.clip.selected_text_emb_ids
+        if ids is None:
+            return None
+        cached = getattr(self, "_r2o_dev", None)
+        if cached is None or cached.device != self._device or cached.shape[0] != ids.shape[0]:
+            cached = self._r2o_dev = ids.to(self._device)
+        return cached
+
+    @staticmethod
+    def _padded_keywords(outputs: list):
+        """The validation outputs' keyword tensors [b, n_b, E] as one [U, N, E] tensor (N = the largest n_b) and counts [U]."""
+        n_max = max(o["keywords"].shape[1] for o in outputs)
+        kws, lens = [], []
+        for o in outputs:
+            kw = o["keywords"]
+            b, n, _ = kw.shape
+            kws.append(kw if n == n_max else torch.nn.functional.pad(kw, (0, 0, 0, n_max - n)))
+            kl = o.get("keywords_len", None)
+            lens.append(torch.full((b,), n, device=kw.device, dtype=torch.long) if kl is None else kl.to(kw.device).long().clamp(max=n))
+        return torch.cat(kws, dim=0), torch.cat(lens, dim=0)
+
+    def _gold_texts(self, outputs: list) -> list:
+        """One gold entry per utterance: the decoded caption when the CLIP wrapper has a tokenizer, else the caption's token ids up to
+        <|endoftext|>; "" for batches that carried no ``text``."""
+        tok = getattr(self.clip, "tokenizer", None)
+        gold = []
+        for o in outputs:
+            texts = o.get("gold_text", None)
+            if texts is None:
+                gold += [""] * int(o["keywords"].shape[0])
+                continue
+            for sent in texts:
+                ids = torch.as_tensor(sent).reshape(-1).tolist()
+                if tok is not None:
+                    gold.append(tok.decode(ids))
+                else:
+                    gold.append(ids[: ids.index(49407) + 1] if 49407 in ids else [i for i in ids if i != 0])
+        return gold
+
+    def detokenize_keywords(self, outputs: list, K: Optional[int] = None, decode: Optional[Callable] = None) -> list:
+        """kwClip.py:380-437: ``outputs`` as validation_epoch_end takes them -> the reference's JSON structure, one ``{"gold",
+        "neighbors": {"keyword_i": [[token, score] x K]}}`` per utterance with as many keywords as its ``keywords_len``.  ``K``
+        defaults to ``cascaded_branch.keyword.detokenized_K_neighbors`` (10), the scores to its ``retrieve_method`` (cosine)."""
+        from .keyword_neighbors import extract_dynamic_keyword_neighbors, extract_fixed_keyword_neighbors
+        outputs = [o["others"] if "others" in o else o for o in outputs]
+        kwcfg = self.config.model_settings.cascaded_branch.keyword
+        retrieve_method = kwcfg.get("retrieve_method", "cosine")
+        if retrieve_method not in ["cosine", "pseudo_inverse"]:
+            raise NotImplementedError(retrieve_method)
+        K = int(kwcfg.get("detokenized_K_neighbors", 10)) if K is None else int(K)
+        table = self._token_table()
+        gold_texts = self._gold_texts(outputs)
+        if self.keyword_num is not None:
+            kw = torch.cat([o["keywords"].reshape(-1, self.keyword_num, self.subword_embd_dim) for o in outputs], dim=0)
+            return extract_fixed_keyword_neighbors(model=self, K=K, retrieve_method=retrieve_method, tokenEmbeddings=table,
+                                                   keywordEmbeddings=kw, gold_texts=gold_texts, decode=decode)
+        lengths = []
+        for o in outputs:
+            kl = o.get("keywords_len", None)
+            lengths += [int(o["keywords"].shape[1])] * int(o["keywords"].shape[0]) if kl is None else kl.tolist()
+        return self._extract_dynamic(outputs, K, retrieve_method, table, gold_texts, lengths, decode)
+
+    def _extract_dynamic(self, outputs, K, retrieve_method, table, gold_texts, lengths, decode):
+        """extract_dynamic_keyword_neighbors cuts ``gold_texts`` / ``kwEmbedLengths`` by ``config.data.dev_batch_size``; the batches
+        handed in here carry their own sizes, so each goes in as one batch of its own size (one call, one device-to-host copy)."""
+        from .keyword_neighbors import extract_dynamic_keyword_neighbors
+        sizes = [int(o["keywords"].shape[0]) for o in outputs]
+        bs = max(sizes)
+        # pad every batch's slice of the flat lists to ``bs`` entries: the function indexes them by i * bs
+        gold_p, len_p, at = [], [], 0
+        for n in sizes:
+            gold_p += gold_texts[at: at + n] + [None] * (bs - n)
+            len_p += lengths[at: at + n] + [0] * (bs - n)
+            at += n
+
+        class _M:                                           # the three attributes the function reads
+            pass
+        m = _M()
+        m.config = Config({"data": {"dev_batch_size": bs}})
+        m.subword_embd_dim, m.clip, m.device = self.subword_embd_dim, self.clip, self._device
+        m.cascaded_branch = self.cascaded_branch             # its quantiser's VocabTables cache is reused
+        return extract_dynamic_keyword_neighbors(model=m, K=K, retrieve_method=retrieve_method, outputs=outputs, tokenEmbeddings=table,
+                                                 keywordEmbeddings_list=[[o["keywords"]] for o in outputs], gold_texts=gold_p,
+                                                 kwEmbedLengths=len_p, decode=decode)
+
+    def keyword_statistics(self, outputs: list) -> dict:
+        """kwClip.py:325-353: mean / std / norm per keyword slot, kw_mean_mse, kw_std_mse over the epoch's keywords, computed on the
+        device (keyword_neighbors.keyword_statistics) and logged through log_dict."""
+        from .keyword_neighbors import keyword_statistics
+        outputs = [o["others"] if "others" in o else o for o in outputs]
+        kw, lens = self._padded_keywords(outputs)
+        stats = keyword_statistics(kw, self._token_table(), lens)
+        flat = {f"kw_{s}/{k}": v for s in ("mean", "std", "norm") for k, v in stats[s].items()}
+        flat.update({"kw_mean_mse": stats["kw_mean_mse"], "kw_std_mse": stats["kw_std_mse"]})
+        self.log_dict(flat, sync_dist=True)
+        return stats
+
+    def keyword_hit_rate(self, idx: torch.Tensor, gold_text: torch.Tensor) -> dict:
+        """Share of keywords with one of their K neighbours in the caption (keyword_neighbors.keyword_hit_rate); ``idx`` holds
+        indices into this model's token table."""
+        from .keyword_neighbors import keyword_hit_rate
+        return keyword_hit_rate(idx, gold_text, self._reduced_to_original())
+
+    def _log_detokenized(self, outputs: list) -> None:
+        import json
+        import os
+        self.detokenized = self.detokenize_keywords(outputs)
+        self.keyword_stats = self.keyword_statistics(outputs)
+        if all(o.get("gold_text", None) is not None for o in outputs):
+            from .keyword_neighbors import keyword_neighbors
+            kwcfg = self.config.model_settings.cascaded_branch.keyword
+            kw, lens = self._padded_keywords(outputs)
+            _, idx = keyword_neighbors(kw, self._token_table(), int(kwcfg.get("detokenized_K_neighbors", 10)), keywords_len=lens,
+                                       retrieve_method=kwcfg.get("retrieve_method", "cosine"),
+                                       tables=self.cascaded_branch.vector_quantizer._tables)
+            gold = torch.cat([torch.stack([torch.as_tensor(t).reshape(-1) for t in o["gold_text"]]) for o in outputs], dim=0)
+            self.keyword_hits = self.keyword_hit_rate(idx, gold)
+            self.log_dict({"kw_hit_rate": self.keyword_hits["mean"]}, sync_dist=True)
+        root = self.config.get("trainer", {}).get("default_root_dir", None)
+        if root:
+            text_dir = os.path.join(root, "retokenizeText")
+            os.makedirs(text_dir, exist_ok=True)
+            with open(os.path.join(text_dir, f"keywords_ep{int(getattr(self, 'current_epoch', 0))}.json"), "w") as f:
+                json.dump(self.detokenized, f, indent=4)
 
     # --------------------------------------------------------------------------------------------- checkpoints (f4)
     @staticmethod
@@ -491,6 +637,26 @@ class KWClip_GeneralTransformer(nn.Module):
             output = self.parallel_branch(audio_feat=audio_feat, audio_feat_len=audio_feat_len)
         return {"cascaded_audio_feat": output["cascaded_audio_feat"], "parallel_audio_feat": output["parallel_audio_feat"],
                 "vq_results": output["vq_results"], "keywords": output["keywords"]}
+
+    def extract_keywords(self, wav) -> dict:
+        """kwClip.py:1093-1103, the inference entry of the keyword recipes: ``wav`` one 1-D waveform (or a list of them) ->
+        ``{"vq_results", "dsample_results"}`` with ``vq_results["targets"]`` flattened to a list of ORIGINAL CLIP token ids
+        (``clip.reducedl2Original`` when the vocabulary is reduced; slots past an utterance's ``dsample_feats_length`` included, as
+        in the reference)."""
+        if self.cascaded_branch is None:
+            raise RuntimeError("extract_keywords needs a keyword branch (cascaded+ / hybrid+ recipe)")
+        if isinstance(wav, torch.Tensor) and wav.dim() == 1:
+            wav = [wav]
+        wav, wav_len = self.processWavs(wav)
+        with torch.no_grad():
+            audio_feat, audio_feat_len = self.forward_audio(wav, wav_len)
+            output = self.cascaded_branch(audio_feat=audio_feat, audio_feat_len=audio_feat_len, otherInputs={})
+        vq_results, dsample_results = output["vq_results"], output["dsample_results"]
+        targets = vq_results["targets"].flatten().tolist()
+        if self.clip.selected_text_emb_ids is not None:
+            targets = [self.clip.reducedl2Original[t] for t in targets]
+        vq_results["targets"] = targets
+        return {"vq_results": vq_results, "dsample_results": dsample_results}
 
     def feature_extractor_s3prl(self, wav) -> Tuple[torch.Tensor, Tuple]:
         """kwClip.py:965-997: the HuBERT states (fresh tensors: the encoder clones what it hands out) followed by the branch

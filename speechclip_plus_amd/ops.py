@@ -747,24 +747,31 @@ def vq_prep(kw: torch.Tensor, eps: float = 1e-8):
     return kwn_T, rnorm
 
 
-def split3_bf16(x: torch.Tensor, side: int, row_scale: Optional[torch.Tensor] = None, rows_pad: int = 128, cols_pad: int = 64) -> torch.Tensor:
+def split3_bf16(x: torch.Tensor, side: int, row_scale: Optional[torch.Tensor] = None, rows_pad: int = 128, cols_pad: int = 64,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [R, E] fp32 (* row_scale [R]) -> its three-way bf16 split as the six K-blocks of an fp32-accurate product on the bf16 matrix
-    pipe (sc_split3_bf16): [Rp, 6 Ep] bf16, Rp / Ep = R / E rounded up to ``rows_pad`` / ``cols_pad``; side 0 and side 1 pair up."""
+    pipe (sc_split3_bf16): [Rp, 6 Ep] bf16, Rp / Ep = R / E rounded up to ``rows_pad`` / ``cols_pad``; side 0 and side 1 pair up.
+    ``out``: a caller-owned [Rp, 6 Ep] bf16 buffer to write into (keyword_neighbors reuses one across chunks)."""
     assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and side in (0, 1)
     R, E = x.shape
     Rp, Ep = -(-R // rows_pad) * rows_pad, -(-E // cols_pad) * cols_pad
-    out = torch.empty(Rp, 6 * Ep, device=x.device, dtype=torch.bfloat16)
+    if out is None:
+        out = torch.empty(Rp, 6 * Ep, device=x.device, dtype=torch.bfloat16)
+    assert out.dtype == torch.bfloat16 and tuple(out.shape) == (Rp, 6 * Ep) and out.is_contiguous()
     check(lib().sc_split3_bf16(_p(x), x.stride(0), _p(row_scale), R, E, _p(out), Rp, Ep, side, _stream()), "sc_split3_bf16")
     return out
 
 
-def cosine_scores_split(kw: torch.Tensor, rnorm: torch.Tensor, table_split: torch.Tensor, Vp: int) -> torch.Tensor:
+def cosine_scores_split(kw: torch.Tensor, rnorm: Optional[torch.Tensor], table_split: torch.Tensor, Vp: int,
+                        out: Optional[torch.Tensor] = None, split_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """cos [Nkp, Vp] fp32 = (kw * rnorm) . table_n^T to fp32 accuracy: ONE bf16 GEMM over the six K-blocks of the three-way splits
-    (``table_split`` = split3_bf16(normalised table, side 1), rows padded to Vp)."""
-    A = split3_bf16(kw, 0, row_scale=rnorm)
+    (``table_split`` = split3_bf16(normalised table, side 1), rows padded to Vp).  ``out`` [Nkp, Vp] fp32 / ``split_out`` [Nkp, K6]
+    bf16: caller-owned buffers for the scores and the split of ``kw`` (none allocated here then)."""
+    A = split3_bf16(kw, 0, row_scale=rnorm, out=split_out)
     K6 = A.shape[1]
     assert table_split.shape == (Vp, K6), (table_split.shape, Vp, K6)
-    cos = torch.empty(A.shape[0], Vp, device=kw.device, dtype=torch.float32)
+    cos = torch.empty(A.shape[0], Vp, device=kw.device, dtype=torch.float32) if out is None else out
+    assert cos.dtype == torch.float32 and tuple(cos.shape) == (A.shape[0], Vp) and cos.is_contiguous()
     gemm_raw(A, K6, table_split, K6, cos, Vp, A.shape[0], Vp, K6, out_f32=True)
     return cos
 
@@ -796,6 +803,38 @@ def sgemm_mfma(A: torch.Tensor, Bm: torch.Tensor, a_kmajor: bool = False, b_kmaj
         ev1.record()
         _timer.add("sgemm_mfma_f32", ev0, ev1, 2.0 * M * N * K)
     return out
+
+
+def topk_rows(scores: torch.Tensor, V: int, k: int, vals: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None):
+    """scores [rows, >= V] fp32 (unit column stride, any row pitch and base alignment) -> (vals [rows, k] fp32, idx [rows, k] int32): the
+    k largest of the first V columns of every row, best first - ties to the lower column, NaN above every number, -inf / -1 behind
+    the V-th entry when V < k (sc_topk_rows_f32, csrc/topk.hip).  ``vals`` / ``idx``: caller-owned contiguous outputs."""
+    assert scores.dtype == torch.float32 and scores.dim() == 2 and (scores.stride(1) == 1 or scores.shape[1] == 1)
+    rows = scores.shape[0]
+    assert scores.shape[1] >= V, (scores.shape, V)
+    ld = scores.stride(0) if rows > 1 else max(V, 1)
+    if vals is None:
+        vals = torch.empty(rows, k, device=scores.device, dtype=torch.float32)
+    if idx is None:
+        idx = torch.empty(rows, k, device=scores.device, dtype=torch.int32)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
+    assert tuple(vals.shape) == (rows, k) and tuple(idx.shape) == (rows, k)
+    check(lib().sc_topk_rows_f32(_p(scores) if rows else ctypes.c_void_p(0), ld, rows, V, k, _p(vals) if rows else ctypes.c_void_p(0),
+                                 _p(idx) if rows else ctypes.c_void_p(0), _stream()), "sc_topk_rows_f32")
+    return vals, idx
+
+
+def topk_rescore_cos(kw: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, vals: torch.Tensor, eps: float = 1e-8) -> torch.Tensor:
+    """vals[r, j] <- cos(kw[r], table[idx[r, j]]) accumulated in fp64 (sc_topk_rescore_cos_f32): kw [rows, E], table [V, E] fp32, idx /
+    vals [rows, k] int32 / fp32 contiguous (idx as ops.topk_rows wrote it; -1 -> -inf)."""
+    rows, E = kw.shape
+    assert kw.dtype == torch.float32 and table.dtype == torch.float32 and kw.stride(1) == 1 and table.stride(1) == 1 and table.shape[1] == E
+    assert idx.dtype == torch.int32 and vals.dtype == torch.float32 and idx.is_contiguous() and vals.is_contiguous()
+    assert idx.shape == vals.shape and idx.shape[0] == rows
+    if rows:
+        check(lib().sc_topk_rescore_cos_f32(_p(kw), kw.stride(0), _p(table), table.stride(0), table.shape[0], E, float(eps), _p(idx), rows,
+                                            idx.shape[1], _p(vals), _stream()), "sc_topk_rescore_cos_f32")
+    return vals
 
 
 def vq_rowstats(x: torch.Tensor, V: int, temp: float, mask_cols=(0, 2, 3)):
