@@ -29,7 +29,7 @@ extern "C" {
 typedef uint16_t sc_bf16;
 
 const char* sc_last_error(void);
-int sc_abi_version(void);     /* 4 since round 4 (sc_segments; sc_gemm_args / sc_hubert_layer_args grew the segment fields) */
+int sc_abi_version(void);     /* 5: sc_adam_f32 takes its betas as doubles; 4 since round 4 (sc_segments; sc_gemm_args / sc_hubert_layer_args grew the segment fields) */
 int sc_is_diag_build(void);   /* 1: libspeechclip_hip_diag.so - the same sources built with SC_DIAG_BUILD: also holds the diagnostic kernels
                                  (sc_gemm_args.tile 32 = timing only, RESULTS WRONG; 34 = stamped) and the LayerNorm-folded GEMMs; the
                                  product library refuses both */
@@ -765,9 +765,9 @@ int sc_vit_embed_ln_bf16(const float* G, const float* cls, const float* pos, con
  * trainer.gradient_clip_val).  sumsq: partial sums of squares for the global norm.
  * ---------------------------------------------------------------------------------------------- */
 int sc_sumsq_f32(const float* x, int64_t n, float* partial, int32_t nblk, void* stream);
-int sc_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+int sc_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
                 float eps, float weight_decay, int32_t step, const float* gnorm_sq_partial, int32_t nblk,
-                float max_norm, void* stream);
+                float max_norm, void* stream);      /* betas as doubles (ABI 5): 1 - beta and 1 - beta^step are formed in double, rounded once */
 
 /* ------------------------------------------------------------------------------------------------
  * Keyword prompt of the cascaded branches in the text tower's packed rows (round 4; replaces the ~35 element-wise torch launches of

@@ -242,7 +242,7 @@ SIGNATURES = {
     "sc_rt_softmax_bwd_reduce": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "sc_rt_l2norm_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "sc_sumsq_f32": [c_void_p, c_i64, c_void_p, c_int, c_void_p],
-    "sc_adam_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_int, c_float, c_void_p],
+    "sc_adam_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_float, ctypes.c_double, ctypes.c_double, c_float, c_float, c_int, c_void_p, c_int, c_float, c_void_p],
 }
 
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libspeechclip_hip_diag.so")

@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x,
 
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
-                                                   float beta1, float beta2, float eps, float wd, float bc1,
+                                                   float beta1, float omb1, float beta2, float omb2, float eps, float wd, float bc1,
                                                    float bc2_sqrt, const float* __restrict__ gn_partial, int nblk,
                                                    float max_norm) {
     float clip = 1.f;
@@ -302,8 +302,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         float gi = g[i] * clip;
         const float pi = p[i];
         gi = fmaf(wd, pi, gi);
-        const float mi = beta1 * m[i] + (1.f - beta1) * gi;
-        const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
+        const float mi = beta1 * m[i] + omb1 * gi;
+        const float vi = beta2 * v[i] + omb2 * gi * gi;
         m[i] = mi;
         v[i] = vi;
         const float denom = sqrtf(vi) / bc2_sqrt + eps;
@@ -363,14 +363,18 @@ extern "C" int sc_sumsq_f32(const float* x, int64_t n, float* partial, int32_t n
     return 0;
 }
 
-extern "C" int sc_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+// The betas arrive as doubles: 1 - beta and the bias corrections 1 - beta^step are formed in double and rounded ONCE.  In single
+// precision 1 - 0.98f is already 9.5e-7 off (1 - 0.999f: 1.3e-5), which went straight into v (tests/test_gpu_loss_optim.py).
+extern "C" int sc_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
                            float eps, float weight_decay, int32_t step, const float* gnorm_sq_partial, int32_t nblk,
                            float max_norm, void* stream) {
     SC_CHECK(p && g && m && v && n > 0 && step >= 1, "sc_adam_f32: bad args");
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
+    SC_CHECK(beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1., "sc_adam_f32: betas (%g, %g)", beta1, beta2);
+    const float bc1 = (float)(1. - pow(beta1, (double)step));
+    const float bc2_sqrt = (float)sqrt(1. - pow(beta2, (double)step));
     const int grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, gnorm_sq_partial, nblk, max_norm);
+    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, (float)beta1, (float)(1. - beta1),
+                       (float)beta2, (float)(1. - beta2), eps, weight_decay, bc1, bc2_sqrt, gnorm_sq_partial, nblk, max_norm);
     SC_LAUNCH_CHECK();
     return 0;
 }

@@ -1260,7 +1260,8 @@ def sumsq(x: torch.Tensor, nblk: int = 1024) -> torch.Tensor:
 def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float, beta1: float, beta2: float,
               eps: float, weight_decay: float, step: int, gn_partial: Optional[torch.Tensor], max_norm: float) -> None:
     nblk = gn_partial.numel() if gn_partial is not None else 0
-    check(lib().sc_adam_f32(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, step,
+    # the betas cross as doubles: 1 - beta and the bias corrections are formed in double on the host side of the entry point
+    check(lib().sc_adam_f32(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, float(beta1), float(beta2), eps, weight_decay, step,
                             _p(gn_partial), nblk, max_norm, _stream()), "sc_adam_f32")
 
 

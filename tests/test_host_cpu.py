@@ -23,7 +23,7 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/speechclip_hip.h but not exported"
     assert set(_lib.SIGNATURES) | {"sc_last_error", "sc_hash32", "sc_infonce_workspace_floats", "sc_workspace_bytes", "sc_sizeof"} == declared
-    assert lib.sc_abi_version() == 4
+    assert lib.sc_abi_version() == 5
     # the ctypes mirrors of the argument structs have the C structs' sizes (checked again at every load: _lib.lib())
     for what, cls in enumerate((_lib.GemmArgs, _lib.HubertLayerArgs, _lib.RtGemmArgs, _lib.RtLnArgs, _lib.RtLnBwdArgs)):
         assert lib.sc_sizeof(what) == ctypes.sizeof(cls), cls.__name__
