@@ -139,34 +139,74 @@ __global__ __launch_bounds__(256) void layernorm16_kernel(const uint16_t* __rest
 }
 
 // ---------------------------------------------------------------------------------------- weighted sum
-// out[b, t + row_off, :] = sum_n w[n] * h[n, b, t, :]   (t + row_off < R)
-__global__ __launch_bounds__(256) void wsum_fwd_kernel(const uint16_t* __restrict__ h, const float* __restrict__ w,
-                                                       int NL, uint16_t* __restrict__ out, int B, int R, int D,
-                                                       int row_off) {
+// The states h[n] come in one of two row layouts; the kernels below are written once and take the layout as a policy (a kernel
+// argument by value).  A layout says how many rows the grid-stride loop walks, how far two layers of h are apart, and which row
+// of h (src) and of out / g (out) a loop row stands for.  The loop domain differs per layout on purpose: it decides which thread adds
+// which element, hence the bits of the backward's dw_partial.
+struct RowRef {
+    int64_t src, out;
+    bool live;
+};
+
+// uniform [B, R, D]: out[b, t + row_off, :] = sum_n w[n] * h[n, b, t, :]   (t + row_off < R); the loop walks the SOURCE rows, rows of out
+// that no source row maps to are left untouched
+struct UniformRows {
+    int B, R;
+    static constexpr bool kZeroDeadRows = false;
+    __device__ __forceinline__ int64_t count() const { return (int64_t)B * R; }
+    __device__ __forceinline__ int64_t plane(int D) const { return (int64_t)B * R * D; }
+    __device__ __forceinline__ RowRef at(int64_t row, int row_off) const {
+        const int t = (int)(row % R);
+        return {row, row + row_off, t + row_off < R};
+    }
+};
+
+// ragged rows (sc_segments, round 4): utterance b's frames at rows row0[b] + t of every h[n], out / g a UNIFORM [B, Rout, D] buffer:
+// out[b, s] = sum_n w[n] h[n, row0[b] + s - row_off] for 0 <= s - row_off < pitch_b, zero elsewhere; the loop walks the OUTPUT rows, every
+// row of out is written
+struct SegRows {
+    const int32_t* row0;
+    int B, Rout;
+    int64_t plane_;
+    static constexpr bool kZeroDeadRows = true;
+    __device__ __forceinline__ int64_t count() const { return (int64_t)B * Rout; }
+    __device__ __forceinline__ int64_t plane(int) const { return plane_; }
+    __device__ __forceinline__ RowRef at(int64_t orow, int row_off) const {
+        const int b = (int)(orow / Rout), t = (int)(orow % Rout) - row_off;
+        const int r0 = row0[b], pitch = row0[b + 1] - r0;
+        return {(int64_t)(r0 + t), orow, t >= 0 && t < pitch};
+    }
+};
+
+template <typename Rows>
+__global__ __launch_bounds__(256) void wsum_fwd_kernel(const uint16_t* __restrict__ h, const float* __restrict__ w, int NL,
+                                                       uint16_t* __restrict__ out, Rows rows, int D, int row_off) {
     const int64_t chunks_per_row = D >> 3;
-    const int64_t total = (int64_t)B * R * chunks_per_row;
-    const int64_t plane = (int64_t)B * R * D;
+    const int64_t total = rows.count() * chunks_per_row;
+    const int64_t plane = rows.plane(D);
     float wl[32];
 #pragma unroll
     for (int n = 0; n < 32; ++n) wl[n] = n < NL ? w[n] : 0.f;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
         const int64_t row = q / chunks_per_row;
         const int cc = (int)(q % chunks_per_row);
-        const int t = (int)(row % R);
-        if (t + row_off >= R) continue;
+        const RowRef m = rows.at(row, row_off);
+        if (!Rows::kZeroDeadRows && !m.live) continue;
         float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const uint16_t* src = h + row * D + cc * 8;
+        if (m.live) {
+            const uint16_t* src = h + m.src * D + cc * 8;
 #pragma unroll 4
-        for (int n = 0; n < NL; ++n) {
-            const uint4 u = *(const uint4*)(src + n * plane);
-            const float wn = wl[n];
-            acc[0] += wn * bflo(u.x); acc[1] += wn * bfhi(u.x); acc[2] += wn * bflo(u.y); acc[3] += wn * bfhi(u.y);
-            acc[4] += wn * bflo(u.z); acc[5] += wn * bfhi(u.z); acc[6] += wn * bflo(u.w); acc[7] += wn * bfhi(u.w);
+            for (int n = 0; n < NL; ++n) {
+                const uint4 u = *(const uint4*)(src + n * plane);
+                const float wn = wl[n];
+                acc[0] += wn * bflo(u.x); acc[1] += wn * bfhi(u.x); acc[2] += wn * bflo(u.y); acc[3] += wn * bfhi(u.y);
+                acc[4] += wn * bflo(u.z); acc[5] += wn * bfhi(u.z); acc[6] += wn * bflo(u.w); acc[7] += wn * bfhi(u.w);
+            }
         }
         uint4 o;
         o.x = pack2bf(acc[0], acc[1]); o.y = pack2bf(acc[2], acc[3]);
         o.z = pack2bf(acc[4], acc[5]); o.w = pack2bf(acc[6], acc[7]);
-        *(uint4*)(out + (row + row_off) * D + cc * 8) = o;
+        *(uint4*)(out + m.out * D + cc * 8) = o;
     }
 }
 
@@ -184,30 +224,29 @@ __device__ __forceinline__ void load_g8(const GT* gp, f32x4& g0, f32x4& g1) {
     }
 }
 
-// dw_partial[blk, n] = sum over this block's elements of g[b, t + row_off, d] * (h[n, b, t, d] - h[NL - 1, b, t, d])
+// dw_partial[blk, n] = sum over this block's elements of g[out row, d] * (h[n, src row, d] - h[NL - 1, src row, d])
 // The caller only uses the softmax-projected combination w_n (d_n - sum_m w_m d_m), which is invariant under a common shift of
 // the d_n: subtracting the LAST layer element-wise BEFORE the accumulation removes the large common part <g, h> that the
 // projection would cancel afterwards (the differences between layers of a residual stream are one to two orders of magnitude
 // smaller than the states themselves: summing first and subtracting later costs that many digits of the fp32 accumulators).
-template <typename GT>
-__global__ __launch_bounds__(256) void wsum_bwd_kernel(const uint16_t* __restrict__ h, const GT* __restrict__ g,
-                                                       int NL, float* __restrict__ dw_partial, int B, int R, int D,
-                                                       int row_off) {
+template <typename GT, typename Rows>
+__global__ __launch_bounds__(256) void wsum_bwd_kernel(const uint16_t* __restrict__ h, const GT* __restrict__ g, int NL,
+                                                       float* __restrict__ dw_partial, Rows rows, int D, int row_off) {
     __shared__ float red[4][32];
     const int64_t chunks_per_row = D >> 3;
-    const int64_t total = (int64_t)B * R * chunks_per_row;
-    const int64_t plane = (int64_t)B * R * D;
+    const int64_t total = rows.count() * chunks_per_row;
+    const int64_t plane = rows.plane(D);
     float acc[32];
 #pragma unroll
     for (int n = 0; n < 32; ++n) acc[n] = 0.f;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
         const int64_t row = q / chunks_per_row;
         const int cc = (int)(q % chunks_per_row);
-        const int t = (int)(row % R);
-        if (t + row_off >= R) continue;
+        const RowRef m = rows.at(row, row_off);
+        if (!m.live) continue;
         f32x4 g0, g1;
-        load_g8(g + (row + row_off) * D + cc * 8, g0, g1);
-        const uint16_t* src = h + row * D + cc * 8;
+        load_g8(g + m.out * D + cc * 8, g0, g1);
+        const uint16_t* src = h + m.src * D + cc * 8;
         const uint4 r = *(const uint4*)(src + (int64_t)(NL - 1) * plane);
 #pragma unroll
         for (int n = 0; n < 31; ++n) {
@@ -386,28 +425,30 @@ __device__ __forceinline__ void load_row_norm(const uint16_t* __restrict__ src, 
         for (int j = 0; j < 8; ++j) xh[i][j] *= rstd;
 }
 
-template <int NE>
-__global__ __launch_bounds__(256) void wsum_norm_fwd_kernel(const uint16_t* __restrict__ h, const float* __restrict__ w,
-                                                            int NL, uint16_t* __restrict__ out, int B, int R, int D,
-                                                            int row_off) {
+template <int NE, typename Rows>
+__global__ __launch_bounds__(256) void wsum_norm_fwd_kernel(const uint16_t* __restrict__ h, const float* __restrict__ w, int NL,
+                                                            uint16_t* __restrict__ out, Rows rows, int D, int row_off) {
     const int lane = threadIdx.x & 63;
     const int nchunks = D >> 3;
-    const int64_t rows = (int64_t)B * R, plane = rows * D;
-    for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (int64_t)gridDim.x * 4) {
-        if ((int)(row % R) + row_off >= R) continue;
+    const int64_t count = rows.count(), plane = rows.plane(D);
+    for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < count; row += (int64_t)gridDim.x * 4) {
+        const RowRef m = rows.at(row, row_off);
+        if (!Rows::kZeroDeadRows && !m.live) continue;
         float acc[NE][8];
 #pragma unroll
         for (int i = 0; i < NE; ++i)
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
-        for (int n = 0; n < NL; ++n) {
-            float xh[NE][8];
-            load_row_norm<NE>(h + n * plane + row * D, lane, nchunks, D, 1e-5f, xh);
-            const float wn = w[n];
+        if (m.live) {
+            for (int n = 0; n < NL; ++n) {
+                float xh[NE][8];
+                load_row_norm<NE>(h + n * plane + m.src * D, lane, nchunks, D, 1e-5f, xh);
+                const float wn = w[n];
 #pragma unroll
-            for (int i = 0; i < NE; ++i)
+                for (int i = 0; i < NE; ++i)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) acc[i][j] += wn * xh[i][j];
+                    for (int j = 0; j < 8; ++j) acc[i][j] += wn * xh[i][j];
+            }
         }
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
@@ -416,32 +457,32 @@ __global__ __launch_bounds__(256) void wsum_norm_fwd_kernel(const uint16_t* __re
                 uint4 o;
                 o.x = pack2bf(acc[i][0], acc[i][1]); o.y = pack2bf(acc[i][2], acc[i][3]);
                 o.z = pack2bf(acc[i][4], acc[i][5]); o.w = pack2bf(acc[i][6], acc[i][7]);
-                *(uint4*)(out + (row + row_off) * D + ch * 8) = o;
+                *(uint4*)(out + m.out * D + ch * 8) = o;
             }
         }
     }
 }
 
-template <int NE, typename GT>
-__global__ __launch_bounds__(256) void wsum_norm_bwd_kernel(const uint16_t* __restrict__ h, const GT* __restrict__ g,
-                                                            int NL, float* __restrict__ dw_partial, int B, int R, int D,
-                                                            int row_off) {
+template <int NE, typename GT, typename Rows>
+__global__ __launch_bounds__(256) void wsum_norm_bwd_kernel(const uint16_t* __restrict__ h, const GT* __restrict__ g, int NL,
+                                                            float* __restrict__ dw_partial, Rows rows, int D, int row_off) {
     __shared__ float red[4][32];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nchunks = D >> 3;
-    const int64_t rows = (int64_t)B * R, plane = rows * D;
+    const int64_t count = rows.count(), plane = rows.plane(D);
     float accn[32];
 #pragma unroll
     for (int n = 0; n < 32; ++n) accn[n] = 0.f;
-    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
-        if ((int)(row % R) + row_off >= R) continue;
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < count; row += (int64_t)gridDim.x * 4) {
+        const RowRef m = rows.at(row, row_off);
+        if (!m.live) continue;
         float gv[NE][8];
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
             const int ch = lane + i * 64;
             if (ch < nchunks) {
                 f32x4 g0, g1;
-                load_g8(g + (row + row_off) * D + ch * 8, g0, g1);
+                load_g8(g + m.out * D + ch * 8, g0, g1);
                 gv[i][0] = g0[0]; gv[i][1] = g0[1]; gv[i][2] = g0[2]; gv[i][3] = g0[3];
                 gv[i][4] = g1[0]; gv[i][5] = g1[1]; gv[i][6] = g1[2]; gv[i][7] = g1[3];
             } else {
@@ -450,12 +491,12 @@ __global__ __launch_bounds__(256) void wsum_norm_bwd_kernel(const uint16_t* __re
             }
         }
         float xr[NE][8];                 // reference layer (the last one): see wsum_bwd_kernel
-        load_row_norm<NE>(h + (int64_t)(NL - 1) * plane + row * D, lane, nchunks, D, 1e-5f, xr);
+        load_row_norm<NE>(h + (int64_t)(NL - 1) * plane + m.src * D, lane, nchunks, D, 1e-5f, xr);
 #pragma unroll
         for (int n = 0; n < 31; ++n) {
             if (n < NL - 1) {
                 float xh[NE][8];
-                load_row_norm<NE>(h + n * plane + row * D, lane, nchunks, D, 1e-5f, xh);
+                load_row_norm<NE>(h + n * plane + m.src * D, lane, nchunks, D, 1e-5f, xh);
                 float d = 0.f;
 #pragma unroll
                 for (int i = 0; i < NE; ++i)
@@ -501,42 +542,9 @@ __global__ __launch_bounds__(256) void posconv_prep_kernel(const uint16_t* __res
 
 
 // ---------------------------------------------------------------------------------------- ragged rows (sc_segments, round 4)
-// Weighted sum from the segment layout (utterance b's frames at rows row0[b] + t of every h[n]) into a UNIFORM [B, Rout, D] buffer:
-// out[b, s] = sum_n w[n] h[n, row0[b] + s - row_off] for 0 <= s - row_off < pitch_b, zero elsewhere (every row of out is written).
-__global__ __launch_bounds__(256) void wsum_fwd_seg_kernel(const uint16_t* __restrict__ h, const float* __restrict__ w, int NL,
-                                                           uint16_t* __restrict__ out, const int32_t* __restrict__ row0, int B, int Rout,
-                                                           int D, int row_off, int64_t plane) {
-    const int64_t chunks_per_row = D >> 3;
-    const int64_t total = (int64_t)B * Rout * chunks_per_row;
-    float wl[32];
-#pragma unroll
-    for (int n = 0; n < 32; ++n) wl[n] = n < NL ? w[n] : 0.f;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t orow = q / chunks_per_row;
-        const int cc = (int)(q % chunks_per_row);
-        const int b = (int)(orow / Rout), t = (int)(orow % Rout) - row_off;
-        const int r0 = row0[b], pitch = row0[b + 1] - r0;
-        float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (t >= 0 && t < pitch) {
-            const uint16_t* src = h + (int64_t)(r0 + t) * D + cc * 8;
-#pragma unroll 4
-            for (int n = 0; n < NL; ++n) {
-                const uint4 u = *(const uint4*)(src + n * plane);
-                const float wn = wl[n];
-                acc[0] += wn * bflo(u.x); acc[1] += wn * bfhi(u.x); acc[2] += wn * bflo(u.y); acc[3] += wn * bfhi(u.y);
-                acc[4] += wn * bflo(u.z); acc[5] += wn * bfhi(u.z); acc[6] += wn * bflo(u.w); acc[7] += wn * bfhi(u.w);
-            }
-        }
-        uint4 o;
-        o.x = pack2bf(acc[0], acc[1]); o.y = pack2bf(acc[2], acc[3]);
-        o.z = pack2bf(acc[4], acc[5]); o.w = pack2bf(acc[6], acc[7]);
-        *(uint4*)(out + orow * D + cc * 8) = o;
-    }
-}
-
-// The same sum for a layer count known at compile time (13 / 25: base / large), one 16-byte chunk per thread (round 5): grid (chunks of an
-// utterance's Rout rows / 256, B) - no 64-bit divisions, no grid-stride loop -, the NLT weights in registers under constant indices (the
-// generic kernel above indexes its weight array with a loop variable: v_movrel sequences), all NLT loads of a chunk in flight before
+// wsum_fwd_kernel<SegRows>'s sum for a layer count known at compile time (13 / 25: base / large), one 16-byte chunk per thread (round 5): grid
+// (chunks of an utterance's Rout rows / 256, B) - no 64-bit divisions, no grid-stride loop -, the NLT weights in registers under constant indices
+// (the generic kernel indexes its weight array with a loop variable: v_movrel sequences), all NLT loads of a chunk in flight before
 // the first multiply-add.  Same additions in the same order: same bits.
 template <int NLT>
 __global__ __launch_bounds__(256) void wsum_fwd_seg_fixed_kernel(const uint16_t* __restrict__ h, const float* __restrict__ w,
@@ -567,50 +575,7 @@ __global__ __launch_bounds__(256) void wsum_fwd_seg_fixed_kernel(const uint16_t*
     *(uint4*)(out + ((int64_t)b * Rout + s) * D + cc * 8) = o;
 }
 
-// as wsum_bwd_kernel, g in the uniform [B, Rout, D] layout, h in the segment layout
-template <typename GT>
-__global__ __launch_bounds__(256) void wsum_bwd_seg_kernel(const uint16_t* __restrict__ h, const GT* __restrict__ g, int NL,
-                                                           float* __restrict__ dw_partial, const int32_t* __restrict__ row0, int B, int Rout,
-                                                           int D, int row_off, int64_t plane) {
-    __shared__ float red[4][32];
-    const int64_t chunks_per_row = D >> 3;
-    const int64_t total = (int64_t)B * Rout * chunks_per_row;
-    float acc[32];
-#pragma unroll
-    for (int n = 0; n < 32; ++n) acc[n] = 0.f;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t orow = q / chunks_per_row;
-        const int cc = (int)(q % chunks_per_row);
-        const int b = (int)(orow / Rout), t = (int)(orow % Rout) - row_off;
-        const int r0 = row0[b], pitch = row0[b + 1] - r0;
-        if (t < 0 || t >= pitch) continue;
-        f32x4 g0, g1;
-        load_g8(g + orow * D + cc * 8, g0, g1);
-        const uint16_t* src = h + (int64_t)(r0 + t) * D + cc * 8;
-        const uint4 r = *(const uint4*)(src + (int64_t)(NL - 1) * plane);
-#pragma unroll
-        for (int n = 0; n < 31; ++n) {
-            if (n < NL - 1) {
-                const uint4 u = *(const uint4*)(src + n * plane);
-                acc[n] += g0[0] * (bflo(u.x) - bflo(r.x)) + g0[1] * (bfhi(u.x) - bfhi(r.x)) + g0[2] * (bflo(u.y) - bflo(r.y)) +
-                          g0[3] * (bfhi(u.y) - bfhi(r.y)) + g1[0] * (bflo(u.z) - bflo(r.z)) + g1[1] * (bfhi(u.z) - bfhi(r.z)) +
-                          g1[2] * (bflo(u.w) - bflo(r.w)) + g1[3] * (bfhi(u.w) - bfhi(r.w));
-            }
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int n = 0; n < 32; ++n) {
-        const float s = wave_sum(acc[n]);
-        if (lane == 0) red[wave][n] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NL)
-        dw_partial[(int64_t)blockIdx.x * NL + threadIdx.x] =
-            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-
-// wsum_bwd_seg_kernel for a layer count known at compile time (round 5): the same elements per thread in the same order (grid-stride over the
+// wsum_bwd_kernel<GT, SegRows> for a layer count known at compile time (round 5): the same elements per thread in the same order (grid-stride over the
 // 16-byte chunks of the uniform gradient), but 32-bit index arithmetic (the generic kernel spends two 64-bit divisions per chunk), every load of a
 // chunk in flight before the first use, and NLT - 1 wavefront reductions instead of 32.
 template <int NLT, typename GT>
@@ -651,102 +616,6 @@ __global__ __launch_bounds__(256) void wsum_bwd_seg_fixed_kernel(const uint16_t*
     __syncthreads();
     if (threadIdx.x < NLT)
         dw_partial[(int64_t)blockIdx.x * NLT + threadIdx.x] =
-            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-
-template <int NE>
-__global__ __launch_bounds__(256) void wsum_norm_fwd_seg_kernel(const uint16_t* __restrict__ h, const float* __restrict__ w, int NL,
-                                                                uint16_t* __restrict__ out, const int32_t* __restrict__ row0, int B, int Rout,
-                                                                int D, int row_off, int64_t plane) {
-    const int lane = threadIdx.x & 63;
-    const int nchunks = D >> 3;
-    const int64_t orows = (int64_t)B * Rout;
-    for (int64_t orow = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); orow < orows; orow += (int64_t)gridDim.x * 4) {
-        const int b = (int)(orow / Rout), t = (int)(orow % Rout) - row_off;
-        const int r0 = row0[b], pitch = row0[b + 1] - r0;
-        float acc[NE][8];
-#pragma unroll
-        for (int i = 0; i < NE; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
-        if (t >= 0 && t < pitch) {
-            for (int n = 0; n < NL; ++n) {
-                float xh[NE][8];
-                load_row_norm<NE>(h + n * plane + (int64_t)(r0 + t) * D, lane, nchunks, D, 1e-5f, xh);
-                const float wn = w[n];
-#pragma unroll
-                for (int i = 0; i < NE; ++i)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[i][j] += wn * xh[i][j];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NE; ++i) {
-            const int ch = lane + i * 64;
-            if (ch < nchunks) {
-                uint4 o;
-                o.x = pack2bf(acc[i][0], acc[i][1]); o.y = pack2bf(acc[i][2], acc[i][3]);
-                o.z = pack2bf(acc[i][4], acc[i][5]); o.w = pack2bf(acc[i][6], acc[i][7]);
-                *(uint4*)(out + orow * D + ch * 8) = o;
-            }
-        }
-    }
-}
-
-template <int NE, typename GT>
-__global__ __launch_bounds__(256) void wsum_norm_bwd_seg_kernel(const uint16_t* __restrict__ h, const GT* __restrict__ g, int NL,
-                                                                float* __restrict__ dw_partial, const int32_t* __restrict__ row0, int B,
-                                                                int Rout, int D, int row_off, int64_t plane) {
-    __shared__ float red[4][32];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nchunks = D >> 3;
-    const int64_t orows = (int64_t)B * Rout;
-    float accn[32];
-#pragma unroll
-    for (int n = 0; n < 32; ++n) accn[n] = 0.f;
-    for (int64_t orow = (int64_t)blockIdx.x * 4 + wave; orow < orows; orow += (int64_t)gridDim.x * 4) {
-        const int b = (int)(orow / Rout), t = (int)(orow % Rout) - row_off;
-        const int r0 = row0[b], pitch = row0[b + 1] - r0;
-        if (t < 0 || t >= pitch) continue;
-        const int64_t row = r0 + t;
-        float gv[NE][8];
-#pragma unroll
-        for (int i = 0; i < NE; ++i) {
-            const int ch = lane + i * 64;
-            if (ch < nchunks) {
-                f32x4 g0, g1;
-                load_g8(g + orow * D + ch * 8, g0, g1);
-                gv[i][0] = g0[0]; gv[i][1] = g0[1]; gv[i][2] = g0[2]; gv[i][3] = g0[3];
-                gv[i][4] = g1[0]; gv[i][5] = g1[1]; gv[i][6] = g1[2]; gv[i][7] = g1[3];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) gv[i][j] = 0.f;
-            }
-        }
-        float xr[NE][8];
-        load_row_norm<NE>(h + (int64_t)(NL - 1) * plane + row * D, lane, nchunks, D, 1e-5f, xr);
-#pragma unroll
-        for (int n = 0; n < 31; ++n) {
-            if (n < NL - 1) {
-                float xh[NE][8];
-                load_row_norm<NE>(h + n * plane + row * D, lane, nchunks, D, 1e-5f, xh);
-                float d = 0.f;
-#pragma unroll
-                for (int i = 0; i < NE; ++i)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) d += gv[i][j] * (xh[i][j] - xr[i][j]);
-                accn[n] += d;
-            }
-        }
-    }
-#pragma unroll
-    for (int n = 0; n < 32; ++n) {
-        const float s = wave_sum(accn[n]);
-        if (lane == 0) red[wave][n] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NL)
-        dw_partial[(int64_t)blockIdx.x * NL + threadIdx.x] =
             (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
@@ -809,24 +678,49 @@ extern "C" int sc_layernorm_bf16(const sc_bf16* x, int64_t ldx, const float* gam
     return 0;
 }
 
+namespace {
+
+// The launch ladders, once per direction and for either layout.  The entry points check their arguments and size the forward grid.
+template <typename Rows>
+int wsum_fwd_launch(const uint16_t* h, const float* w, int NL, uint16_t* out, const Rows& rows, int D, int row_off, bool normalize, int grid,
+                    hipStream_t s) {
+    if (!normalize) hipLaunchKernelGGL(wsum_fwd_kernel<Rows>, dim3(grid), dim3(256), 0, s, h, w, NL, out, rows, D, row_off);
+    else if (D <= 512) hipLaunchKernelGGL((wsum_norm_fwd_kernel<1, Rows>), dim3(grid), dim3(256), 0, s, h, w, NL, out, rows, D, row_off);
+    else hipLaunchKernelGGL((wsum_norm_fwd_kernel<2, Rows>), dim3(grid), dim3(256), 0, s, h, w, NL, out, rows, D, row_off);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename Rows>
+int wsum_bwd_launch(const uint16_t* h, const void* gv, int NL, float* dw_partial, int nblk, const Rows& rows, int D, int row_off, int flags,
+                    hipStream_t s) {
+    const bool normalize = flags & 1, g16 = flags & 2;         // bit 1: g is bf16
+    const float* g = (const float*)gv;
+    const uint16_t* gh = (const uint16_t*)gv;
+    if (!normalize) {
+        if (g16) hipLaunchKernelGGL((wsum_bwd_kernel<uint16_t, Rows>), dim3(nblk), dim3(256), 0, s, h, gh, NL, dw_partial, rows, D, row_off);
+        else hipLaunchKernelGGL((wsum_bwd_kernel<float, Rows>), dim3(nblk), dim3(256), 0, s, h, g, NL, dw_partial, rows, D, row_off);
+    } else if (D <= 512) {
+        if (g16) hipLaunchKernelGGL((wsum_norm_bwd_kernel<1, uint16_t, Rows>), dim3(nblk), dim3(256), 0, s, h, gh, NL, dw_partial, rows, D, row_off);
+        else hipLaunchKernelGGL((wsum_norm_bwd_kernel<1, float, Rows>), dim3(nblk), dim3(256), 0, s, h, g, NL, dw_partial, rows, D, row_off);
+    } else {
+        if (g16) hipLaunchKernelGGL((wsum_norm_bwd_kernel<2, uint16_t, Rows>), dim3(nblk), dim3(256), 0, s, h, gh, NL, dw_partial, rows, D, row_off);
+        else hipLaunchKernelGGL((wsum_norm_bwd_kernel<2, float, Rows>), dim3(nblk), dim3(256), 0, s, h, g, NL, dw_partial, rows, D, row_off);
+    }
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
 extern "C" int sc_wsum_fwd(const sc_bf16* h, const float* w, int32_t NL, sc_bf16* out, int32_t B, int32_t R, int32_t D,
                            int32_t row_off, int32_t normalize, void* stream) {
     SC_CHECK(h && w && out, "sc_wsum_fwd: null pointer");
     SC_CHECK(NL >= 1 && NL <= 32 && D % 8 == 0 && row_off >= 0 && row_off < R, "sc_wsum_fwd: bad NL/D/row_off");
-    if (normalize) {
-        SC_CHECK(D <= 1024, "sc_wsum_fwd: normalised variant needs D <= 1024 (got %d)", D);
-        const int64_t rows = (int64_t)B * R;
-        const int grid = (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096);
-        if (D <= 512) hipLaunchKernelGGL(wsum_norm_fwd_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, h, w, NL, out, B, R, D, row_off);
-        else hipLaunchKernelGGL(wsum_norm_fwd_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, h, w, NL, out, B, R, D, row_off);
-        SC_LAUNCH_CHECK();
-        return 0;
-    }
-    const int64_t total = (int64_t)B * R * (D / 8);
-    const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(wsum_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, h, w, NL, out, B, R, D, row_off);
-    SC_LAUNCH_CHECK();
-    return 0;
+    if (normalize) SC_CHECK(D <= 1024, "sc_wsum_fwd: normalised variant needs D <= 1024 (got %d)", D);
+    const int64_t rows = (int64_t)B * R, total = rows * (D / 8);
+    const int grid = normalize ? (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096) : (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    return wsum_fwd_launch(h, w, NL, out, UniformRows{B, R}, D, row_off, normalize, grid, (hipStream_t)stream);
 }
 
 extern "C" int sc_wsum_bwd(const sc_bf16* h, const void* gv, int32_t NL, float* dw_partial, int32_t nblk, int32_t B,
@@ -834,26 +728,8 @@ extern "C" int sc_wsum_bwd(const sc_bf16* h, const void* gv, int32_t NL, float* 
     SC_CHECK(h && gv && dw_partial, "sc_wsum_bwd: null pointer");
     SC_CHECK(NL >= 1 && NL <= 32 && D % 8 == 0 && nblk >= 1 && row_off >= 0 && row_off < R, "sc_wsum_bwd: bad args");
     SC_CHECK(((uintptr_t)gv % 16) == 0, "sc_wsum_bwd: g must be 16-byte aligned");
-    const bool normalize = flags & 1, g16 = flags & 2;         // bit 1: g is bf16
-    const float* g = (const float*)gv;
-    const uint16_t* gh = (const uint16_t*)gv;
-    hipStream_t s = (hipStream_t)stream;
-    if (normalize) {
-        SC_CHECK(D <= 1024, "sc_wsum_bwd: normalised variant needs D <= 1024 (got %d)", D);
-        if (D <= 512) {
-            if (g16) hipLaunchKernelGGL((wsum_norm_bwd_kernel<1, uint16_t>), dim3(nblk), dim3(256), 0, s, h, gh, NL, dw_partial, B, R, D, row_off);
-            else hipLaunchKernelGGL((wsum_norm_bwd_kernel<1, float>), dim3(nblk), dim3(256), 0, s, h, g, NL, dw_partial, B, R, D, row_off);
-        } else {
-            if (g16) hipLaunchKernelGGL((wsum_norm_bwd_kernel<2, uint16_t>), dim3(nblk), dim3(256), 0, s, h, gh, NL, dw_partial, B, R, D, row_off);
-            else hipLaunchKernelGGL((wsum_norm_bwd_kernel<2, float>), dim3(nblk), dim3(256), 0, s, h, g, NL, dw_partial, B, R, D, row_off);
-        }
-        SC_LAUNCH_CHECK();
-        return 0;
-    }
-    if (g16) hipLaunchKernelGGL(wsum_bwd_kernel<uint16_t>, dim3(nblk), dim3(256), 0, s, h, gh, NL, dw_partial, B, R, D, row_off);
-    else hipLaunchKernelGGL(wsum_bwd_kernel<float>, dim3(nblk), dim3(256), 0, s, h, g, NL, dw_partial, B, R, D, row_off);
-    SC_LAUNCH_CHECK();
-    return 0;
+    if (flags & 1) SC_CHECK(D <= 1024, "sc_wsum_bwd: normalised variant needs D <= 1024 (got %d)", D);
+    return wsum_bwd_launch(h, gv, NL, dw_partial, nblk, UniformRows{B, R}, D, row_off, flags, (hipStream_t)stream);
 }
 
 extern "C" int sc_wsum_lazy_fwd(const sc_bf16* h, const float* w, int32_t NL, sc_bf16* out, int32_t B, int32_t R, int32_t D,
@@ -897,30 +773,20 @@ extern "C" int sc_wsum_fwd_seg(const sc_bf16* h, const float* w, int32_t NL, sc_
                                int32_t row_off, int32_t normalize, void* stream) {
     SC_CHECK(h && w && out && seg && seg->row0, "sc_wsum_fwd_seg: null pointer");
     SC_CHECK(NL >= 1 && NL <= 32 && D % 8 == 0 && row_off >= 0 && Rout > row_off && seg->B > 0 && seg->rows > 0, "sc_wsum_fwd_seg: bad NL/D/row_off");
+    if (normalize) SC_CHECK(D <= 1024, "sc_wsum_fwd_seg: normalised variant needs D <= 1024 (got %d)", D);
     const int B = seg->B;
     const int64_t plane = (int64_t)seg->rows * D;
     hipStream_t s = (hipStream_t)stream;
-    if (normalize) {
-        SC_CHECK(D <= 1024, "sc_wsum_fwd_seg: normalised variant needs D <= 1024 (got %d)", D);
-        const int64_t rows = (int64_t)B * Rout;
-        const int grid = (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096);
-        if (D <= 512) hipLaunchKernelGGL(wsum_norm_fwd_seg_kernel<1>, dim3(grid), dim3(256), 0, s, h, w, NL, out, seg->row0, B, Rout, D, row_off, plane);
-        else hipLaunchKernelGGL(wsum_norm_fwd_seg_kernel<2>, dim3(grid), dim3(256), 0, s, h, w, NL, out, seg->row0, B, Rout, D, row_off, plane);
-        SC_LAUNCH_CHECK();
-        return 0;
-    }
-    const int64_t total = (int64_t)B * Rout * (D / 8);
-    if ((NL == 13 || NL == 25) && (int64_t)Rout * (D / 8) < (1ll << 30) && B <= 65535 && !sc_option(5)) {      // option 5: A/B switch (tools/)
+    if (!normalize && (NL == 13 || NL == 25) && (int64_t)Rout * (D / 8) < (1ll << 30) && B <= 65535 && !sc_option(5)) {      // option 5: A/B switch (tools/)
         const dim3 g2((unsigned)(((int64_t)Rout * (D / 8) + 255) / 256), (unsigned)B);
         if (NL == 13) hipLaunchKernelGGL(wsum_fwd_seg_fixed_kernel<13>, g2, dim3(256), 0, s, h, w, out, seg->row0, Rout, D, row_off, plane);
         else hipLaunchKernelGGL(wsum_fwd_seg_fixed_kernel<25>, g2, dim3(256), 0, s, h, w, out, seg->row0, Rout, D, row_off, plane);
         SC_LAUNCH_CHECK();
         return 0;
     }
-    const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(wsum_fwd_seg_kernel, dim3(grid), dim3(256), 0, s, h, w, NL, out, seg->row0, B, Rout, D, row_off, plane);
-    SC_LAUNCH_CHECK();
-    return 0;
+    const int64_t rows = (int64_t)B * Rout, total = rows * (D / 8);
+    const int grid = normalize ? (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096) : (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    return wsum_fwd_launch(h, w, NL, out, SegRows{seg->row0, B, Rout, plane}, D, row_off, normalize, grid, s);
 }
 
 extern "C" int sc_wsum_bwd_seg(const sc_bf16* h, const void* gv, int32_t NL, float* dw_partial, int32_t nblk, const sc_segments* seg,
@@ -928,25 +794,14 @@ extern "C" int sc_wsum_bwd_seg(const sc_bf16* h, const void* gv, int32_t NL, flo
     SC_CHECK(h && gv && dw_partial && seg && seg->row0, "sc_wsum_bwd_seg: null pointer");
     SC_CHECK(((uintptr_t)gv % 16) == 0, "sc_wsum_bwd_seg: g must be 16-byte aligned");
     const bool normalize = flags & 1, g16 = flags & 2;         // bit 1: g is bf16
-    const float* g = (const float*)gv;
-    const uint16_t* gh = (const uint16_t*)gv;
     SC_CHECK(NL >= 1 && NL <= 32 && D % 8 == 0 && nblk >= 1 && row_off >= 0 && Rout > row_off && seg->B > 0 && seg->rows > 0, "sc_wsum_bwd_seg: bad args");
+    if (normalize) SC_CHECK(D <= 1024, "sc_wsum_bwd_seg: normalised variant needs D <= 1024 (got %d)", D);
     const int B = seg->B;
     const int64_t plane = (int64_t)seg->rows * D;
     hipStream_t s = (hipStream_t)stream;
-    if (normalize) {
-        SC_CHECK(D <= 1024, "sc_wsum_bwd_seg: normalised variant needs D <= 1024 (got %d)", D);
-        if (D <= 512) {
-            if (g16) hipLaunchKernelGGL((wsum_norm_bwd_seg_kernel<1, uint16_t>), dim3(nblk), dim3(256), 0, s, h, gh, NL, dw_partial, seg->row0, B, Rout, D, row_off, plane);
-            else hipLaunchKernelGGL((wsum_norm_bwd_seg_kernel<1, float>), dim3(nblk), dim3(256), 0, s, h, g, NL, dw_partial, seg->row0, B, Rout, D, row_off, plane);
-        } else {
-            if (g16) hipLaunchKernelGGL((wsum_norm_bwd_seg_kernel<2, uint16_t>), dim3(nblk), dim3(256), 0, s, h, gh, NL, dw_partial, seg->row0, B, Rout, D, row_off, plane);
-            else hipLaunchKernelGGL((wsum_norm_bwd_seg_kernel<2, float>), dim3(nblk), dim3(256), 0, s, h, g, NL, dw_partial, seg->row0, B, Rout, D, row_off, plane);
-        }
-        SC_LAUNCH_CHECK();
-        return 0;
-    }
-    if ((NL == 13 || NL == 25) && (int64_t)B * Rout * (D / 8) < (1ll << 31) && !sc_option(5)) {      // option 5: A/B switch (tools/)
+    if (!normalize && (NL == 13 || NL == 25) && (int64_t)B * Rout * (D / 8) < (1ll << 31) && !sc_option(5)) {      // option 5: A/B switch (tools/)
+        const float* g = (const float*)gv;
+        const uint16_t* gh = (const uint16_t*)gv;
         if (NL == 13) {
             if (g16) hipLaunchKernelGGL((wsum_bwd_seg_fixed_kernel<13, uint16_t>), dim3(nblk), dim3(256), 0, s, h, gh, dw_partial, seg->row0, B, Rout, D, row_off, plane);
             else hipLaunchKernelGGL((wsum_bwd_seg_fixed_kernel<13, float>), dim3(nblk), dim3(256), 0, s, h, g, dw_partial, seg->row0, B, Rout, D, row_off, plane);
@@ -957,10 +812,7 @@ extern "C" int sc_wsum_bwd_seg(const sc_bf16* h, const void* gv, int32_t NL, flo
         SC_LAUNCH_CHECK();
         return 0;
     }
-    if (g16) hipLaunchKernelGGL(wsum_bwd_seg_kernel<uint16_t>, dim3(nblk), dim3(256), 0, s, h, gh, NL, dw_partial, seg->row0, B, Rout, D, row_off, plane);
-    else hipLaunchKernelGGL(wsum_bwd_seg_kernel<float>, dim3(nblk), dim3(256), 0, s, h, g, NL, dw_partial, seg->row0, B, Rout, D, row_off, plane);
-    SC_LAUNCH_CHECK();
-    return 0;
+    return wsum_bwd_launch(h, gv, NL, dw_partial, nblk, SegRows{seg->row0, B, Rout, plane}, D, row_off, flags, s);
 }
 
 extern "C" int sc_posconv_prep_seg(const sc_bf16* x, const int32_t* valid_len, sc_bf16* xz, sc_bf16* xg, const sc_segments* seg, int32_t D,

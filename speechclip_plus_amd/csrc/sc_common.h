@@ -325,7 +325,10 @@ __device__ __forceinline__ int sc_tr_swizzle(int row) { return ((row >> 1) & 15)
 // host side
 void sc_set_error(const char* fmt, ...);
 int sc_num_cus();   // compute units of the current device (immutable cache; 256 on MI355X)
-int sc_option(int key);   // tuning switches (sc_set_option): 1 = plain stores on residual tiles of the 256- / 128-row GEMMs
+// tuning switches for same-process A/B (sc_set_option(key, 1); all 0 by default).  Live keys: 1 = plain stores on residual tiles of the 256- / 128-row
+// GEMMs; 2 = conv 0 + LayerNorm by the two-pass reduction kernel (frontend.hip); 3 = round 3's block -> tile map of gemm256_kernel; 5 = the generic
+// weighted-sum kernels on the segment layout at NL = 13 / 25 (rowops.hip); 6 = the sequential integrate-and-fire walk (cif.hip)
+int sc_option(int key);
 #define SC_CHECK(cond, ...)                 \
     do {                                    \
         if (!(cond)) {                      \

@@ -1074,6 +1074,59 @@ def test_weighted_sum_logit_gradient_on_a_residual_stream(dev, normalize):
     assert e < 1e-4, e
 
 
+def test_weighted_sum_kernels_agree_across_the_two_row_layouts(dev):
+    """The weighted-sum kernels are written once and take the row layout as a policy (csrc/rowops.hip: UniformRows / SegRows).  The
+    same states laid out uniformly [B, R] and as segments of equal pitch R: the forwards are bit-equal on every live row, the dead rows
+    (in front of row_off) are zero in the segment output and untouched in the uniform one; each backward keeps the 4 digits of the
+    residual-stream test above against an fp64 sum (the two walk different loop domains, so their partial sums are not bit-equal).
+    sc_set_option(5, 1) keeps the segment calls on the generic kernel at NL = 13.
+
+    The states are a residual stream as above.  At these sizes a sum <g, h_n - h_last> of zero-mean terms can land anywhere near zero
+    (at NL = 2 the whole gradient is ONE such sum), and no fp32 sum keeps 4 digits of a result hundreds of times smaller than its
+    terms.  So layer n also carries (1 - n / (NL - 1)) of an alternating +-0.03 pattern over the features (zero mean per row: the
+    normalised variant keeps it) that the gradient shares: the sums get a part that does not cancel.  The test asserts that condition
+    in fp64 on its own data, sum |terms| / |result| < 100 after the softmax projection: fp32 round-off, 6e-8 of the terms, then stays
+    an order of magnitude inside the 1e-4 bound."""
+    from speechclip_plus_amd import _lib
+    ops = _ops()
+    g = torch.Generator(device="cpu").manual_seed(21)
+    B, R = 3, 24
+    seg = ops.RowSegments([R] * B, [R] * B, dev)
+    _lib.lib().sc_set_option(5, 1)
+    try:
+        for D in (8, 768):
+            for NL in (2, 13):
+                q = 1.0 - 2.0 * (torch.arange(D) % 2)
+                base = torch.randn(B * R, D, generator=g) * 2.0 + 0.5
+                h = bf(base + 0.03 * (torch.randn(NL, B * R, D, generator=g) + torch.linspace(1.0, 0.0, NL).view(NL, 1, 1) * q)).to(dev)
+                w = torch.softmax(torch.randn(NL, generator=g) * 0.5, 0).to(dev)
+                gout = bf(torch.randn(B, R, D, generator=g) + 0.25 * q).to(dev)
+                for off in (0, 1):
+                    for normalize in (False, True):
+                        case = (D, NL, off, normalize)
+                        out_u = torch.full((B, R, D), 7.0, device=dev, dtype=torch.bfloat16)
+                        out_s = torch.full((B, R, D), 7.0, device=dev, dtype=torch.bfloat16)
+                        ops.wsum_fwd(h, w, out_u, B, R, D, off, normalize=normalize)
+                        ops.wsum_fwd(h, w, out_s, B, R, D, off, normalize=normalize, seg=seg)
+                        assert torch.equal(out_u[:, off:], out_s[:, off:]), case
+                        assert bool((out_s[:, :off] == 0).all()) and bool((out_u[:, :off] == 7.0).all()), case
+                        hd = h.double().view(NL, B, R, D)
+                        if normalize:
+                            hd = F.layer_norm(hd, (D,))
+                        terms = gout[:, off:].double().unsqueeze(0) * (hd[:, :, : R - off] - hd[-1:, :, : R - off])
+                        d, mag = terms.sum((1, 2, 3)), terms.abs().sum((1, 2, 3))
+                        wd = w.double()
+                        ref = wd * (d - (wd * d).sum())
+                        assert float((wd * (mag + (wd * mag).sum())).norm() / ref.norm()) < 100, case
+                        for gt in (gout.float(), gout):
+                            for s in (None, seg):
+                                got = ops.wsum_bwd_logits(h, gt, w, B, R, D, off, normalize=normalize, seg=s)
+                                e = rel_l2(got.double(), ref)
+                                assert e < 1e-4, (case, gt.dtype, s is not None, e)
+    finally:
+        _lib.lib().sc_set_option(5, 0)
+
+
 @pytest.mark.parametrize("n,p_drop", [(72, 0.0), (512, 0.0), (1024, 0.2), (260, 0.5)])
 def test_softmax_rows_fwd_bwd_vs_torch(dev, n, p_drop):
     """csrc/softmax.hip on its own: masked row softmax (+ hash dropout) and its backward against fp32 torch, row lengths that use
