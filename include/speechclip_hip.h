@@ -139,7 +139,9 @@ typedef struct {
      *   aux_mode 1  dual store:  Ct <- u = bf16(acc + bias) (the pre-activation the backward needs),  C <- act(u)   (FFN fc1 of a layer
      *               that is differentiated: one launch instead of GEMM + sc_act_bf16)
      *   aux_mode 2  C <- bf16(acc) * act'(Ct)   (the input-gradient GEMM of fc2 followed by the activation's backward: Ct = the saved u)
-     * Both reproduce the two-launch sequence bit for bit (the activation reads the ROUNDED values the first kernel would have stored). */
+     *   aux_mode 3  C <- act(u) as mode 1 computes it, u not stored (Ct NULL; 128-row tiles): the same layer run forward-only gives the
+     *               bits of the differentiated run without keeping its pre-activation
+     * All reproduce the two-launch sequence bit for bit (the activation reads the ROUNDED values the first kernel would have stored). */
     int32_t aux_mode;
     int32_t reserved3;
     /* ---- ragged rows (round 4): seg_chunk != NULL replaces the uniform `R` of the transposed store - row m belongs to the
@@ -785,6 +787,15 @@ int sc_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float l
 int sc_prompt_assemble(const float* keywords, int64_t ldb, const int64_t* count, const float* tok, const float* pos, sc_bf16* X,
                        int32_t* eot_row, int64_t* clamped, int32_t B, int32_t Bp, int32_t N, int32_t W, int32_t SEG, int32_t n_pos,
                        void* stream);
+/* Caption tokens in the same packed rows (ClipModel.encode_text, avssl/module/clip_official.py:213-220 -> openai/CLIP encode_text), one
+ * launch: ids [B, L <= 77] int64 (row stride ld_ids), table [V, W] fp32 (leading dimension ldt), pos [77, W] fp32.
+ *   X[b*SEG + t] <- bf16(table[ids[b, t]] + pos[t]) for b < B, t < n_pos (fp32 add, rounded once); every other row of X [Bp*SEG, W] zero,
+ *   every row written.  eot_row[b] <- b*SEG + e_b, e_b = the FIRST position of the row's largest id among t < L (text.argmax(dim=-1): the
+ *   end-of-text position in the full and in a reduced vocabulary), clamped to n_pos - 1.  An id outside [0, V) reads nothing and
+ *   contributes a zero embedding.  *bad (device counter, may be NULL) += clamps + such ids among the rows assembled.
+ *   W % 8 == 0, ldt % 4 == 0, n_pos <= min(L, SEG); table, pos and X 16-byte aligned. */
+int sc_text_assemble(const int64_t* ids, int64_t ld_ids, const float* table, int64_t ldt, const float* pos, sc_bf16* X, int32_t* eot_row,
+                     int64_t* bad, int32_t B, int32_t Bp, int32_t L, int32_t V, int32_t W, int32_t SEG, int32_t n_pos, void* stream);
 int sc_prompt_assemble_bwd(const sc_bf16* dX, const int64_t* count, float* dkeywords, int64_t ldb, int32_t B, int32_t N, int32_t W,
                            int32_t SEG, int32_t n_pos, void* stream);
 int sc_rows_gather_bf16(const sc_bf16* X, const int32_t* row, float* out, int32_t B, int32_t W, void* stream);

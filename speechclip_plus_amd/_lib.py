@@ -222,6 +222,7 @@ SIGNATURES = {
     "sc_colsum_f32": [c_void_p, c_i64, c_int, c_int, c_void_p, c_float, c_float, c_void_p],
     "sc_headmask_f32": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "sc_prompt_assemble": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "sc_text_assemble": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "sc_prompt_assemble_bwd": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "sc_rows_gather_bf16": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "sc_vit_patchify_bf16": [c_void_p, c_i64, c_i64, c_i64, c_void_p, c_int, ctypes.POINTER(Segments), c_int, c_int, c_void_p],

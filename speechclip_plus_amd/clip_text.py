@@ -115,6 +115,10 @@ class ClipModel(nn.Module):
         self.out_dim = a["width"]
         # keyword counts that pointed behind the keyword tensor and were clamped by encode_keywords (device counter, read on request)
         self.register_buffer("eot_clamped", torch.zeros((), dtype=torch.int64), persistent=False)
+        # ids outside the table and end-of-text positions behind the prefix that sc_text_assemble met (encode_text checks the range on
+        # the host first: stays 0 unless that check is bypassed)
+        self.register_buffer("text_bad", torch.zeros(1, dtype=torch.int64), persistent=False)
+        self.tokenizer = None                    # attach a BPE tokenizer (openai/CLIP's SimpleTokenizer interface) for prep_text
         self.selected_text_emb_ids = None
         if reduce_subword_embbedding is not None:
             # clip_official.py:63-108: keep only the sub-words seen in the captions.  Accepts the reference's .npy path
@@ -215,3 +219,85 @@ class ClipModel(nn.Module):
         n_pos = min(CONTEXT_LEN, int(keyword_num) + 2)          # the causal prefix up to the end-of-text position
         x = self._transformer(x[:, :n_pos])
         return _EotHeadFn.apply(x[:, 1 + keyword_num], ln.weight, ln.bias, ln.eps, self.model.text_projection)
+
+    # ------------------------------------------------------------------------------------------------- captions
+    def to_reduced_ids(self, text: torch.Tensor) -> torch.Tensor:
+        """ORIGINAL CLIP token ids -> ids of the reduced table through one lookup tensor (a new tensor: the caller's is not written;
+        clip_official.py:178-181 / kwClip.py:518-524 loop over every element in Python).  An id that is not in the reduced vocabulary
+        raises ValueError - at once for host ids; device ids come back with -1 in its place and encode_text, which reads the id range
+        anyway, raises for it (``_original``), so that the mapping costs no host read of its own.  Full vocabulary: ``text`` itself."""
+        if self.selected_text_emb_ids is None:
+            return text
+        lut = getattr(self, "_o2r_lut", None)
+        if lut is None or lut.device != text.device:
+            lut = torch.full((CLIP_VOCAB + 1,), -1, dtype=torch.int64)           # last entry: every id outside the CLIP vocabulary
+            lut[self.selected_text_emb_ids] = torch.arange(self.selected_text_emb_ids.numel())
+            lut = self._o2r_lut = lut.to(text.device)
+        t = text.long()
+        out = lut[torch.where((t < 0) | (t >= CLIP_VOCAB), CLIP_VOCAB, t)]
+        missing = t[out < 0] if not t.is_cuda else t[:0]
+        if missing.numel():
+            raise ValueError(f"token id {int(missing[0])} is not in the reduced vocabulary ({self.selected_text_emb_ids.numel()} sub-words)")
+        return out
+
+    def prep_text(self, sents: list) -> torch.Tensor:
+        """clip_official.py:168-182 (clip.tokenize): sentences -> [B, 77] int64 ids of the table in use, [SOT, BPE ids, EOT, 0 ...].
+        The BPE vocabulary is not part of this package: ``self.tokenizer`` must have been attached (``encode(str) -> list of ids``,
+        openai/CLIP's SimpleTokenizer)."""
+        if getattr(self, "tokenizer", None) is None:
+            raise RuntimeError("prep_text needs a tokenizer: attach one as `clip.tokenizer` (openai/CLIP's SimpleTokenizer interface; "
+                               "INTEGRATION.md) or pass token ids to encode_text / forward_text")
+        if isinstance(sents, str):
+            sents = [sents]
+        res = torch.zeros(len(sents), CONTEXT_LEN, dtype=torch.int64)
+        for i, sent in enumerate(sents):
+            toks = [SOT_TOKEN] + list(self.tokenizer.encode(sent)) + [EOT_TOKEN]
+            if len(toks) > CONTEXT_LEN:
+                raise RuntimeError(f"Input {sent} is too long for context length {CONTEXT_LEN}")
+            res[i, : len(toks)] = torch.tensor(toks, dtype=torch.int64)
+        return self.to_reduced_ids(res)
+
+    def encode_text(self, text: torch.Tensor, bucket: bool = True, _original: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """clip_official.py:213-220 -> openai/CLIP ``encode_text``: text [B, L <= 77] integer ids OF THE TABLE IN USE (reduced ids when
+        the vocabulary is reduced) -> [B, embed_dim] fp32, token_embedding + positional_embedding -> transformer -> ln_final -> the row
+        at ``text.argmax(-1)`` @ text_projection.  Forward-only, under no_grad (the tower is frozen).  The tower is causal and only the
+        end-of-text row is read, so every caption runs on its own prefix at its own segment class (clip_text_hip.text_buckets;
+        ``bucket`` False: the whole batch at the class of its longest caption - the baseline the bucketing is measured against).
+        ``text`` may live on the host: the end-of-text positions are then computed there and only the ids are uploaded; for device ids
+        the positions and the id range come back in one small copy."""
+        if not isinstance(text, torch.Tensor):
+            raise TypeError(f"Unknown text type {type(text)}")
+        if text.dim() != 2 or text.shape[1] > CONTEXT_LEN or text.shape[1] < 1 or text.shape[0] < 1:
+            raise ValueError(f"Incorrect text tensor shape {tuple(text.shape)}: [B, L <= {CONTEXT_LEN}] token ids")
+        if text.dtype.is_floating_point or text.dtype.is_complex or text.dtype == torch.bool:
+            raise TypeError(f"text must hold integer token ids, got {text.dtype}")
+        self._check_tower()
+        emb = self.model.token_embedding.weight
+        V, B = emb.shape[0], text.shape[0]
+        with torch.no_grad():
+            t = text.detach().to(torch.int64)
+            stats = torch.cat([t.argmax(dim=-1), t.amin().reshape(1), t.amax().reshape(1)]).tolist()   # device ids: the one copy to the host
+            eot_pos, lo, hi = stats[:B], stats[B], stats[B + 1]
+            if lo < 0 and _original is not None:         # ids mapped by to_reduced_ids on the device: name the caller's id
+                raise ValueError(f"token id {int(_original[t < 0][0])} is not in the reduced vocabulary ({V} sub-words)")
+            if lo < 0 or hi >= V:
+                raise ValueError(f"token id {lo if lo < 0 else hi} is outside the token table in use [0, {V})")
+            dev = emb.device
+            if not emb.is_cuda:
+                raise RuntimeError("the CLIP text tower runs on the HIP kernels: device tensors only")
+            from . import ops
+            from .clip_text_hip import text_rows
+            t = t.to(dev)
+            if t.stride(1) != 1:
+                t = t.contiguous()
+            table = ops.aligned16(emb.detach() if emb.dtype == torch.float32 else emb.detach().float())
+            if table.stride(1) != 1 or table.stride(0) % 4:
+                table = table.contiguous()
+            heads = self.model.transformer.resblocks[0].attn.num_heads
+            rows, order = text_rows(t, eot_pos, table, self._prompt_constants(dev)[1], self._tower_weights(dev), heads, bucket=bucket,
+                                    bad=self.text_bad)
+            ln = self.model.ln_final
+            out = _EotHeadFn.apply(rows, ln.weight, ln.bias, ln.eps, self.model.text_projection)
+            if order is not None:                        # back to input order
+                out = torch.empty_like(out).index_copy_(0, order, out)
+            return out

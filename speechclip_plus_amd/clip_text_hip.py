@@ -89,8 +89,20 @@ def _geometry(B: int, T: int):
     return SEG, Bp, Bp * SEG, 1 if SEG == BLOCK else SEG
 
 
-def tower_forward(X: torch.Tensor, weights, heads: int, causal: int):
-    """X [M, W] bf16 packed rows -> (output rows [M, W] bf16, what the backward needs)"""
+def text_buckets(eot_pos) -> list:
+    """End-of-text positions of a batch of captions (host integers) -> [(SEG, n_pos, indices)], one entry per segment class in use:
+    a caption whose prefix e + 1 is at most 32 positions runs on 32-row segments, at most 64 on 64, else on 128; ``n_pos`` is the class's
+    longest prefix and ``indices`` its captions in input order.  The tower is causal and only the end-of-text row is read, so a
+    caption costs its own prefix, as the keyword prompts do."""
+    by_seg = {}
+    for i, e in enumerate(eot_pos):
+        by_seg.setdefault(_segment(int(e) + 1), []).append(i)
+    return [(seg, max(int(eot_pos[i]) for i in idx) + 1, idx) for seg, idx in sorted(by_seg.items())]
+
+
+def tower_forward(X: torch.Tensor, weights, heads: int, causal: int, save: bool = True):
+    """X [M, W] bf16 packed rows -> (output rows [M, W] bf16, what the backward needs).  ``save`` False (forward-only: caption
+    embeddings): nothing is kept - no log-sum-exp, no fc1 pre-activation, ``saved`` stays empty - and the output has the same bits."""
     M, W = X.shape
     dev = X.device
     NB = M // BLOCK
@@ -110,17 +122,19 @@ def tower_forward(X: torch.Tensor, weights, heads: int, causal: int):
         else:
             vt = ops.head_transpose(qkv[:, 2 * W:], NB, BLOCK, heads)
             att = torch.empty(M, W, device=dev, dtype=torch.bfloat16)
-            lse2 = torch.empty(NB, heads, BLOCK, device=dev, dtype=torch.float32)
+            lse2 = torch.empty(NB, heads, BLOCK, device=dev, dtype=torch.float32) if save else None
             ops.attn_fwd(qkv[:, : 2 * W], vt, valid, att, NB, BLOCK, heads, W, scale, lse2=lse2, causal=causal)
         X2 = ops.linear_bf16(att, w.wo, w.bo, residual=X)
-        u = torch.empty(M, w.w1.shape[0], device=dev, dtype=torch.bfloat16)
+        u = torch.empty(M, w.w1.shape[0], device=dev, dtype=torch.bfloat16) if save else None
+        aux_mode = 1 if save else 3                                                # 3: QuickGELU of the rounded u, u itself not stored
         if fold:
-            f = ops.linear_bf16(X2, w.w1_ln, w.c1, act=2, aux=u, aux_mode=1, ln_colsum=w.s1, ln_eps=w.eps2)      # LN2 in the prologue
+            f = ops.linear_bf16(X2, w.w1_ln, w.c1, act=2, aux=u, aux_mode=aux_mode, ln_colsum=w.s1, ln_eps=w.eps2)      # LN2 in the prologue
         else:
             h2 = ops.layernorm_bf16(X2, w.g2, w.be2, eps=w.eps2)
-            f = ops.linear_bf16(h2, w.w1, w.b1, act=2, aux=u, aux_mode=1)          # u = fc1 pre-activation (kept), f = QuickGELU(u)
+            f = ops.linear_bf16(h2, w.w1, w.b1, act=2, aux=u, aux_mode=aux_mode)   # u = fc1 pre-activation (kept), f = QuickGELU(u)
         Xn = ops.linear_bf16(f, w.w2, w.b2, residual=X2)
-        saved.append((X, qkv, None if short else att, lse2, X2, u))
+        if save:
+            saved.append((X, qkv, None if short else att, lse2, X2, u))
         X = Xn
     return X, saved
 
@@ -146,6 +160,42 @@ def tower_backward(dX: torch.Tensor, weights, saved, heads: int, causal: int, q_
         dh1 = ops.linear_bf16(dqkv, w.wqkvT)
         dX = ops.layernorm_bwd(X, dh1, w.g1, w.eps1, dres=dX2)
     return dX
+
+
+# Packed rows of one tower call of ``text_rows``: a retrieval set has thousands of captions, the workspace (the rows, their QKV and
+# the 4 W wide MLP rows, ~12 W bf16 values per row: 200 MB at W = 512) is bounded by this and not by the set; 16384 rows fill the chip
+# (128 row tiles of 128 on 256 CUs times the column tiles) and hold 512 captions of the 32 class.
+TEXT_CHUNK_ROWS = 16384
+
+
+def text_rows(ids: torch.Tensor, eot_pos, table: torch.Tensor, pos: torch.Tensor, weights, heads: int, bucket: bool = True, bad=None):
+    """Caption ids [B, L] int64 on the device + their end-of-text positions on the host -> (rows [B, W] fp32: the tower's output at each
+    caption's end-of-text position, in the order ``order``; order: None = input order, else an int64 device tensor - row j belongs to
+    caption order[j]).  Every segment class of ``text_buckets`` runs at its own length (``bucket`` False: the whole batch at the class
+    of its longest caption), in chunks of at most TEXT_CHUNK_ROWS packed rows: assemble -> forward-only tower -> gather, three kinds of
+    launches and nothing kept between chunks."""
+    B = ids.shape[0]
+    if bucket:
+        buckets = text_buckets(eot_pos)
+    else:
+        n_pos = max(int(e) for e in eot_pos) + 1
+        buckets = [(_segment(n_pos), n_pos, list(range(B)))]
+    order = None
+    if len(buckets) > 1:                                 # the classes lie back to back: one gather of the ids, slices from there on
+        order = torch.tensor([i for _, _, idx in buckets for i in idx], dtype=torch.int64).to(ids.device)
+        ids = ids.index_select(0, order)
+    rows = torch.empty(B, table.shape[1], device=ids.device, dtype=torch.float32)
+    at = 0
+    for SEG, n_pos, idx in buckets:
+        per = BLOCK // SEG
+        step = max(per, TEXT_CHUNK_ROWS // SEG)
+        for c0 in range(at, at + len(idx), step):
+            nb = min(step, at + len(idx) - c0)
+            X, eot_row, _ = ops.text_assemble(ids[c0: c0 + nb], table, pos, -(-nb // per) * per, SEG, n_pos, bad=bad)
+            X, _ = tower_forward(X, weights, heads, 1 if SEG == BLOCK else SEG, save=False)
+            ops.rows_gather(X, eot_row, out=rows[c0: c0 + nb])
+        at += len(idx)
+    return rows, order
 
 
 class TextTowerFn(torch.autograd.Function):

@@ -302,8 +302,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const sc_gemm_args p) {
                     uint4 r;             // the values the plain GEMM would have stored
                     r.x = pack2bf(v[0], v[1]); r.y = pack2bf(v[2], v[3]); r.z = pack2bf(v[4], v[5]); r.w = pack2bf(v[6], v[7]);
                     const float rr[8] = {bflo(r.x), bfhi(r.x), bflo(r.y), bfhi(r.y), bflo(r.z), bfhi(r.z), bflo(r.w), bfhi(r.w)};
-                    if (p.aux_mode == 1) {
-                        *(uint4*)X = r;                                              // u
+                    if (p.aux_mode != 2) {
+                        if (p.aux_mode == 1) *(uint4*)X = r;                         // u (aux_mode 3, forward-only: not kept)
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] = act_fwd(rr[e], p.act);   // act(u)
                     } else {
@@ -425,12 +425,13 @@ extern "C" int sc_gemm_bf16(const sc_gemm_args* args, void* stream) {
         return sc_gemm256_launch(a, (hipStream_t)stream);
     }
     if (a.aux_mode) {
-        SC_CHECK((a.aux_mode == 1 || a.aux_mode == 2) && (a.act == 1 || a.act == 2) && a.Ct && a.n_split < 0 && !a.out_f32 && !a.tn &&
-                 a.drop_p == 0.f && !a.ln_stats && !a.stats_out && !a.res_stats && ((uintptr_t)a.Ct % 16) == 0,
-                 "sc_gemm_bf16: aux_mode needs act 1 / 2, the aux pointer in Ct (16-byte aligned), bf16 output and a plain epilogue");
-        // 128-row tiles: both activations; 256-row tiles (round 4): erf-GELU, plain epilogue (no residual)
-        SC_CHECK(a.tile == 0 || a.tile == 1 || a.tile == 3 || a.tile == 13 || a.tile == 14 || a.tile == 15 || ((a.tile == 2 || a.tile == 7 || a.tile == 8) && a.act == 1 && !a.residual),
-                 "sc_gemm_bf16: aux_mode on the 256-row tiles needs act = 1 (erf-GELU) and no residual");
+        SC_CHECK(a.aux_mode >= 1 && a.aux_mode <= 3 && (a.act == 1 || a.act == 2) && (a.aux_mode == 3 ? !a.Ct : a.Ct != nullptr) && a.n_split < 0 &&
+                 !a.out_f32 && !a.tn && a.drop_p == 0.f && !a.ln_stats && !a.stats_out && !a.res_stats && ((uintptr_t)a.Ct % 16) == 0,
+                 "sc_gemm_bf16: aux_mode needs act 1 / 2, the aux pointer in Ct (16-byte aligned; none for mode 3), bf16 output and a plain epilogue");
+        // 128-row tiles: both activations; 256-row tiles (round 4): erf-GELU, plain epilogue (no residual), modes 1 and 2
+        SC_CHECK(a.tile == 0 || a.tile == 1 || a.tile == 3 || a.tile == 13 || a.tile == 14 || a.tile == 15 ||
+                 ((a.tile == 2 || a.tile == 7 || a.tile == 8) && a.aux_mode != 3 && a.act == 1 && !a.residual),
+                 "sc_gemm_bf16: aux_mode on the 256-row tiles needs mode 1 / 2, act = 1 (erf-GELU) and no residual");
     } else {
         // act = 2 (QuickGELU) as a plain epilogue: every tile family (the 256-row tiles through their ACT = 2 instances); no dropout
         // variant is built for it (the CLIP towers are frozen, eval-mode)
@@ -470,7 +471,7 @@ extern "C" int sc_gemm_bf16(const sc_gemm_args* args, void* stream) {
     if (tile == 0) {
         const int64_t tiles256 = (int64_t)((a.M + 255) / 256) * ((a.N + 255) / 256) * a.nb1 * a.nb2;
         if (a.N <= 64 && a.n_split < 0) tile = 3;            // narrow outputs (grouped pos_conv, N = 48)
-        else if (!ln_self && (!a.aux_mode || (a.act == 1 && !a.residual)) && a.M >= 512 && a.N >= 192 && tiles256 >= 192 && (a.n_split < 0 || a.n_split % 64 == 0)) tile = 2;
+        else if (!ln_self && (!a.aux_mode || (a.aux_mode != 3 && a.act == 1 && !a.residual)) && a.M >= 512 && a.N >= 192 && tiles256 >= 192 && (a.n_split < 0 || a.n_split % 64 == 0)) tile = 2;
         else {
             // small problems (the text tower's 2048 packed rows): 128 x 64 tiles give twice the workgroups, 10-20 % faster up to two
             // waves of 128 x 128 tiles per CU (tools/bench_small_gemm.py)

@@ -48,6 +48,54 @@ __global__ __launch_bounds__(128) void prompt_assemble_kernel(const float* __res
     }
 }
 
+// Caption tokens in the tower's packed rows (ClipModel.encode_text, clip_official.py:213-220 -> openai/CLIP encode_text):
+// X[b SEG + t] = bf16(table[ids[b, t]] + pos[t]) for t < n_pos, b < B; 0 elsewhere (every row is written).  The block of a sample's row 0
+// also finds the row the head reads, text.argmax(-1): the FIRST position of the largest id among the L given (the end-of-text token has
+// the largest id of both vocabularies), clamped into the prefix.  An id outside [0, V) reads nothing: zero embedding, counted in *bad
+// together with the clamps (the host checks the range first, ClipModel.encode_text; this is the net behind it).
+__global__ __launch_bounds__(128) void text_assemble_kernel(const int64_t* __restrict__ ids, int64_t ld_ids, const float* __restrict__ table,
+                                                            int64_t ldt, const float* __restrict__ pos, uint16_t* __restrict__ X,
+                                                            int32_t* __restrict__ eot_row, unsigned long long* __restrict__ bad, int B, int L,
+                                                            int V, int W, int SEG, int n_pos) {
+    __shared__ int64_t s_id[128];
+    __shared__ int s_t[128];
+    const int r = blockIdx.x, b = r / SEG, t = r - b * SEG;
+    uint16_t* x = X + (int64_t)r * W;
+    if (b >= B || t >= n_pos) {
+        for (int c = threadIdx.x * 8; c < W; c += 128 * 8) *(uint4*)(x + c) = make_uint4(0, 0, 0, 0);
+        return;
+    }
+    if (t == 0) {                                        // block-uniform: L <= 128 positions, one per thread
+        const int k = threadIdx.x;
+        s_id[k] = k < L ? ids[(int64_t)b * ld_ids + k] : INT64_MIN;
+        s_t[k] = k;
+        __syncthreads();
+        for (int h = 64; h > 0; h >>= 1) {
+            if (k < h && (s_id[k + h] > s_id[k] || (s_id[k + h] == s_id[k] && s_t[k + h] < s_t[k]))) { s_id[k] = s_id[k + h]; s_t[k] = s_t[k + h]; }
+            __syncthreads();
+        }
+        if (k == 0) {
+            const bool over = s_t[0] > n_pos - 1;
+            eot_row[b] = b * SEG + (over ? n_pos - 1 : s_t[0]);
+            if (over && bad) atomicAdd(bad, 1ull);
+        }
+    }
+    const int64_t id = ids[(int64_t)b * ld_ids + t];
+    const bool zero = id < 0 || id >= V;
+    if (zero && bad && threadIdx.x == 0) atomicAdd(bad, 1ull);
+    const float* e = table + (zero ? 0 : id) * ldt;
+    const float* pp = pos + (int64_t)t * W;
+    for (int c = threadIdx.x * 4; c < W; c += 128 * 4) {
+        const f32x4 pv = *(const f32x4*)(pp + c);
+        f32x4 ev = {0.f, 0.f, 0.f, 0.f};
+        if (!zero) ev = *(const f32x4*)(e + c);
+        uint2 o;
+        o.x = pack2bf(ev[0] + pv[0], ev[1] + pv[1]);
+        o.y = pack2bf(ev[2] + pv[2], ev[3] + pv[3]);
+        *(uint2*)(x + c) = o;
+    }
+}
+
 // dkw[b, j] = float(dX[b SEG + j + 1]) for j + 1 < min(index_b, n_pos), else 0        (every element of dkw is written)
 __global__ __launch_bounds__(128) void prompt_assemble_bwd_kernel(const uint16_t* __restrict__ dX, const int64_t* __restrict__ count,
                                                                   float* __restrict__ dkw, int64_t ldb, int N, int W, int SEG, int n_pos) {
@@ -113,6 +161,21 @@ extern "C" int sc_prompt_assemble(const float* keywords, int64_t ldb, const int6
              "sc_prompt_assemble: operands must be 16-byte aligned");
     hipLaunchKernelGGL(prompt_assemble_kernel, dim3(Bp * SEG), dim3(128), 0, (hipStream_t)stream, keywords, ldb, count, tok, pos, X, eot_row,
                        (unsigned long long*)clamped, B, N, W, SEG, n_pos);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sc_text_assemble(const int64_t* ids, int64_t ld_ids, const float* table, int64_t ldt, const float* pos, uint16_t* X, int32_t* eot_row,
+                                int64_t* bad, int32_t B, int32_t Bp, int32_t L, int32_t V, int32_t W, int32_t SEG, int32_t n_pos, void* stream) {
+    SC_CHECK(ids && table && pos && X && eot_row, "sc_text_assemble: null pointer");
+    SC_CHECK(B > 0 && Bp >= B && L > 0 && L <= 77 && ld_ids >= L && V > 0 && SEG > 0 && n_pos >= 1 && n_pos <= SEG && n_pos <= L,
+             "sc_text_assemble: B=%d Bp=%d L=%d V=%d SEG=%d n_pos=%d (L <= 77 positions, n_pos <= min(L, SEG))", B, Bp, L, V, SEG, n_pos);
+    SC_CHECK((int64_t)Bp * SEG <= INT32_MAX, "sc_text_assemble: Bp * SEG = %lld rows (at most 2^31 - 1)", (long long)Bp * SEG);
+    SC_CHECK(W > 0 && W % 8 == 0 && ldt >= W && ldt % 4 == 0, "sc_text_assemble: W=%d must be a multiple of 8 (ldt of 4, ldt >= W)", W);
+    SC_CHECK(((uintptr_t)table % 16) == 0 && ((uintptr_t)pos % 16) == 0 && ((uintptr_t)X % 16) == 0 && ((uintptr_t)ids % 8) == 0,
+             "sc_text_assemble: operands must be 16-byte aligned (ids: 8)");
+    hipLaunchKernelGGL(text_assemble_kernel, dim3(Bp * SEG), dim3(128), 0, (hipStream_t)stream, ids, ld_ids, table, ldt, pos, X, eot_row,
+                       (unsigned long long*)bad, B, L, V, W, SEG, n_pos);
     SC_LAUNCH_CHECK();
     return 0;
 }

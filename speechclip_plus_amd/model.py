@@ -159,7 +159,7 @@ def set_dropout(model: nn.Module, enabled: bool) -> nn.Module:
 
 class KWClip_GeneralTransformer(nn.Module):
     def __init__(self, config, image_encoder: Optional[Union[Callable, str]] = None, device: str = "cuda", hubert_state_dict=None,
-                 hubert_arch=None):
+                 hubert_arch=None, text_encoder: Optional[str] = None):
         super().__init__()
         if isinstance(config, str):                   # path of a reference yaml recipe (config/**/*.yaml parse unchanged)
             config = load_config(config)
@@ -172,6 +172,8 @@ class KWClip_GeneralTransformer(nn.Module):
             # frozen submodule (state-dict keys image_encoder.*); getTrainableParams lists modules by name and never includes it
             image_encoder = ClipImageEncoder(config.clip.get("name", "ViT-B/32"),
                                              image_encoder_trainable=bool(config.clip.get("image_encoder_trainable", False)))
+        if text_encoder is not None and text_encoder != "clip":
+            raise ValueError(f"text_encoder={text_encoder!r}: 'clip' (the frozen CLIP text tower) or None")
         self.audio_encoder_type = config.audio_encoder.type
         if self.audio_encoder_type != "FairseqHubert":
             raise NotImplementedError(f"audio_encoder.type = {self.audio_encoder_type}: only FairseqHubert is built "
@@ -212,6 +214,10 @@ class KWClip_GeneralTransformer(nn.Module):
             if ds is not None and ds.type == "cif":
                 self.quantity_loss_weight = ds.cif.get("quantity_loss_weight", 1.0)
                 self.quantity_loss_criteria = nn.L1Loss()
+        if self.clip is None and text_encoder == "clip":
+            # a recipe without a keyword branch holds no text tower: built on request for forward_text (caption embeddings, zero-shot
+            # retrieval).  Same module and state-dict keys (clip.model.*) as the keyword recipes', frozen, never in getTrainableParams.
+            self.clip = ClipModel(device=device, **{k: v for k, v in config.clip.items() if k not in ("embed_dim", "device")})
         if ms.parallel_objective_weight > 0 and self.cascaded_branch is None:
             logger.info("Create Parallel Branch")
             self.parallel_branch = KW_ParallelBranch(config=config, audio_dim=self.audio_embd_dim,
@@ -269,6 +275,46 @@ class KWClip_GeneralTransformer(nn.Module):
             raise ValueError(f"Incorrect image tensor shape {images.shape}")
         with torch.no_grad():
             return self.image_encoder(images)
+
+    def forward_text(self, sents: Union[list, torch.Tensor]) -> torch.Tensor:
+        """kwClip.py:509-527: sentences (through ``clip.prep_text``: needs a tokenizer) or a 2-D tensor of ORIGINAL CLIP token ids ->
+        caption embeddings [B, embed_dim] fp32 (un-normalised, as the reference returns them).  With a reduced vocabulary the ids are
+        mapped through one lookup tensor into a new tensor; the reference rewrites the caller's tensor element by element."""
+        if self.clip is None:
+            raise RuntimeError("forward_text needs the CLIP text tower: a keyword recipe holds one, any other builds it with "
+                               "text_encoder=\"clip\"")
+        if isinstance(sents, list):
+            return self.clip.encode_text(self.clip.prep_text(sents))
+        if not isinstance(sents, torch.Tensor):
+            raise TypeError(f"Unknown text type {type(sents)}")
+        if sents.dim() != 2:
+            raise ValueError(f"Incorrect text tensor shape {sents.shape}")
+        if self.clip.selected_text_emb_ids is None:
+            return self.clip.encode_text(sents)
+        return self.clip.encode_text(self.clip.to_reduced_ids(sents), _original=sents)
+
+    def reportRetrieval(self, score_per_A: torch.Tensor, score_per_B: torch.Tensor, AB_answers: torch.Tensor, BA_answers: torch.Tensor,
+                        metadata: dict = {"modality_A_title": "audio", "modality_B_title": "image", "modality_A_logAbbr": "A",
+                                          "modality_B_logAbbr": "I"}):
+        """kwClip.py:529-598: recall@k in both directions (retrieval.mutualRetrieval, on the device) under the modality names of
+        ``metadata``, logged as ``val_recall_{AB}`` / ``val_recall_{BA}`` / ``val_recall_mean`` / ``val_recall_mean_10`` through
+        log_dict; also returns the three dictionaries (the reference only logs them)."""
+        from .retrieval import mutualRetrieval
+        assert "modality_A_title" in metadata
+        assert "modality_B_title" in metadata
+        assert "modality_A_logAbbr" in metadata
+        assert "modality_B_logAbbr" in metadata
+        recall_AB, recall_BA, recall_mean = mutualRetrieval(score_per_A=score_per_A, score_per_B=score_per_B, AB_answers=AB_answers,
+                                                            BA_answers=BA_answers, recall_at=self.recall_at,
+                                                            modality_A_title=metadata["modality_A_title"],
+                                                            modality_B_title=metadata["modality_B_title"])
+        ab = "{}{}".format(metadata["modality_A_logAbbr"], metadata["modality_B_logAbbr"])
+        ba = "{}{}".format(metadata["modality_B_logAbbr"], metadata["modality_A_logAbbr"])
+        logged = {f"val_recall_{ab}": recall_AB, f"val_recall_{ba}": recall_BA, "val_recall_mean": recall_mean}
+        if "recall@10" in recall_mean:                  # the reference's checkpoint monitor (it requires 10 in recall_at)
+            logged["val_recall_mean_10"] = recall_mean["recall@10"]
+        self.log_dict(logged, sync_dist=True)
+        return recall_AB, recall_BA, recall_mean
 
     def processWavs(self, wav):
         wav_len = [len(x) for x in wav]
@@ -443,10 +489,12 @@ class KWClip_GeneralTransformer(nn.Module):
         """``log_setting.log_detokenize_results`` (kwClip.py:87-89).  The reference defaults to True; here a config without the key -
         or without ``log_setting`` - keeps validation exactly as it was."""
         ls = self.config.get("log_setting", None)
+        if self.cascaded_branch is None:               # a text tower alone (text_encoder="clip") has no keywords to detokenise
+            return False
         return bool(ls.get("log_detokenize_results", False)) if ls is not None else False
 
     def _token_table(self) -> torch.Tensor:
-        if self.clip is None:
+        if self.clip is None or self.cascaded_branch is None:
             raise RuntimeError("keyword detokenisation needs a keyword branch (cascaded+ / hybrid+ recipe): this model has no CLIP text side")
         return self.clip.model.token_embedding.weight
 

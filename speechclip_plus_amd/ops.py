@@ -168,7 +168,10 @@ def gemm_raw(A: torch.Tensor, lda: int, W: torch.Tensor, ldw: int, C: torch.Tens
     a.drop_p, a.drop_seed = float(drop_p), int(drop_seed) & 0xffffffff
     a.tap_c = int(tap_c)
     a.k_total = int(k_total)
-    if aux_mode:            # activation fused with a second [M, N] bf16 operand of C's row stride (sc_gemm_args.aux_mode)
+    if aux_mode == 3:       # forward-only twin of mode 1: the activation of the rounded pre-activation, which is not stored
+        assert aux is None and Ct is None
+        a.aux_mode = 3
+    elif aux_mode:          # activation fused with a second [M, N] bf16 operand of C's row stride (sc_gemm_args.aux_mode)
         assert aux is not None and aux.dtype == torch.bfloat16 and Ct is None and aux.stride(0) == ldc and aux.stride(1) == 1
         a.Ct, a.aux_mode = _p(aux), int(aux_mode)
     a.tn = int(tn)          # C[m, n] = sum_r A[r, m] W[r, n]: both operands row-indexed by the reduction (weight gradients)
@@ -251,7 +254,8 @@ def linear_bf16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
                 alg_rows: Optional[int] = None, tile: int = 0, drop_p: float = 0.0, drop_seed: int = 0,
                 aux: Optional[torch.Tensor] = None, aux_mode: int = 0, ln_colsum: Optional[torch.Tensor] = None, ln_eps: float = 0.0) -> torch.Tensor:
     """y[M, N] = epi(x[M, K] . w[N, K]^T) for contiguous 2-D operands.  ``aux`` / ``aux_mode`` (small problems, 128-row tiles):
-    1 = also store the pre-activation into ``aux`` and return act(it); 2 = return (x . w^T) * act'(aux).
+    1 = also store the pre-activation into ``aux`` and return act(it); 2 = return (x . w^T) * act'(aux); 3 = the values of 1, nothing
+    stored (``aux`` None).
     ``ln_colsum`` / ``ln_eps``: y = epi(LayerNorm(x) . w0^T) with the LayerNorm in the GEMM's prologue - ``w`` = w0 diag(gamma),
     ``ln_colsum[n]`` = sum_k w[n, k], ``bias[n]`` = sum_k beta[k] w0[n, k] + bias0[n] (``fold_layernorm``); K <= 1024."""
     M, K = x.shape
@@ -1538,6 +1542,29 @@ def prompt_assemble(keywords: torch.Tensor, count: torch.Tensor, tok: torch.Tens
     return X, eot_row
 
 
+def text_assemble(ids: torch.Tensor, table: torch.Tensor, pos: torch.Tensor, Bp: int, SEG: int, n_pos: int, out: Optional[torch.Tensor] = None,
+                  bad: Optional[torch.Tensor] = None):
+    """ids [B, L <= 77] int64 (unit column stride, any row stride), table [V, W] fp32 (rows dense), pos [>= n_pos, W] fp32 ->
+    X [Bp * SEG, W] bf16 (rows b SEG + t = table[ids[b, t]] + pos[t] for t < n_pos; zero elsewhere), eot_row [B] int32 (rows of X at the
+    first position of each caption's largest id, clamped to n_pos - 1), bad [1] int64 (clamps + ids outside [0, V), which embed as
+    zero) - sc_text_assemble.  ``out``: X's storage; ``bad``: a counter to add to instead of a fresh zero."""
+    B, L = ids.shape
+    V, W = table.shape
+    assert ids.dtype == torch.int64 and ids.stride(1) == 1 and (B == 1 or ids.stride(0) >= L)
+    assert table.dtype == torch.float32 and table.stride(1) == 1 and table.stride(0) >= W
+    assert pos.dtype == torch.float32 and pos.is_contiguous() and pos.shape[0] >= n_pos and pos.shape[1] == W
+    if out is None:
+        out = torch.empty(Bp * SEG, W, device=ids.device, dtype=torch.bfloat16)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (Bp * SEG, W)
+    eot_row = torch.empty(B, device=ids.device, dtype=torch.int32)
+    if bad is None:
+        bad = torch.zeros(1, device=ids.device, dtype=torch.int64)
+    assert bad.dtype == torch.int64 and bad.numel() == 1
+    check(lib().sc_text_assemble(_p(ids), ids.stride(0) if B > 1 else L, _p(table), table.stride(0), _p(pos), _p(out), _p(eot_row), _p(bad),
+                                 B, Bp, L, V, W, SEG, n_pos, _stream()), "sc_text_assemble")
+    return out, eot_row, bad
+
+
 def prompt_assemble_bwd(dX: torch.Tensor, count: torch.Tensor, B: int, N: int, SEG: int, n_pos: int) -> torch.Tensor:
     """dX [>= B * SEG, W] bf16 -> dkeywords [B, N, W] fp32 (rows behind a sample's keyword count: zero)"""
     W = dX.shape[1]
@@ -1548,10 +1575,12 @@ def prompt_assemble_bwd(dX: torch.Tensor, count: torch.Tensor, B: int, N: int, S
     return dk
 
 
-def rows_gather(X: torch.Tensor, row: torch.Tensor) -> torch.Tensor:
+def rows_gather(X: torch.Tensor, row: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[b] = float(X[row[b]]): X [M, W] bf16 contiguous, row [B] int32"""
     assert X.dtype == torch.bfloat16 and X.is_contiguous() and row.dtype == torch.int32
-    out = torch.empty(row.numel(), X.shape[1], device=X.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(row.numel(), X.shape[1], device=X.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (row.numel(), X.shape[1])
     check(lib().sc_rows_gather_bf16(_p(X), _p(row), _p(out), row.numel(), X.shape[1], _stream()), "sc_rows_gather_bf16")
     return out
 
