@@ -29,7 +29,8 @@ extern "C" {
 typedef uint16_t sc_bf16;
 
 const char* sc_last_error(void);
-int sc_abi_version(void);     /* 5: sc_adam_f32 takes its betas as doubles; 4 since round 4 (sc_segments; sc_gemm_args / sc_hubert_layer_args grew the segment fields) */
+int sc_abi_version(void);     /* 6: one front-end entry point per kernel (sc_wav_prep, sc_conv0_stats, sc_conv0_gn_gelu, sc_conv0_ln_gelu take
+                                 seg / wav_off / out_f32; their _seg, _crop, _len and _f32 symbols are gone); 5: sc_adam_f32 takes its betas as doubles; 4 since round 4 (sc_segments; sc_gemm_args / sc_hubert_layer_args grew the segment fields) */
 int sc_is_diag_build(void);   /* 1: libspeechclip_hip_diag.so - the same sources built with SC_DIAG_BUILD: also holds the diagnostic kernels
                                  (sc_gemm_args.tile 32 = timing only, RESULTS WRONG; 34 = stamped) and the LayerNorm-folded GEMMs; the
                                  product library refuses both */
@@ -226,27 +227,46 @@ int sc_layernorm_bf16(const sc_bf16* x, int64_t ldx, const float* gamma, const f
                       int64_t ldy, int64_t rows, int32_t D, float eps, int32_t act, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Waveform front end.
- *   sc_wav_prep: speech_encoder_plus.py:506-518 (optional per-utterance layer_norm over the whole
- *     waveform, zero padding) -> padded fp32 [B, ldw_out], samples >= wav_len[b] are 0.
- *   sc_conv0_stats + sc_conv0_finalize: GroupNorm(512,512) statistics of conv layer 0 over the padded
- *     time axis T0 (fairseq Fp32GroupNorm, "default" extractor mode) computed analytically from the
- *     10x10 Gram matrix of the strided waveform (fp64 accumulation) -> scale/shift [B, C] fp32.
- *   sc_conv0_gn_gelu: conv0 (C_in=1, k=10, s=5, no bias) + GroupNorm affine + GELU, channels-last bf16
- *     out[b*R0 + t, c].
+ * Waveform front end: one entry point per kernel; the row layout, the crop and the fp32 debug stores are arguments.
+ *   sc_wav_prep: speech_encoder_plus.py:506-518 (optional per-utterance layer_norm over the whole waveform, zero padding) of the
+ *     caller's [B, ldw_in] batch (padded length L) -> prepared fp32 waveform, samples >= wav_len[b] are 0.
+ *   sc_conv0_stats + sc_conv0_finalize: GroupNorm(512,512) statistics of conv layer 0 over the padded time axis T0 (fairseq
+ *     Fp32GroupNorm, "default" extractor mode) computed analytically from the 10x10 Gram matrix of the strided waveform (fp64
+ *     accumulation) -> scale/shift [B, C] fp32.
+ *   sc_conv0_gn_gelu: conv0 (C_in=1, k=10, s=5, no bias) + GroupNorm affine + GELU on the prepared waveform, channels-last.
+ *   sc_conv0_ln_gelu: "layer_norm" extractor mode (HuBERT-large): conv0 (+bias; NULL: none) -> LayerNorm over the 512 channels -> GELU.
+ * Row layout (seg; sc_wav_prep and the two conv-0 forwards).
+ *   NULL: uniform rows.  The prepared waveform is [B, ldw_out] (ldw_out >= L; read as [B, ldw], ldw >= 5 (R0 - 1) + 10) and
+ *     utterance b's R0 output rows are out[b*R0 + t, c].  samples_per_row is not read.
+ *   ragged rows (round 4; seg = the sc_segments tables): the prepared waveform is ONE flat buffer, utterance b at sample
+ *     samples_per_row * row0[b] (320 = 5 * 64: conv layer 0 then reads x[5 r + j] for its flat output row r = 64 * row0[b] + t, like
+ *     every later conv layer reads rows 2 r ..), zero from wav_len[b] to the end of its region; it needs samples_per_row * rows + 16
+ *     floats.  The conv-0 forwards write out row 64 * row0[b] + t for t < 64 * pitch_b.  B must equal seg->B; ldw_out / ldw / R0 are
+ *     not read.
+ * Crop (wav_off; the two kernels that read the caller's batch: sc_wav_prep, sc_conv0_stats).  The in-forward training crop (round 5):
+ *   avssl/module/speech_encoder_plus.py:548-552 calls random_crop_max_length (avssl/data/audio_transforms.py:5-23) per utterance on
+ *   the un-padded list and re-pads (:506-518).  Here the caller's [B, ldw] batch stays where it is: utterance b is
+ *   wav[b, wav_off[b] : wav_off[b] + wav_len[b]] (wav_len = the CROPPED lengths, L = their maximum, wav_off[b] + wav_len[b] <= ldw is
+ *   the caller's contract), read in place.  NULL: no crop.
+ * Padded-length statistics (wav_len of sc_conv0_stats).  The statistics run over the PADDED batch length T0 - fairseq feeds the
+ *   zero-padded batch (speech_encoder_plus.py:75) - whatever the row layout.  NULL: wav is the prepared, zero-padded batch
+ *   (ldw >= 5 (T0 - 1) + 10; no wav_off).  Otherwise wav is the caller's batch and samples >= wav_len[b] read as 0.
+ * out_f32 (the two conv-0 forwards).  0: out is sc_bf16*.  1: the fp32 debug mode - out is float*, the same arithmetic with unrounded
+ *   stores; uniform rows only, and sc_conv0_ln_gelu then always runs its two-pass kernel.
  * ---------------------------------------------------------------------------------------------- */
-int sc_wav_prep(const float* wav, int64_t ldw_in, const int64_t* wav_len, float* out, int64_t ldw_out,
-                int32_t B, int32_t L, int32_t normalize, void* stream);
+int sc_wav_prep(const float* wav, int64_t ldw_in, const int64_t* wav_len, const int64_t* wav_off, float* out, int64_t ldw_out,
+                const sc_segments* seg, int32_t samples_per_row, int32_t B, int32_t L, int32_t normalize, void* stream);
 #define SC_CONV0_NSTAT 66   /* 55 Gram entries + 10 sums + pad */
-int sc_conv0_stats(const float* wav, int64_t ldw, int32_t B, int32_t T0, int32_t nchunk, double* partial,
-                   void* stream);
+int sc_conv0_stats(const float* wav, int64_t ldw, const int64_t* wav_len, const int64_t* wav_off, int32_t B, int32_t T0, int32_t nchunk,
+                   double* partial, void* stream);
 int sc_conv0_finalize(const double* partial, int32_t nchunk, const float* w0 /*[C,10]*/, const float* gamma,
                       const float* beta, int32_t B, int32_t C, int32_t T0, float eps, float* scale,
                       float* shift, void* stream);
-int sc_conv0_gn_gelu(const float* wav, int64_t ldw, const float* w0, const float* scale, const float* shift,
-                     sc_bf16* out, int32_t B, int32_t R0, int32_t C, void* stream);
-int sc_conv0_gn_gelu_f32(const float* wav, int64_t ldw, const float* w0, const float* scale, const float* shift,
-                         float* out, int32_t B, int32_t R0, int32_t C, void* stream);      /* fp32 debug mode: unrounded stores */
+int sc_conv0_gn_gelu(const float* wav, int64_t ldw, const sc_segments* seg, int32_t samples_per_row, const float* w0, const float* scale,
+                     const float* shift, void* out, int32_t out_f32, int32_t B, int32_t R0, int32_t C, void* stream);
+int sc_conv0_ln_gelu(const float* wav, int64_t ldw, const sc_segments* seg, int32_t samples_per_row, const float* w0, const float* bias,
+                     const float* gamma, const float* beta, float eps, void* out, int32_t out_f32, int32_t B, int32_t R0, int32_t C,
+                     void* stream);
 /* backward of conv layer 0 + GroupNorm + GELU for the fully trainable encoder (speech_encoder_plus.py:556-562; the input is the
  * waveform: parameter gradients only).  dy [B*R0, 512] bf16 = gradient of the layer's output, scale / shift / stats = the forward's
  * (sc_conv0_finalize, sc_conv0_stats with nchunk chunks).  partial: scratch [B, nwc, 512, 12] fp32 (nwc % 4 == 0 wave chunks);
@@ -259,37 +279,6 @@ int sc_conv0_gn_bwd(const float* wav, int64_t ldw, const float* w0, const float*
  * B * nwc with sc_colsum_f32 (nwc % 4 == 0). */
 int sc_conv0_ln_bwd(const float* wav, int64_t ldw, const float* w0, const float* bias, const float* gamma, const float* beta, float eps,
                     const sc_bf16* dy, int32_t B, int32_t T0, int32_t R0, int32_t C, float* partial, int32_t nwc, void* stream);
-/* Ragged rows (sc_segments; round 4).  The prepared waveform is ONE flat buffer, utterance b at sample samples_per_row * row0[b]
- * (320 = 5 * 64: conv layer 0 then reads x[5 r + j] for its flat output row r = 64 * row0[b] + t, like every later conv layer reads
- * rows 2 r ..), zero from wav_len[b] to the end of its region; out needs samples_per_row * rows + 16 floats.
- *   sc_wav_prep_seg    : as sc_wav_prep into that layout
- *   sc_conv0_stats_len : GroupNorm statistics straight from the caller's [B, ldw] batch, samples >= wav_len[b] read as 0 (the
- *                        statistics run over the PADDED batch length T0 - fairseq semantics - whatever the row layout)
- *   sc_conv0_gn_gelu_seg / sc_conv0_ln_gelu_seg : conv layer 0 on the flat waveform, out row 64 * row0[b] + t for t < 64 * pitch_b */
-int sc_wav_prep_seg(const float* wav, int64_t ldw_in, const int64_t* wav_len, float* out, const sc_segments* seg,
-                    int32_t samples_per_row, int32_t L, int32_t normalize, void* stream);
-int sc_conv0_stats_len(const float* wav, int64_t ldw, const int64_t* wav_len, int32_t B, int32_t T0, int32_t nchunk, double* partial,
-                       void* stream);
-int sc_conv0_gn_gelu_seg(const float* wav_flat, const sc_segments* seg, int32_t samples_per_row, const float* w0, const float* scale,
-                         const float* shift, sc_bf16* out, int32_t C, void* stream);
-/* The in-forward training crop (round 5): avssl/module/speech_encoder_plus.py:548-552 calls random_crop_max_length
- * (avssl/data/audio_transforms.py:5-23) per utterance on the un-padded list and re-pads (:506-518).  Here the caller's [B, ldw] batch
- * stays where it is: utterance b is wav[b, wav_off[b] : wav_off[b] + wav_len[b]] (wav_len = the CROPPED lengths, L = their maximum,
- * wav_off[b] + wav_len[b] <= ldw is the caller's contract), read in place by the two kernels that touch the caller's batch.
- * wav_off == NULL: the un-cropped entry points above. */
-int sc_wav_prep_crop(const float* wav, int64_t ldw_in, const int64_t* wav_len, const int64_t* wav_off, float* out, int64_t ldw_out,
-                     int32_t B, int32_t L, int32_t normalize, void* stream);
-int sc_wav_prep_seg_crop(const float* wav, int64_t ldw_in, const int64_t* wav_len, const int64_t* wav_off, float* out,
-                         const sc_segments* seg, int32_t samples_per_row, int32_t L, int32_t normalize, void* stream);
-int sc_conv0_stats_len_crop(const float* wav, int64_t ldw, const int64_t* wav_len, const int64_t* wav_off, int32_t B, int32_t T0,
-                            int32_t nchunk, double* partial, void* stream);
-int sc_conv0_ln_gelu_seg(const float* wav_flat, const sc_segments* seg, int32_t samples_per_row, const float* w0, const float* bias,
-                         const float* gamma, const float* beta, float eps, sc_bf16* out, int32_t C, void* stream);
-/* "layer_norm" extractor mode (HuBERT-large): conv0 (+bias) -> LayerNorm over the 512 channels -> GELU */
-int sc_conv0_ln_gelu(const float* wav, int64_t ldw, const float* w0, const float* bias, const float* gamma,
-                     const float* beta, float eps, sc_bf16* out, int32_t B, int32_t R0, int32_t C, void* stream);
-int sc_conv0_ln_gelu_f32(const float* wav, int64_t ldw, const float* w0, const float* bias, const float* gamma,
-                         const float* beta, float eps, float* out, int32_t B, int32_t R0, int32_t C, void* stream);   /* fp32 debug mode */
 
 /* ------------------------------------------------------------------------------------------------
  * pos_conv input: zero padded frames (speech_encoder_plus.py:32-33 index_put(x, padding_mask, 0)) and
@@ -396,7 +385,7 @@ int sc_softmax_fwd(const float* scores, const uint8_t* key_mask, sc_bf16* P, sc_
 int sc_softmax_bwd(const float* dP, const sc_bf16* P, sc_bf16* dS, int64_t rows, int32_t n, float scale, float drop_p,
                    uint32_t drop_seed, void* stream);
 /* fp32 DEBUG mode (SURVEY 8d "fp32 kernel mode (for debugging)"; host side speechclip_plus_amd/debug_fp32.py): the same kernels with
- * unrounded fp32 outputs - softmax probabilities here, the conv layer 0 activations below (sc_conv0_gn_gelu_f32, sc_conv0_ln_gelu_f32);
+ * unrounded fp32 outputs - softmax probabilities here, the conv layer 0 activations above (out_f32 of sc_conv0_gn_gelu / sc_conv0_ln_gelu);
  * every product of that mode runs on sc_sgemm_mfma_f32 / sc_sgemm_f32_ex, the norms on sc_rowln_f32_fwd, GELU on sc_gelu_f32. */
 int sc_softmax_fwd_f32(const float* scores, const uint8_t* key_mask, float* P, int64_t rows, int32_t n, int32_t rows_per_batch,
                        float scale, void* stream);

@@ -114,13 +114,6 @@ SIGNATURES = {
                          c_float, ctypes.c_uint32, c_void_p],
     "sc_attn_fwd_seg_bf16": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, ctypes.POINTER(Segments), c_void_p, c_int, c_int, c_int,
                              c_float, c_void_p, c_int, c_float, ctypes.c_uint32, c_void_p],
-    "sc_wav_prep_seg": [c_void_p, c_i64, c_void_p, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_void_p],
-    "sc_conv0_stats_len": [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
-    "sc_wav_prep_crop": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p],
-    "sc_wav_prep_seg_crop": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_void_p],
-    "sc_conv0_stats_len_crop": [c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
-    "sc_conv0_gn_gelu_seg": [c_void_p, ctypes.POINTER(Segments), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "sc_conv0_ln_gelu_seg": [c_void_p, ctypes.POINTER(Segments), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p],
     "sc_posconv_prep_seg": [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_void_p],
     "sc_posconv_seg_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_void_p],
     "sc_wsum_fwd_seg": [c_void_p, c_void_p, c_int, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_int, c_void_p],
@@ -136,13 +129,12 @@ SIGNATURES = {
     "sc_attn32_fwd_bf16": [c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_float, c_void_p],
     "sc_attn32_bwd_bf16": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_float, c_void_p],
     "sc_layernorm_bf16": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_float, c_int, c_void_p],
-    "sc_wav_prep": [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p],
-    "sc_conv0_stats": [c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p],
+    "sc_wav_prep": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, ctypes.POINTER(Segments), c_int, c_int, c_int, c_int, c_void_p],
+    "sc_conv0_stats": [c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "sc_conv0_finalize": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
-    "sc_conv0_gn_gelu": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "sc_conv0_ln_gelu": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p],
-    "sc_conv0_gn_gelu_f32": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "sc_conv0_ln_gelu_f32": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p],
+    "sc_conv0_gn_gelu": [c_void_p, c_i64, ctypes.POINTER(Segments), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "sc_conv0_ln_gelu": [c_void_p, c_i64, ctypes.POINTER(Segments), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int,
+                         c_int, c_void_p],
     "sc_softmax_fwd_f32": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, ctypes.c_float, c_void_p],
     "sc_conv0_ln_bwd": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
     "sc_posconv_prep": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],

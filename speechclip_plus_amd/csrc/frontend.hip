@@ -730,62 +730,34 @@ __global__ __launch_bounds__(256) void conv0_gn_bwd_finalize_kernel(const float*
 
 }  // namespace
 
-extern "C" int sc_wav_prep(const float* wav, int64_t ldw_in, const int64_t* wav_len, float* out, int64_t ldw_out,
-                           int32_t B, int32_t L, int32_t normalize, void* stream) {
-    SC_CHECK(wav && wav_len && out, "sc_wav_prep: null pointer");
-    SC_CHECK(B > 0 && L > 0 && ldw_out >= L && ldw_in >= L, "sc_wav_prep: bad sizes");
+// ---------------------------------------------------------------------------------------- C entry points
+// One entry per kernel.  The row layout (seg == NULL: uniform rows; seg: the ragged layout of sc_segments), the in-forward crop
+// (wav_off) and the fp32 debug stores (out_f32) are arguments: include/speechclip_hip.h, "Waveform front end".
+extern "C" int sc_wav_prep(const float* wav, int64_t ldw_in, const int64_t* wav_len, const int64_t* wav_off, float* out, int64_t ldw_out,
+                           const sc_segments* seg, int32_t samples_per_row, int32_t B, int32_t L, int32_t normalize, void* stream) {
+    SC_CHECK(wav && wav_len && out && (!seg || seg->row0), "sc_wav_prep: null pointer");
+    SC_CHECK(B > 0 && L > 0 && ldw_in >= L, "sc_wav_prep: bad sizes");
+    if (seg)
+        SC_CHECK(seg->B == B && samples_per_row > 0 && samples_per_row % 5 == 0,
+                 "sc_wav_prep: B=%d against seg->B=%d, samples_per_row=%d must be a positive multiple of 5", B, seg->B, samples_per_row);
+    else
+        SC_CHECK(ldw_out >= L, "sc_wav_prep: ldw_out < L");
     // without normalisation the kernel is a pure copy: spread each utterance over 32 blocks
-    hipLaunchKernelGGL(wav_prep_kernel, dim3(B, normalize ? 4 : 32), dim3(normalize ? 1024 : 256), 0, (hipStream_t)stream, wav, ldw_in, wav_len, out, ldw_out, L, normalize, (const int32_t*)nullptr, 0, (const int64_t*)nullptr);
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sc_wav_prep_seg_crop(const float* wav, int64_t ldw_in, const int64_t* wav_len, const int64_t* wav_off, float* out,
-                                    const sc_segments* seg, int32_t samples_per_row, int32_t L, int32_t normalize, void* stream) {
-    SC_CHECK(wav && wav_len && out && seg && seg->row0, "sc_wav_prep_seg: null pointer");
-    SC_CHECK(seg->B > 0 && L > 0 && ldw_in >= L && samples_per_row > 0 && samples_per_row % 5 == 0, "sc_wav_prep_seg: bad sizes");
-    hipLaunchKernelGGL(wav_prep_kernel, dim3(seg->B, normalize ? 4 : 32), dim3(normalize ? 1024 : 256), 0, (hipStream_t)stream, wav, ldw_in, wav_len,
-                       out, (int64_t)0, L, normalize, seg->row0, samples_per_row, wav_off);
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sc_wav_prep_seg(const float* wav, int64_t ldw_in, const int64_t* wav_len, float* out, const sc_segments* seg,
-                               int32_t samples_per_row, int32_t L, int32_t normalize, void* stream) {
-    return sc_wav_prep_seg_crop(wav, ldw_in, wav_len, nullptr, out, seg, samples_per_row, L, normalize, stream);
-}
-
-extern "C" int sc_wav_prep_crop(const float* wav, int64_t ldw_in, const int64_t* wav_len, const int64_t* wav_off, float* out,
-                                int64_t ldw_out, int32_t B, int32_t L, int32_t normalize, void* stream) {
-    SC_CHECK(wav && wav_len && out, "sc_wav_prep_crop: null pointer");
-    SC_CHECK(B > 0 && L > 0 && ldw_out >= L && ldw_in >= L, "sc_wav_prep_crop: bad sizes");
     hipLaunchKernelGGL(wav_prep_kernel, dim3(B, normalize ? 4 : 32), dim3(normalize ? 1024 : 256), 0, (hipStream_t)stream, wav, ldw_in, wav_len, out,
-                       ldw_out, L, normalize, (const int32_t*)nullptr, 0, wav_off);
+                       seg ? (int64_t)0 : ldw_out, L, normalize, seg ? seg->row0 : (const int32_t*)nullptr, seg ? samples_per_row : 0, wav_off);
     SC_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int sc_conv0_stats(const float* wav, int64_t ldw, int32_t B, int32_t T0, int32_t nchunk, double* partial,
-                              void* stream) {
+extern "C" int sc_conv0_stats(const float* wav, int64_t ldw, const int64_t* wav_len, const int64_t* wav_off, int32_t B, int32_t T0, int32_t nchunk,
+                              double* partial, void* stream) {
     SC_CHECK(wav && partial, "sc_conv0_stats: null pointer");
-    SC_CHECK(B > 0 && T0 > 0 && nchunk > 0 && ldw >= 5 * (int64_t)(T0 - 1) + 10, "sc_conv0_stats: bad sizes");
-    hipLaunchKernelGGL(conv0_stats_kernel, dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, wav, ldw, T0, nchunk, partial, (const int64_t*)nullptr, (const int64_t*)nullptr);
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sc_conv0_stats_len_crop(const float* wav, int64_t ldw, const int64_t* wav_len, const int64_t* wav_off, int32_t B, int32_t T0,
-                                       int32_t nchunk, double* partial, void* stream) {
-    SC_CHECK(wav && wav_len && partial, "sc_conv0_stats_len: null pointer");
-    SC_CHECK(B > 0 && T0 > 0 && nchunk > 0, "sc_conv0_stats_len: bad sizes");
+    SC_CHECK(wav_len || !wav_off, "sc_conv0_stats: wav_off needs wav_len");
+    // with wav_len the kernel masks every read at and past wav_len[b]: only the prepared batch has to hold all T0 windows
+    SC_CHECK(B > 0 && T0 > 0 && nchunk > 0 && (wav_len || ldw >= 5 * (int64_t)(T0 - 1) + 10), "sc_conv0_stats: bad sizes");
     hipLaunchKernelGGL(conv0_stats_kernel, dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, wav, ldw, T0, nchunk, partial, wav_len, wav_off);
     SC_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int sc_conv0_stats_len(const float* wav, int64_t ldw, const int64_t* wav_len, int32_t B, int32_t T0, int32_t nchunk,
-                                  double* partial, void* stream) {
-    return sc_conv0_stats_len_crop(wav, ldw, wav_len, nullptr, B, T0, nchunk, partial, stream);
 }
 
 extern "C" int sc_conv0_finalize(const double* partial, int32_t nchunk, const float* w0, const float* gamma,
@@ -797,61 +769,61 @@ extern "C" int sc_conv0_finalize(const double* partial, int32_t nchunk, const fl
     return 0;
 }
 
-extern "C" int sc_conv0_gn_gelu(const float* wav, int64_t ldw, const float* w0, const float* scale, const float* shift,
-                                sc_bf16* out, int32_t B, int32_t R0, int32_t C, void* stream) {
+// the row layout of a conv-0 forward as its kernels take it - (ldw, R0) for uniform rows, (row0, spr) for the segment layout - and the
+// grid over it: 128 output rows per workgroup, as many workgroups per utterance as the longest one needs
+constexpr int C0_ROWS_PER_BLOCK = 128;
+struct conv0_rows {
+    int64_t ldw;
+    int R0;
+    const int32_t* row0;
+    int spr;
+    dim3 grid;
+};
+
+// the layout and output checks sc_conv0_gn_gelu and sc_conv0_ln_gelu (`who`) share; fills r.  0, or -1 with the error set
+static int conv0_fwd_rows(const char* who, int64_t ldw, const sc_segments* seg, int32_t spr, const void* out, int32_t out_f32, int32_t B,
+                          int32_t R0, conv0_rows* r) {
+    SC_CHECK(!seg || seg->row0, "%s: null pointer", who);
+    SC_CHECK(((uintptr_t)out % 16) == 0, "%s: alignment", who);
+    if (seg) {
+        SC_CHECK(!out_f32, "%s: out_f32 is for uniform rows only", who);
+        SC_CHECK(seg->B > 0 && seg->B == B && seg->max_pitch > 0 && spr > 0 && spr % 5 == 0,
+                 "%s: B=%d against seg->B=%d, samples_per_row=%d must be a positive multiple of 5", who, B, seg->B, spr);
+    } else {
+        SC_CHECK(ldw >= 5 * (int64_t)(R0 - 1) + 10, "%s: ldw=%lld too small for R0=%d", who, (long long)ldw, R0);
+    }
+    const int rows = seg ? seg->max_pitch * (spr / 5) : R0;
+    const dim3 grid((rows + C0_ROWS_PER_BLOCK - 1) / C0_ROWS_PER_BLOCK, B);
+    *r = seg ? conv0_rows{0, 0, seg->row0, spr, grid} : conv0_rows{ldw, R0, nullptr, 0, grid};
+    return 0;
+}
+
+extern "C" int sc_conv0_gn_gelu(const float* wav, int64_t ldw, const sc_segments* seg, int32_t samples_per_row, const float* w0, const float* scale,
+                                const float* shift, void* out, int32_t out_f32, int32_t B, int32_t R0, int32_t C, void* stream) {
     SC_CHECK(wav && w0 && scale && shift && out, "sc_conv0_gn_gelu: null pointer");
-    SC_CHECK(C % 512 == 0 && ldw >= 5 * (int64_t)(R0 - 1) + 10, "sc_conv0_gn_gelu: C=%d must be a multiple of 512; ldw too small", C);
-    SC_CHECK(((uintptr_t)out % 16) == 0, "sc_conv0_gn_gelu: alignment");
-    const int rows_per_block = 128;
-    dim3 grid((R0 + rows_per_block - 1) / rows_per_block, B);
-    hipLaunchKernelGGL(conv0_gn_gelu_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, wav, ldw, w0, scale, shift, (void*)out, R0, C, rows_per_block,
-                       (const int32_t*)nullptr, 0);
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sc_conv0_gn_gelu_seg(const float* wav_flat, const sc_segments* seg, int32_t samples_per_row, const float* w0, const float* scale,
-                                    const float* shift, sc_bf16* out, int32_t C, void* stream) {
-    SC_CHECK(wav_flat && seg && seg->row0 && w0 && scale && shift && out, "sc_conv0_gn_gelu_seg: null pointer");
-    SC_CHECK(C % 512 == 0 && samples_per_row > 0 && samples_per_row % 5 == 0 && seg->B > 0 && seg->max_pitch > 0,
-             "sc_conv0_gn_gelu_seg: C=%d must be a multiple of 512, samples_per_row a multiple of 5", C);
-    SC_CHECK(((uintptr_t)out % 16) == 0, "sc_conv0_gn_gelu_seg: alignment");
-    const int rows_per_block = 128;
-    const int R0max = seg->max_pitch * (samples_per_row / 5);
-    dim3 grid((R0max + rows_per_block - 1) / rows_per_block, seg->B);
-    hipLaunchKernelGGL(conv0_gn_gelu_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, wav_flat, (int64_t)0, w0, scale, shift, (void*)out, 0, C,
-                       rows_per_block, seg->row0, samples_per_row);
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sc_conv0_gn_gelu_f32(const float* wav, int64_t ldw, const float* w0, const float* scale, const float* shift,
-                                    float* out, int32_t B, int32_t R0, int32_t C, void* stream) {
-    SC_CHECK(wav && w0 && scale && shift && out, "sc_conv0_gn_gelu_f32: null pointer");
-    SC_CHECK(C % 512 == 0 && ldw >= 5 * (int64_t)(R0 - 1) + 10, "sc_conv0_gn_gelu_f32: C=%d must be a multiple of 512; ldw too small", C);
-    SC_CHECK(((uintptr_t)out % 16) == 0, "sc_conv0_gn_gelu_f32: alignment");
-    const int rows_per_block = 128;
-    dim3 grid((R0 + rows_per_block - 1) / rows_per_block, B);
-    hipLaunchKernelGGL(conv0_gn_gelu_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, wav, ldw, w0, scale, shift, (void*)out, R0, C, rows_per_block,
-                       (const int32_t*)nullptr, 0);
+    SC_CHECK(C % 512 == 0, "sc_conv0_gn_gelu: C=%d must be a multiple of 512", C);
+    conv0_rows r;
+    if (conv0_fwd_rows("sc_conv0_gn_gelu", ldw, seg, samples_per_row, out, out_f32, B, R0, &r)) return -1;
+    const auto kernel = !out_f32 ? conv0_gn_gelu_kernel<false> : conv0_gn_gelu_kernel<true>;
+    hipLaunchKernelGGL(kernel, r.grid, dim3(256), 0, (hipStream_t)stream, wav, r.ldw, w0, scale, shift, out, r.R0, C, C0_ROWS_PER_BLOCK, r.row0, r.spr);
     SC_LAUNCH_CHECK();
     return 0;
 }
 
 // layer_norm-mode conv 0 through the closed-form row statistics (round 6): 77 raw channel sums into a stream-ordered scratch of 616
 // bytes (hipMallocAsync / hipFreeAsync on the caller's stream: nothing outlives the call, nothing is shared between streams), then the
-// main kernel.  sc_set_option(2, 1): the two-pass reduction kernel, for A/B (tools/bench_conv0ln.py).  Returns 1 (caller falls back to
-// the two-pass kernel) when the runtime has no stream-ordered allocator.
-static int conv0_ln_closed_form(const float* wav, int64_t ldw, const float* w0, const float* bias, const float* gamma, const float* beta, float eps,
-                                sc_bf16* out, dim3 grid, int R0, const int32_t* row0, int spr, hipStream_t s) {
+// main kernel.  Returns 1 (caller falls back to the two-pass kernel) when the runtime has no stream-ordered allocator.
+static int conv0_ln_closed_form(const float* wav, const float* w0, const float* bias, const float* gamma, const float* beta, float eps, sc_bf16* out,
+                                const conv0_rows& r, hipStream_t s) {
+    static_assert(C0_ROWS_PER_BLOCK == 128, "conv0_ln_gelu_stats_kernel walks 128 rows per workgroup (RPB)");
     double* raw = nullptr;
     if (hipMallocAsync((void**)&raw, C0LN_RAW * sizeof(double), s) != hipSuccess) {
         (void)hipGetLastError();                    // no stream-ordered allocator on this runtime / device: the two-pass kernel needs no scratch
         return 1;
     }
     hipLaunchKernelGGL(conv0_ln_consts_kernel, dim3(C0LN_RAW), dim3(256), 0, s, w0, bias, raw);
-    hipLaunchKernelGGL(conv0_ln_gelu_stats_kernel, grid, dim3(256), 0, s, wav, ldw, w0, bias, gamma, beta, eps, (const double*)raw, (uint16_t*)out, R0,
-                       row0, spr);
+    hipLaunchKernelGGL(conv0_ln_gelu_stats_kernel, r.grid, dim3(256), 0, s, wav, r.ldw, w0, bias, gamma, beta, eps, (const double*)raw, (uint16_t*)out,
+                       r.R0, r.row0, r.spr);
     const hipError_t le = hipGetLastError();
     const hipError_t fe = hipFreeAsync(raw, s);
     if (le != hipSuccess || fe != hipSuccess) {
@@ -861,51 +833,22 @@ static int conv0_ln_closed_form(const float* wav, int64_t ldw, const float* w0, 
     return 0;
 }
 
-extern "C" int sc_conv0_ln_gelu(const float* wav, int64_t ldw, const float* w0, const float* bias, const float* gamma,
-                                const float* beta, float eps, sc_bf16* out, int32_t B, int32_t R0, int32_t C, void* stream) {
+extern "C" int sc_conv0_ln_gelu(const float* wav, int64_t ldw, const sc_segments* seg, int32_t samples_per_row, const float* w0, const float* bias,
+                                const float* gamma, const float* beta, float eps, void* out, int32_t out_f32, int32_t B, int32_t R0, int32_t C,
+                                void* stream) {
     SC_CHECK(wav && w0 && gamma && beta && out, "sc_conv0_ln_gelu: null pointer");
-    SC_CHECK(C == 512 && ldw >= 5 * (int64_t)(R0 - 1) + 10, "sc_conv0_ln_gelu: C must be 512 (got %d); ldw too small", C);
-    SC_CHECK(((uintptr_t)out % 16) == 0, "sc_conv0_ln_gelu: alignment");
-    const int rows_per_block = 128;
-    dim3 grid((R0 + rows_per_block - 1) / rows_per_block, B);
-    if (!sc_option(2)) {
-        const int rc = conv0_ln_closed_form(wav, ldw, w0, bias, gamma, beta, eps, out, grid, R0, nullptr, 0, (hipStream_t)stream);
+    SC_CHECK(C == 512, "sc_conv0_ln_gelu: C must be 512 (got %d)", C);
+    conv0_rows r;
+    if (conv0_fwd_rows("sc_conv0_ln_gelu", ldw, seg, samples_per_row, out, out_f32, B, R0, &r)) return -1;
+    // bf16 stores: the closed form, unless sc_set_option(2, 1) asks for the two-pass reduction kernel (A/B: tools/bench_conv0ln.py);
+    // the fp32 debug stores exist in the two-pass kernel only
+    if (!out_f32 && !sc_option(2)) {
+        const int rc = conv0_ln_closed_form(wav, w0, bias, gamma, beta, eps, (sc_bf16*)out, r, (hipStream_t)stream);
         if (rc <= 0) return rc;
     }
-    hipLaunchKernelGGL(conv0_ln_gelu_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, wav, ldw, w0, bias, gamma, beta, eps, (void*)out, R0, rows_per_block,
-                       (const int32_t*)nullptr, 0);
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sc_conv0_ln_gelu_seg(const float* wav_flat, const sc_segments* seg, int32_t samples_per_row, const float* w0, const float* bias,
-                                    const float* gamma, const float* beta, float eps, sc_bf16* out, int32_t C, void* stream) {
-    SC_CHECK(wav_flat && seg && seg->row0 && w0 && gamma && beta && out, "sc_conv0_ln_gelu_seg: null pointer");
-    SC_CHECK(C == 512 && samples_per_row > 0 && samples_per_row % 5 == 0 && seg->B > 0 && seg->max_pitch > 0,
-             "sc_conv0_ln_gelu_seg: C must be 512 (got %d), samples_per_row a multiple of 5", C);
-    SC_CHECK(((uintptr_t)out % 16) == 0, "sc_conv0_ln_gelu_seg: alignment");
-    const int rows_per_block = 128;
-    const int R0max = seg->max_pitch * (samples_per_row / 5);
-    dim3 grid((R0max + rows_per_block - 1) / rows_per_block, seg->B);
-    if (!sc_option(2)) {
-        const int rc = conv0_ln_closed_form(wav_flat, 0, w0, bias, gamma, beta, eps, out, grid, 0, seg->row0, samples_per_row, (hipStream_t)stream);
-        if (rc <= 0) return rc;
-    }
-    hipLaunchKernelGGL(conv0_ln_gelu_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, wav_flat, (int64_t)0, w0, bias, gamma, beta, eps, (void*)out, 0,
-                       rows_per_block, seg->row0, samples_per_row);
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sc_conv0_ln_gelu_f32(const float* wav, int64_t ldw, const float* w0, const float* bias, const float* gamma,
-                                    const float* beta, float eps, float* out, int32_t B, int32_t R0, int32_t C, void* stream) {
-    SC_CHECK(wav && w0 && gamma && beta && out, "sc_conv0_ln_gelu_f32: null pointer");
-    SC_CHECK(C == 512 && ldw >= 5 * (int64_t)(R0 - 1) + 10, "sc_conv0_ln_gelu_f32: C must be 512 (got %d); ldw too small", C);
-    SC_CHECK(((uintptr_t)out % 16) == 0, "sc_conv0_ln_gelu_f32: alignment");
-    const int rows_per_block = 128;
-    dim3 grid((R0 + rows_per_block - 1) / rows_per_block, B);
-    hipLaunchKernelGGL(conv0_ln_gelu_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, wav, ldw, w0, bias, gamma, beta, eps, (void*)out, R0, rows_per_block,
-                       (const int32_t*)nullptr, 0);
+    const auto kernel = !out_f32 ? conv0_ln_gelu_kernel<false> : conv0_ln_gelu_kernel<true>;
+    hipLaunchKernelGGL(kernel, r.grid, dim3(256), 0, (hipStream_t)stream, wav, r.ldw, w0, bias, gamma, beta, eps, out, r.R0, C0_ROWS_PER_BLOCK, r.row0,
+                       r.spr);
     SC_LAUNCH_CHECK();
     return 0;
 }

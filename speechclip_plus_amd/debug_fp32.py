@@ -4,7 +4,7 @@ Same algorithm, same masks, same layouts of the reference's customHubertForward 
 506-611) as the production path, but every tensor stays fp32 and every product runs in exact fp32 on the matrix pipe
 (sc_sgemm_mfma_f32; the per-head attention products on the batched sc_sgemm_f32_ex), the norms on sc_rowln_f32_fwd, GELU on
 sc_gelu_f32, the softmax and conv layer 0 on the fp32-output variants of the production kernels (sc_softmax_fwd_f32,
-sc_conv0_gn_gelu_f32 / sc_conv0_ln_gelu_f32).  What it is for: separating "a kernel computes the wrong thing" from "bf16 storage
+out_f32 of sc_conv0_gn_gelu / sc_conv0_ln_gelu).  What it is for: separating "a kernel computes the wrong thing" from "bf16 storage
 rounds" - in this mode the 13 / 25 hidden states must agree with the fp32 oracle to ~1e-5 (tests/test_gpu_model.py::
 test_fp32_debug_mode_matches_the_oracle), so whatever the production path differs by beyond that is storage precision
 (cf. the bf16-storage-emulated oracle, tests/test_gpu_recall.py).
@@ -74,17 +74,10 @@ def hubert_hidden_states_fp32(sd: Dict[str, torch.Tensor], arch, wavs: Sequence[
     if ln_mode:
         b0 = _f32(sd["feature_extractor.conv_layers.0.0.bias"], dev) if arch.conv_bias else None
         gam, bet = _f32(sd["feature_extractor.conv_layers.0.2.1.weight"], dev), _f32(sd["feature_extractor.conv_layers.0.2.1.bias"], dev)
-        check(L_.sc_conv0_ln_gelu_f32(_p(wav_pad), ldw, _p(w0), _p(b0), _p(gam), _p(bet), 1e-5, _p(x), B, T0, C, _stream()),
-              "sc_conv0_ln_gelu_f32")
+        ops.conv0_layernorm_gelu(wav_pad, w0, b0, gam, bet, T0, x, out_f32=True)
     else:
-        nchunk = 32
-        partial = torch.empty(B * nchunk * 66, device=dev, dtype=torch.float64)
-        scale, shift = torch.empty(B, C, device=dev), torch.empty(B, C, device=dev)
         gam, bet = _f32(sd["feature_extractor.conv_layers.0.2.weight"], dev), _f32(sd["feature_extractor.conv_layers.0.2.bias"], dev)
-        check(L_.sc_conv0_stats(_p(wav_pad), ldw, B, T0, nchunk, _p(partial), _stream()), "sc_conv0_stats")
-        check(L_.sc_conv0_finalize(_p(partial), nchunk, _p(w0), _p(gam), _p(bet), B, C, T0, 1e-5, _p(scale), _p(shift), _stream()),
-              "sc_conv0_finalize")
-        check(L_.sc_conv0_gn_gelu_f32(_p(wav_pad), ldw, _p(w0), _p(scale), _p(shift), _p(x), B, T0, C, _stream()), "sc_conv0_gn_gelu_f32")
+        ops.conv0_groupnorm_gelu(wav_pad, w0, gam, bet, T0, T0, x, nchunk=32, out_f32=True)
     x = x.view(B, T0, C)
     if debug is not None:
         debug["conv"] = [x]

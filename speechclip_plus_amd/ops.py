@@ -987,22 +987,40 @@ def _wav_window(wav: torch.Tensor, L: Optional[int], wav_off: Optional[torch.Ten
 
 def wav_prep(wav: torch.Tensor, wav_len: torch.Tensor, out: torch.Tensor, normalize: bool, L: Optional[int] = None,
              wav_off: Optional[torch.Tensor] = None) -> None:
-    """L / wav_off: the in-forward crop - utterance b is wav[b, off_b : off_b + len_b], padded length L (sc_wav_prep_crop)"""
+    """L / wav_off: the in-forward crop - utterance b is wav[b, off_b : off_b + len_b], padded length L (sc_wav_prep, uniform rows)"""
     assert wav_len.dtype == torch.int64 and out.dtype == torch.float32
     L = _wav_window(wav, L, wav_off)
-    check(lib().sc_wav_prep_crop(_p(wav), wav.stride(0), _p(wav_len), _p(wav_off), _p(out), out.stride(0), wav.shape[0], L, int(normalize),
-                                 _stream()), "sc_wav_prep_crop")
+    check(lib().sc_wav_prep(_p(wav), wav.stride(0), _p(wav_len), _p(wav_off), _p(out), out.stride(0), None, 0, wav.shape[0], L, int(normalize),
+                            _stream()), "sc_wav_prep")
 
 
 def wav_prep_seg(wav: torch.Tensor, wav_len: torch.Tensor, out_flat: torch.Tensor, seg: "RowSegments", samples_per_row: int,
                  normalize: bool, L: Optional[int] = None, wav_off: Optional[torch.Tensor] = None) -> None:
-    """waveform into the ragged layout: utterance b at sample samples_per_row * row0[b] of ONE flat fp32 buffer (sc_wav_prep_seg);
+    """waveform into the ragged layout: utterance b at sample samples_per_row * row0[b] of ONE flat fp32 buffer (sc_wav_prep with seg);
     L / wav_off as in wav_prep"""
     assert wav_len.dtype == torch.int64 and out_flat.dtype == torch.float32
     assert out_flat.numel() >= samples_per_row * seg.rows + 16
     L = _wav_window(wav, L, wav_off)
-    check(lib().sc_wav_prep_seg_crop(_p(wav), wav.stride(0), _p(wav_len), _p(wav_off), _p(out_flat), seg.ref(), samples_per_row, L,
-                                     int(normalize), _stream()), "sc_wav_prep_seg_crop")
+    check(lib().sc_wav_prep(_p(wav), wav.stride(0), _p(wav_len), _p(wav_off), _p(out_flat), 0, seg.ref(), samples_per_row, seg.B, L,
+                            int(normalize), _stream()), "sc_wav_prep")
+
+
+def _conv0_groupnorm_gelu(stats_wav: torch.Tensor, wav_len: Optional[torch.Tensor], wav_off: Optional[torch.Tensor], x: torch.Tensor,
+                          seg: Optional["RowSegments"], samples_per_row: int, w0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                          T0: int, R0: int, out: torch.Tensor, eps: float, nchunk: int, out_f32: bool = False):
+    """stats -> finalize -> gn_gelu of both row layouts: the GroupNorm statistics of stats_wav over t < T0 (wav_len None: the prepared
+    batch; else the caller's, masked by wav_len / wav_off), then the activation of the prepared waveform x (seg None: [B, ldw] rows)"""
+    B, C = stats_wav.shape[0], w0.shape[0]
+    partial = torch.empty(B * nchunk * 66, device=stats_wav.device, dtype=torch.float64)
+    scale = torch.empty(B, C, device=stats_wav.device, dtype=torch.float32)
+    shift = torch.empty_like(scale)
+    L = lib()
+    check(L.sc_conv0_stats(_p(stats_wav), stats_wav.stride(0), _p(wav_len), _p(wav_off), B, T0, nchunk, _p(partial), _stream()), "sc_conv0_stats")
+    check(L.sc_conv0_finalize(_p(partial), nchunk, _p(w0), _p(gamma), _p(beta), B, C, T0, float(eps), _p(scale), _p(shift), _stream()),
+          "sc_conv0_finalize")
+    check(L.sc_conv0_gn_gelu(_p(x), 0 if seg is not None else x.stride(0), seg.ref() if seg is not None else None, samples_per_row, _p(w0),
+                             _p(scale), _p(shift), _p(out), int(out_f32), B, R0, C, _stream()), "sc_conv0_gn_gelu")
+    return scale, shift, partial, nchunk
 
 
 def conv0_groupnorm_gelu_seg(wav: torch.Tensor, wav_len: torch.Tensor, wav_flat: torch.Tensor, seg: "RowSegments", samples_per_row: int,
@@ -1011,42 +1029,22 @@ def conv0_groupnorm_gelu_seg(wav: torch.Tensor, wav_len: torch.Tensor, wav_flat:
     """conv layer 0 + GroupNorm + GELU on ragged rows.  The GroupNorm statistics run over the PADDED batch length T0 (fairseq feeds the
     zero-padded batch, speech_encoder_plus.py:75) and come straight from the caller's [B, L] batch masked by wav_len; the activation is
     written for the rows of the segment layout only."""
-    B, C = wav.shape[0], w0.shape[0]
-    partial = torch.empty(B * nchunk * 66, device=wav.device, dtype=torch.float64)
-    scale = torch.empty(B, C, device=wav.device, dtype=torch.float32)
-    shift = torch.empty_like(scale)
-    L = lib()
     _wav_window(wav, None, wav_off)
-    check(L.sc_conv0_stats_len_crop(_p(wav), wav.stride(0), _p(wav_len), _p(wav_off), B, T0, nchunk, _p(partial), _stream()),
-          "sc_conv0_stats_len_crop")
-    check(L.sc_conv0_finalize(_p(partial), nchunk, _p(w0), _p(gamma), _p(beta), B, C, T0, float(eps), _p(scale), _p(shift), _stream()),
-          "sc_conv0_finalize")
-    check(L.sc_conv0_gn_gelu_seg(_p(wav_flat), seg.ref(), samples_per_row, _p(w0), _p(scale), _p(shift), _p(out), C, _stream()),
-          "sc_conv0_gn_gelu_seg")
+    _conv0_groupnorm_gelu(wav, wav_len, wav_off, wav_flat, seg, samples_per_row, w0, gamma, beta, T0, 0, out, eps, nchunk)
 
 
 def conv0_layernorm_gelu_seg(wav_flat: torch.Tensor, seg: "RowSegments", samples_per_row: int, w0: torch.Tensor, bias: Optional[torch.Tensor],
                              gamma: torch.Tensor, beta: torch.Tensor, out: torch.Tensor, eps: float = 1e-5) -> None:
-    check(lib().sc_conv0_ln_gelu_seg(_p(wav_flat), seg.ref(), samples_per_row, _p(w0), _p(bias), _p(gamma), _p(beta), float(eps), _p(out),
-                                     w0.shape[0], _stream()), "sc_conv0_ln_gelu_seg")
+    check(lib().sc_conv0_ln_gelu(_p(wav_flat), 0, seg.ref(), samples_per_row, _p(w0), _p(bias), _p(gamma), _p(beta), float(eps), _p(out), 0,
+                                 seg.B, 0, w0.shape[0], _stream()), "sc_conv0_ln_gelu")
 
 
 def conv0_groupnorm_gelu(wav_pad: torch.Tensor, w0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, T0: int,
-                         R0: int, out: torch.Tensor, eps: float = 1e-5, nchunk: int = 8):
-    """conv layer 0 + GroupNorm(C groups) over t < T0 + GELU -> out[B*R0, C] bf16 (channels-last).  Returns what the backward
-    (conv0_groupnorm_gelu_bwd) needs: (scale, shift, Gram statistics, nchunk)."""
-    B = wav_pad.shape[0]
-    C = w0.shape[0]
-    partial = torch.empty(B * nchunk * 66, device=wav_pad.device, dtype=torch.float64)
-    scale = torch.empty(B, C, device=wav_pad.device, dtype=torch.float32)
-    shift = torch.empty_like(scale)
-    L = lib()
-    check(L.sc_conv0_stats(_p(wav_pad), wav_pad.stride(0), B, T0, nchunk, _p(partial), _stream()), "sc_conv0_stats")
-    check(L.sc_conv0_finalize(_p(partial), nchunk, _p(w0), _p(gamma), _p(beta), B, C, T0, float(eps), _p(scale),
-                              _p(shift), _stream()), "sc_conv0_finalize")
-    check(L.sc_conv0_gn_gelu(_p(wav_pad), wav_pad.stride(0), _p(w0), _p(scale), _p(shift), _p(out), B, R0, C, _stream()),
-          "sc_conv0_gn_gelu")
-    return scale, shift, partial, nchunk
+                         R0: int, out: torch.Tensor, eps: float = 1e-5, nchunk: int = 8, out_f32: bool = False):
+    """conv layer 0 + GroupNorm(C groups) over t < T0 + GELU -> out[B*R0, C] bf16 (channels-last; out_f32: the fp32 debug mode's
+    unrounded fp32).  Returns what the backward (conv0_groupnorm_gelu_bwd) needs: (scale, shift, Gram statistics, nchunk)."""
+    assert out.dtype == (torch.float32 if out_f32 else torch.bfloat16)
+    return _conv0_groupnorm_gelu(wav_pad, None, None, wav_pad, None, 0, w0, gamma, beta, T0, R0, out, eps, nchunk, out_f32)
 
 
 def conv0_groupnorm_gelu_bwd(wav_pad: torch.Tensor, w0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, saved, dy: torch.Tensor,
@@ -1066,11 +1064,13 @@ def conv0_groupnorm_gelu_bwd(wav_pad: torch.Tensor, w0: torch.Tensor, gamma: tor
 
 
 def conv0_layernorm_gelu(wav_pad: torch.Tensor, w0: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.Tensor,
-                         beta: torch.Tensor, R0: int, out: torch.Tensor, eps: float = 1e-5) -> None:
-    """conv layer 0 (+bias) + LayerNorm over channels + GELU ("layer_norm" extractor mode) -> out[B*R0, 512] bf16."""
+                         beta: torch.Tensor, R0: int, out: torch.Tensor, eps: float = 1e-5, out_f32: bool = False) -> None:
+    """conv layer 0 (+bias) + LayerNorm over channels + GELU ("layer_norm" extractor mode) -> out[B*R0, 512] bf16 (out_f32: the fp32
+    debug mode's unrounded fp32)."""
+    assert out.dtype == (torch.float32 if out_f32 else torch.bfloat16)
     B, C = wav_pad.shape[0], w0.shape[0]
-    check(lib().sc_conv0_ln_gelu(_p(wav_pad), wav_pad.stride(0), _p(w0), _p(bias), _p(gamma), _p(beta), float(eps), _p(out),
-                                 B, R0, C, _stream()), "sc_conv0_ln_gelu")
+    check(lib().sc_conv0_ln_gelu(_p(wav_pad), wav_pad.stride(0), None, 0, _p(w0), _p(bias), _p(gamma), _p(beta), float(eps), _p(out),
+                                 int(out_f32), B, R0, C, _stream()), "sc_conv0_ln_gelu")
 
 
 def conv0_layernorm_gelu_bwd(wav_pad: torch.Tensor, w0: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor,

@@ -961,7 +961,7 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
     def forward(self, wav: Union[torch.Tensor, list], wav_len: Union[torch.Tensor, list] = [],
                 feat_select_idx: Union[str, list] = None, return_hidden_states: bool = False) -> Tuple:
         # :539-554.  A padded (B, width) batch - what collate_general builds and Lightning moves - goes to the kernels AS IS, with or
-        # without the training crop: the two kernels that read it (sc_wav_prep*_crop, sc_conv0_stats_len_crop) take the padded length,
+        # without the training crop: the two kernels that read it (sc_wav_prep, sc_conv0_stats) take the padded length,
         # the lengths and the crop offsets and read utterance b from wav[b, off_b : off_b + len_b] in place; the reference's un-pad /
         # crop / re-pad (:539-552, :506-518) never happens as data movement.  A list of waveforms is padded once.
         crop = self.training and self.max_audio_len >= 0

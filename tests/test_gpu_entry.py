@@ -4,7 +4,7 @@ Every shipped recipe feeds whole utterances and crops them to ``max_audio_len: 1
 mode (avssl/module/speech_encoder_plus.py:548-552 -> avssl/data/audio_transforms.py:5-23), on a batch Lightning has already moved to
 the device (avssl/model/kwClip.py:145-147; ``wav_len`` from avssl/data/collate_function.py:7-36).  Here that route is: crop offsets
 drawn on the host (the reference's stream of draws), uploaded with the step's other integers, and the two kernels that read the
-caller's batch (sc_wav_prep*_crop, sc_conv0_stats_len_crop) read utterance b from ``wav[b, off_b : off_b + len_b]`` in place - no
+caller's batch (sc_wav_prep, sc_conv0_stats) read utterance b from ``wav[b, off_b : off_b + len_b]`` in place - no
 list of slices, no re-padded copy; lengths keep a host twin through the transfer (data.transfer_batch_to_device), so the rows stay
 ragged and nothing reads the device back.
 

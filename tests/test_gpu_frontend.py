@@ -163,7 +163,7 @@ def _padded(utt, lens, width):
 def test_conv0_groupnorm_gelu_seg_against_fp64_and_uniform(dev, case, crop):
     """GroupNorm statistics over the batch's padded T0 on the zero-padded waveform (the caller's batch masked by wav_len / wav_off):
     rel-L2 < 5e-3 per utterance on its valid frames against fp64 (one bf16 store, test_frontend_conv0's bound), and bit-identical to
-    the uniform-row kernel (sc_conv0_gn_gelu) on every frame whose window lies inside the utterance's segment."""
+    the uniform-row launch (sc_conv0_gn_gelu without seg) on every frame whose window lies inside the utterance's segment."""
     ops = _ops()
     name, kinds, lens, spr = case
     L = max(lens)
@@ -208,7 +208,7 @@ def test_conv0_layernorm_gelu_seg_against_fp64_and_uniform(dev, case, with_bias)
     """closed form (sc_set_option(2, 0)) and two-pass (sc_set_option(2, 1)) on ragged rows, the waveform normalised by wav_prep_seg
     as the large model's forward does: per utterance on its valid frames rel-L2 < 5e-3 against fp64 and at most 1.05x the two-pass
     kernel's error, all values finite, the two kernels within one bf16 ulp or 1e-6 of each other (the criteria of
-    test_frontend_conv0_layer_norm_mode_closed_form_statistics), and each bit-identical to its uniform-row launch (sc_conv0_ln_gelu)."""
+    test_frontend_conv0_layer_norm_mode_closed_form_statistics), and each bit-identical to its uniform-row launch (sc_conv0_ln_gelu without seg)."""
     from speechclip_plus_amd._lib import lib
     ops = _ops()
     name, kinds, lens, spr = case
@@ -253,6 +253,116 @@ def test_conv0_layernorm_gelu_seg_against_fp64_and_uniform(dev, case, with_bias)
             e_new, e_old = rel_l2(ob[0][:nv], ref), rel_l2(ob[1][:nv], ref)
             print(f"{name} b{b} {kinds[b]} len {n}: closed form {e_new:.3e}, two-pass {e_old:.3e}")
             assert e_new < 5e-3 and e_new <= 1.05 * e_old + 1e-6, (name, b, kinds[b], e_new, e_old)
+
+
+# ------------------------------------------------------------------------------------------------ 4: the fp32-output forms
+U64 = 2.0 ** -53
+GELU_SLOPE = 1.13              # max |gelu'| = 1.1290 (at x = sqrt 2): |gelu(n + dn) - gelu(n)| <= 1.13 |dn|, no higher-order term
+SECOND_ORDER = 1.001           # products of two error terms: every relative term here is < 1e-4
+
+
+def _gelu_erf_form_error(n):
+    """|gelu_erf(n) - gelu(n)| for an exact fp32 argument n (csrc/sc_common.h; docs/parity.md): gelu = (h + |h|) - |h| erfc(|z|), h = n / 2;
+    A&S 7.1.28 bounds erfc by 3e-7 absolute, its fp32 evaluation (6 Horner roundings x 16, four squarings x (8 + 4 + 2 + 1), rcp) by
+    112 u relative, the rounding of z = |n| / sqrt 2 moves erfc by < u; the closing fma rounds once"""
+    return 0.5 * n.abs() * (3e-7 + 112 * U * torch.erfc(n.abs() / math.sqrt(2.0)) + U) + U * F.gelu(n).abs()
+
+
+def _f32_bound_groupnorm(x64, T0, w0, gam, bet):
+    """(reference (B, T0, C), element bound) of conv0_groupnorm_gelu(out_f32=True); docs/parity.md, "conv layer 0, fp32 outputs"."""
+    X = _windows(x64, T0)                                                  # [B, T, 10]
+    w, g, be = w0.double(), gam.double()[None, :, None], bet.double()[None, :, None]
+    y = torch.einsum("btj,cj->bct", X, w)
+    absWX = torch.einsum("btj,cj->bct", X.abs(), w.abs())
+    mu = y.mean(-1, keepdim=True)
+    var = y.var(-1, unbiased=False, keepdim=True)
+    rs = 1.0 / torch.sqrt(var + EPS)
+    sc, sh = g * rs, be - mu * g * rs
+    n = y * sc + sh
+    # fp64 Gram statistics: at most T0 + 100 roundings on the way to scale / shift, charged on the sums of absolute values; the same
+    # again for the fp64 reference's own statistics
+    e64 = 2 * (T0 + 100) * U64
+    d_mu = e64 * absWX.mean(-1, keepdim=True)
+    d_var = e64 * ((absWX * absWX).mean(-1, keepdim=True) + 2 * mu.abs() * absWX.mean(-1, keepdim=True))
+    d_rs = 0.5 * d_var / (var + EPS) + 4 * U64                             # relative
+    d_sc = sc.abs() * (d_rs + U)                                           # rounded to fp32 once
+    d_sh = sc.abs() * d_mu + (mu * sc).abs() * d_rs + U * sh.abs()
+    d_y = 10 * U * absWX                                                   # the 10-FMA chain
+    d_n = sc.abs() * d_y + y.abs() * d_sc + d_sh + U * n.abs()             # n = fma(y, sc, sh)
+    bound = SECOND_ORDER * (GELU_SLOPE * d_n + _gelu_erf_form_error(n))
+    return F.gelu(n).transpose(1, 2), bound.transpose(1, 2)
+
+
+def _f32_bound_layernorm(x64, T0, w0, bias, gam, bet):
+    """(reference (B, T0, C), element bound) of conv0_layernorm_gelu(out_f32=True): the two-pass kernel, statistics in fp32."""
+    X = _windows(x64, T0)
+    w, ga, be = w0.double(), gam.double(), bet.double()
+    b0 = torch.zeros(C, dtype=torch.float64) if bias is None else bias.double()
+    y = torch.einsum("btj,cj->btc", X, w) + b0
+    d_y = 10 * U * (torch.einsum("btj,cj->btc", X.abs(), w.abs()) + b0.abs())          # the chain starts at the bias: 10 roundings
+    m = y.mean(-1, keepdim=True)
+    a = y - m
+    var = (a * a).mean(-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + EPS)
+    xh = a * rstd
+    n = ga * xh + be
+    d_m = d_y.mean(-1, keepdim=True) + 14 * U * y.abs().mean(-1, keepdim=True)            # 8 serial adds + a 6-level wave tree
+    d_a = d_y + d_m + U * a.abs()
+    d_var = 2 * (a.abs() * d_a).mean(-1, keepdim=True) + 16 * U * var                       # squares, 8 adds, the tree, + eps
+    d_rs = 0.5 * d_var / (var + EPS) + 2 * U                                                # relative; rsqrtf: 1 ulp
+    d_xh = rstd * d_a + xh.abs() * (d_rs + U)
+    d_n = ga.abs() * (d_xh + U * xh.abs()) + U * n.abs()
+    bound = SECOND_ORDER * (GELU_SLOPE * d_n + _gelu_erf_form_error(n))
+    return F.gelu(n), bound
+
+
+@pytest.mark.parametrize("form", ["groupnorm", "layernorm", "layernorm_nobias"])
+def test_conv0_fp32_outputs_against_fp64(dev, form):
+    """out_f32=True of the two uniform conv-0 wrappers (the fp32 debug mode's kernels: same taps and affine, the 3e-7 erf-GELU form,
+    unrounded stores) against fp64, every element within its derived bound (docs/parity.md, "conv layer 0, fp32 outputs").  B = 2 (noise,
+    DC offset), T0 = R0 = 131: a full 128-row workgroup plus a 3-row one whose last wave iteration (4 rows, 2 in the LayerNorm kernel)
+    is partial.  The flag does not leak: the bf16 call before and after the fp32 one give the same bits, out_f32=False or left out."""
+    ops = _ops()
+    T0 = R0 = 131
+    kinds = ["noise", "dc"]
+    B = len(kinds)
+    g = torch.Generator().manual_seed(41)
+    L = 5 * (T0 - 1) + 10
+    wav = torch.zeros(B, L + 6)
+    for b, k in enumerate(kinds):
+        wav[b, :L] = _signal(k, L, g)
+    w0, bias, gam, bet = _weights(23)
+    if form == "layernorm_nobias":
+        bias = None
+    wd = wav.to(dev)
+    if form == "groupnorm":
+        td = [t.to(dev) for t in (w0, gam, bet)]
+        run = lambda out, **kw: ops.conv0_groupnorm_gelu(wd, *td, T0, R0, out, **kw)
+        ref, bound = _f32_bound_groupnorm(wav.double(), T0, w0, gam, bet)
+        assert rel_l2(ref, _ref_groupnorm(wav.double(), T0, w0, gam, bet)) < 1e-9     # the bound's restatement is the file's reference
+    else:
+        td = [t.to(dev) if t is not None else None for t in (w0, bias, gam, bet)]
+        run = lambda out, **kw: ops.conv0_layernorm_gelu(wd, *td, R0, out, **kw)
+        ref, bound = _f32_bound_layernorm(wav.double(), T0, w0, bias, gam, bet)
+        assert rel_l2(ref, _ref_layernorm(wav.double()[:, :L], w0, bias, gam, bet)) < 1e-12
+    bf = [torch.full((B * R0, C), float("nan"), device=dev, dtype=torch.bfloat16) for _ in range(2)]
+    out = torch.full((B * R0, C), float("nan"), device=dev, dtype=torch.float32)
+    saved0 = run(bf[0])
+    saved = run(out, out_f32=True)
+    saved1 = run(bf[1], out_f32=False)
+    assert torch.equal(bf[0].view(torch.int16), bf[1].view(torch.int16)) and bool(torch.isfinite(bf[0].float()).all())
+    if form == "groupnorm":
+        live = lambda s: (s[0], s[1], s[2].view(B, s[3], 66)[..., :65])          # scale, shift, the 65 written sums per chunk (66th: pad)
+        for a_, b_, c_ in zip(live(saved0), live(saved), live(saved1)):
+            assert torch.equal(a_, b_) and torch.equal(a_, c_)
+    got = out.view(B, R0, C).cpu()
+    assert bool(torch.isfinite(got).all())
+    err = (got.double() - ref).abs()
+    ratio = float((err / bound).max())
+    print(f"{form}: max err / bound {ratio:.3e}, rel-L2 {rel_l2(got, ref):.3e}, largest bound {float(bound.max()):.3e}")
+    assert bool((err <= bound).all()), (form, ratio)
+    # one bf16 rounding of the fp32 result away from the bf16 path (whose GELU is the five-term fit, |error| <= 3.1e-6)
+    assert rel_l2(bf[0].view(B, R0, C).float().cpu(), got) < 5e-3
 
 
 # ------------------------------------------------------------------------------------------------ backward

@@ -34,7 +34,7 @@ def setup():
 @pytest.fixture(scope="module")
 def setup_large():
     """HuBERT-large at two layers (layer_norm extractor, conv bias, utterance-normalised waveform): the only end-to-end consumer of the
-    ragged layer_norm-mode conv 0 (sc_conv0_ln_gelu_seg) and of sc_wav_prep_seg with normalisation"""
+    ragged layer_norm-mode conv 0 (sc_conv0_ln_gelu with seg) and of sc_wav_prep with seg and normalisation"""
     import dataclasses
     from speechclip_plus_amd import KWClip_GeneralTransformer, large_parallel_config, random_hubert_state_dict
     from speechclip_plus_amd.speech_encoder import ARCHS

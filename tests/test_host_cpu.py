@@ -23,7 +23,7 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/speechclip_hip.h but not exported"
     assert set(_lib.SIGNATURES) | {"sc_last_error", "sc_hash32", "sc_infonce_workspace_floats", "sc_workspace_bytes", "sc_sizeof"} == declared
-    assert lib.sc_abi_version() == 5
+    assert lib.sc_abi_version() == 6
     # the ctypes mirrors of the argument structs have the C structs' sizes (checked again at every load: _lib.lib())
     for what, cls in enumerate((_lib.GemmArgs, _lib.HubertLayerArgs, _lib.RtGemmArgs, _lib.RtLnArgs, _lib.RtLnBwdArgs)):
         assert lib.sc_sizeof(what) == ctypes.sizeof(cls), cls.__name__
@@ -33,6 +33,58 @@ def test_library_exports_every_declared_symbol():
     for x in (1, 12345, 0xdeadbeef, 0xffffffff):
         t = ref(x)
         assert lib.sc_hash32(x) == (t ^ (t >> 16))
+
+
+def test_frontend_refusals_are_host_side():
+    """The merged front-end entries (sc_wav_prep, sc_conv0_stats, sc_conv0_gn_gelu, sc_conv0_ln_gelu: row layout, crop and fp32 stores
+    as arguments) check their arguments on the host before any launch: with host pointers and no GPU, every combination the entries
+    refuse returns non-zero with sc_last_error() naming the merged symbol and the reason, and the output buffer keeps its sentinel.
+    (Only refused calls are made: the pointers are host memory no kernel may see.)"""
+    from speechclip_plus_amd import _lib
+    lib = _lib.lib()
+    raw = ctypes.create_string_buffer(b"\xa5" * 4096, 4096)
+    p = (ctypes.addressof(raw) + 15) // 16 * 16              # a 16-byte aligned, non-null host address
+
+    def seg(B=2, row0=p, max_pitch=8):
+        s = _lib.Segments()
+        s.row0, s.chunk, s.B, s.rows, s.max_pitch = row0, p, B, 16, max_pitch
+        return ctypes.byref(s)
+
+    B, L, R0, T0, spr = 2, 100, 131, 131, 320
+    ldw = 5 * (R0 - 1) + 10
+
+    def wav_prep(ldw_out=L, sg=None, spr=0, B=B, wav_len=p, wav_off=None):
+        return lib.sc_wav_prep(p, L, wav_len, wav_off, p, ldw_out, sg, spr, B, L, 0, None)
+
+    def stats(ldw=ldw, wav_len=None, wav_off=None):
+        return lib.sc_conv0_stats(p, ldw, wav_len, wav_off, B, T0, 8, p, None)
+
+    def gn(ldw=ldw, sg=None, spr=0, out_f32=0, B=B, C=512):
+        return lib.sc_conv0_gn_gelu(p, ldw, sg, spr, p, p, p, p, out_f32, B, R0, C, None)
+
+    def ln(ldw=ldw, sg=None, spr=0, out_f32=0, B=B, C=512):
+        return lib.sc_conv0_ln_gelu(p, ldw, sg, spr, p, None, p, p, 1e-5, p, out_f32, B, R0, C, None)
+
+    cases = [("seg with row0 == NULL", "null pointer", [(wav_prep, "sc_wav_prep"), (gn, "sc_conv0_gn_gelu"), (ln, "sc_conv0_ln_gelu")],
+              lambda: dict(sg=seg(row0=None), spr=spr)),
+             ("samples_per_row = 7", "samples_per_row=7", [(wav_prep, "sc_wav_prep"), (gn, "sc_conv0_gn_gelu"), (ln, "sc_conv0_ln_gelu")],
+              lambda: dict(sg=seg(), spr=7)),
+             ("B != seg->B", "B=2 against seg->B=3", [(wav_prep, "sc_wav_prep"), (gn, "sc_conv0_gn_gelu"), (ln, "sc_conv0_ln_gelu")],
+              lambda: dict(sg=seg(B=3), spr=spr)),
+             ("out_f32 with seg", "out_f32", [(gn, "sc_conv0_gn_gelu"), (ln, "sc_conv0_ln_gelu")], lambda: dict(sg=seg(), spr=spr, out_f32=1)),
+             ("wav_off without wav_len", "wav_off needs wav_len", [(stats, "sc_conv0_stats")], lambda: dict(wav_off=p)),
+             ("wav_off without wav_len", "null pointer", [(wav_prep, "sc_wav_prep")], lambda: dict(wav_len=None, wav_off=p)),
+             ("uniform ldw < 5 (R0 - 1) + 10", "too small", [(gn, "sc_conv0_gn_gelu"), (ln, "sc_conv0_ln_gelu")], lambda: dict(ldw=ldw - 1)),
+             ("prepared batch, ldw < 5 (T0 - 1) + 10", "bad sizes", [(stats, "sc_conv0_stats")], lambda: dict(ldw=ldw - 1)),
+             ("uniform ldw_out < L", "ldw_out < L", [(wav_prep, "sc_wav_prep")], lambda: dict(ldw_out=L - 1)),
+             ("C = 256, GroupNorm form", "C=256", [(gn, "sc_conv0_gn_gelu")], lambda: dict(C=256)),
+             ("C = 1024, LayerNorm form", "got 1024", [(ln, "sc_conv0_ln_gelu")], lambda: dict(C=1024))]
+    for what, reason, entries, kwargs in cases:
+        for fn, name in entries:
+            rc = fn(**kwargs())
+            err = lib.sc_last_error().decode()
+            assert rc != 0 and err.startswith(name + ":") and reason in err and "launch" not in err, (what, name, rc, err)
+    assert raw.raw == b"\xa5" * 4096
 
 
 def test_ops_fail_loudly_on_cpu_tensors():

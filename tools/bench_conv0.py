@@ -34,7 +34,7 @@ for r in range(6):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(3):
-        check(lib().sc_conv0_gn_gelu(_p(wav), wav.stride(0), _p(w0), _p(scale), _p(shift), _p(out), B, R0, C, _stream()), "sc_conv0_gn_gelu")
+        check(lib().sc_conv0_gn_gelu(_p(wav), wav.stride(0), None, 0, _p(w0), _p(scale), _p(shift), _p(out), 0, B, R0, C, _stream()), "sc_conv0_gn_gelu")
     e1.record()
     torch.cuda.synchronize()
     if r:
