@@ -424,6 +424,11 @@ int sc_rows_zero_pad_bf16(sc_bf16* buf, int32_t lead, int32_t B, int32_t P, int3
  *     a positive quantity (the reference asserts that on every call, cif.py:121) ; [6] += utterances whose zero quantity could not
  *     be rescaled ; [4], [5] scratch of the per-call check (left at 0) ; [2], [7] the caller's.  fp64 sums.
  *   sc_cif_prepare_bwd: pa / pb of sc_cif_bwd + d quantity (gq, may be NULL) -> d alpha_raw [B,S] (suffix sum of d csum, scaling).
+ *     PRECONDITION: alpha_raw lies in [0, 1], both ends included (the sigmoid output the product feeds).  No derivative of
+ *     clip(alpha_raw, 0, 1) is applied: inside the interval it is 1, and at exactly 0 and 1 torch.clamp passes the gradient too.
+ *     For a value outside [0, 1] the forward clips and this gradient is NOT that of the clipped function.  An utterance with
+ *     quantity <= 0 (all clipped weights zero; ratio forced to 0 by sc_cif_prepare) gets no gradient through the scaling:
+ *     d alpha_raw = gq on its unpadded frames.
  *   sc_cif_tail (inference): tail weight of slot feat_len >= tail_thr -> that row *= thr / weight, feat_len += 1 (clip max_feat),
  *     rows >= feat_len zeroed in out [B,T+1,C]; factor / extend [B] returned for the caller's backward / diagnostics.    S <= 2048. */
 int sc_cif_prepare(const float* alpha_raw, int64_t lda, const uint8_t* pad, int64_t ldp, const int64_t* target, int32_t apply_scaling,

@@ -465,8 +465,10 @@ __global__ __launch_bounds__(256) void cif_prepare_bwd_kernel(const float* __res
         const int s = s0 + i;
         if (s < S) dot += (double)ga[i] * (double)a_clip[(int64_t)b * S + s];
     }
-    const float r = ratio[b];
-    const float corr = scale ? (float)block_sum_d(dot, red) * r / quantity[b] : 0.f;
+    const float r = ratio[b], q = quantity[b];
+    // an utterance whose clipped weights are all zero was not rescaled (ratio = 0, cif_prepare_kernel): no gradient through the
+    // scaling (0 / 0 otherwise), d quantity alone
+    const float corr = (scale && q > 0.f) ? (float)block_sum_d(dot, red) * r / q : 0.f;
     const float g_q = gq ? gq[b] : 0.f;
 #pragma unroll
     for (int i = 0; i < PREP_PER; ++i) {
