@@ -29,7 +29,8 @@ extern "C" {
 typedef uint16_t sc_bf16;
 
 const char* sc_last_error(void);
-int sc_abi_version(void);     /* 6: one front-end entry point per kernel (sc_wav_prep, sc_conv0_stats, sc_conv0_gn_gelu, sc_conv0_ln_gelu take
+int sc_abi_version(void);     /* 6 (round 9, additive: sc_gemm_args.a_rep / sc_hubert_layer_args.w_split took the reserved3 / reserved2 slots - split
+                                 weights for evaluation; sizes unchanged); 6: one front-end entry point per kernel (sc_wav_prep, sc_conv0_stats, sc_conv0_gn_gelu, sc_conv0_ln_gelu take
                                  seg / wav_off / out_f32; their _seg, _crop, _len and _f32 symbols are gone); 5: sc_adam_f32 takes its betas as doubles; 4 since round 4 (sc_segments; sc_gemm_args / sc_hubert_layer_args grew the segment fields) */
 int sc_is_diag_build(void);   /* 1: libspeechclip_hip_diag.so - the same sources built with SC_DIAG_BUILD: also holds the diagnostic kernels
                                  (sc_gemm_args.tile 32 = timing only, RESULTS WRONG; 34 = stamped) and the LayerNorm-folded GEMMs; the
@@ -144,7 +145,14 @@ typedef struct {
      *               bits of the differentiated run without keeping its pre-activation
      * All reproduce the two-launch sequence bit for bit (the activation reads the ROUNDED values the first kernel would have stored). */
     int32_t aux_mode;
-    int32_t reserved3;
+    /* ---- split weights (evaluation mode; docs/rounds/r09_split_weights.md): a_rep = 0 / 1: W is [N, K].  a_rep = 2: W is the [N, 2K]
+     * interleave by 64-column K-tile  [hi tile 0 | lo tile 0 | hi tile 1 | lo tile 1 | ...]  of  W_hi = bf16(W), W_lo = bf16(W - W_hi)
+     * (ldw >= 2K; K, tap_c, lda still describe A), and the K loop reads every A tile twice: physical K-tile kt multiplies the A tile at
+     * koff(kt / 2) with the W tile at 2 koff(kt / 2) + 64 (kt & 1), koff = the visiting order tap_c selects.  One launch, one fp32
+     * accumulator over both halves, so every epilogue (bias, activations, residual, transposed store, segment layout, out_f32,
+     * aux_mode) is the usual one; every tile family, same order, same bits.  Not with tn, LayerNorm folding (ln_*, res_stats,
+     * stats_out), drop_p > 0 or the diagnostic tile ids.  Takes the slot of the former reserved3. */
+    int32_t a_rep;
     /* ---- ragged rows (round 4): seg_chunk != NULL replaces the uniform `R` of the transposed store - row m belongs to the
      * utterance of chunk m / 8 = (first row r0, pitch Rb, ...) (sc_segments.chunk) and goes to
      *       Ct[(N - n_split) * r0 + (n - n_split) * Rb + (m - r0)]          (V^T [H, dh, Rb] per utterance, utterances back to back) */
@@ -731,7 +739,9 @@ typedef struct {
      * segment layout (R, T are then ignored; vt = per utterance [H, 64, pitch]); attn_work / n_attn_work as in sc_attn_fwd_seg_bf16 */
     const sc_segments* seg;
     const int32_t* attn_work;
-    int32_t n_attn_work, reserved2;
+    int32_t n_attn_work;
+    int32_t w_split;                          /* 1: qkv_w / o_w / fc1_w / fc2_w are the [N, 2K] hi / lo interleaves of sc_gemm_args.a_rep = 2 and the four
+                                                 GEMMs run with it (evaluation: p_res must be 0); not with fused_ln.  The former reserved2. */
 } sc_hubert_layer_args;
 int sc_hubert_layer_fwd(const sc_hubert_layer_args* args, void* stream);
 #define SC_WS_INFONCE 0       /* a = Bg */

@@ -33,7 +33,7 @@ class GemmArgs(ctypes.Structure):
         ("tap_c", c_int), ("ln_ns", c_int),
         ("ln_stats", c_void_p), ("ln_colsum", c_void_p), ("res_stats", c_void_p), ("res_gamma", c_void_p), ("res_beta", c_void_p),
         ("stats_out", c_void_p), ("res_ns", c_int), ("ln_eps", ctypes.c_float),
-        ("tn", c_int), ("k_total", c_int), ("aux_mode", c_int), ("reserved3", c_int),
+        ("tn", c_int), ("k_total", c_int), ("aux_mode", c_int), ("a_rep", c_int),
         ("seg_chunk", c_void_p),
     ]
 
@@ -98,7 +98,7 @@ class HubertLayerArgs(ctypes.Structure):
         ("qk", c_void_p), ("vt", c_void_p), ("ctx", c_void_p), ("pre", c_void_p), ("x1", c_void_p), ("ffn", c_void_p),
         ("fused_ln", c_int), ("x_ns", c_int), ("x_stats", c_void_p), ("x_ln_g", c_void_p), ("x_ln_b", c_void_p),
         ("qkv_colsum", c_void_p), ("fc1_colsum", c_void_p), ("stats1", c_void_p), ("out_stats", c_void_p),
-        ("seg", ctypes.POINTER(Segments)), ("attn_work", c_void_p), ("n_attn_work", c_int), ("reserved2", c_int),
+        ("seg", ctypes.POINTER(Segments)), ("attn_work", c_void_p), ("n_attn_work", c_int), ("w_split", c_int),
     ]
 
 

@@ -8,6 +8,10 @@ Normalisations applied on load:
     (8112 x 2 / 19787 x 2 int64).  When that file is not reachable (it does not travel with this package) a synthetic table of
     the same size replaces it, with a warning;
   * ``audio_encoder.name`` aliases (``hubert_base`` -> the same architecture as ``hubert``).
+
+Keys of this package (not in the reference's recipes):
+  * ``audio_encoder.eval_weights``: ``bf16`` (default) or ``split`` - the eval-mode weights of the frozen HuBERT GEMMs
+    (speech_encoder.FairseqSpeechEncoder_Hubert).
 """
 import logging
 import os
@@ -80,6 +84,9 @@ def load_config(src: Union[str, dict], reference_root: str = ".", allow_syntheti
             logger.warning("reduced-vocabulary table %s not found: using a synthetic table of %d sub-words", vocab,
                            REDUCED_VOCAB_SIZE[stat])
             clip["reduce_subword_embbedding"] = synthetic_reduced_vocab(REDUCED_VOCAB_SIZE[stat])
+    ew = cfg.audio_encoder.get("eval_weights", "bf16")
+    if ew not in ("bf16", "split"):
+        raise ValueError(f"audio_encoder.eval_weights = {ew!r}: 'bf16' or 'split'")
     ms = cfg.model_settings
     ms.setdefault("cascaded_objective_weight", 0.0)
     ms.setdefault("parallel_objective_weight", 0.0)

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const sc_gemm_args p) {
     // aligned with the bands only when nM was a multiple of 64 (B x 512 rows), and with the ragged layout's arbitrary row counts a
     // band straddled two XCDs most of the time (PMC: 487 MB per launch at M = 64 x 504 against 434 MB at M = 64 x 512).  An XCD's list
     // may be one row of tiles shorter than its neighbour's; a virtual block past its XCD's list has no tile (returns false).
-    const bool xcd_rows = (gridDim.x & 7) == 0 && nM >= 8 && !p.reserved3;      // reserved3: A/B switch (sc_set_option(3, 1): round-3 map)
+    const bool xcd_rows = (gridDim.x & 7) == 0 && nM >= 8 && !(p.reserved & 2);      // reserved bit 1: A/B switch (sc_set_option(3, 1): round-3 map)
     auto tile_of = [&](int vb, int& m0, int& n0) -> bool {
         constexpr int GM = 8;
         if (xcd_rows) {
@@ -275,7 +275,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const sc_gemm_args p) {
         }
     };
     // TN form with ragged slices: slice z1 covers reduction rows [z1 K, min((z1 + 1) K, k_total))
-    const int nk = (TNM && p.k_total > 0 ? min(p.K, p.k_total - (int)(blockIdx.z / p.nb2) * p.K) : p.K) / BK;
+    // a_rep = 2 (split weights, sc_gemm_args.a_rep; never with TN): W is the [N, 2K] interleave [hi tile 0 | lo tile 0 | hi tile 1 | ...]
+    // and the K loop runs over 2 K / 64 PHYSICAL K-tiles - physical tile kt multiplies the A tile of logical tile kt / 2 (staged
+    // again: same DMA, same slot rotation, same counted waits) with the W tile 2 koff(kt / 2) + 64 (kt & 1).  rsh = 0: kt is the logical tile.
+    const int rsh = (!TNM && p.a_rep == 2) ? 1 : 0;
+    const int nk = ((TNM && p.k_total > 0 ? min(p.K, p.k_total - (int)(blockIdx.z / p.nb2) * p.K) : p.K) / BK) << rsh;
     // K-tile kt -> first k of the tile.  Conv-shaped A (tap_c = C_in, K = 3 C_in, lda = 2 C_in): per 64-channel block visit tap 0,
     // tap 2, tap 1 - tap 2 of row r is tap 0 of row r + 1, so that tile is fetched again while the L2 still holds it.
     const int tap_c = p.tap_c;
@@ -284,6 +288,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const sc_gemm_args p) {
         const int c = kt / 3, j = kt - 3 * c;
         return (j == 0 ? 0 : (3 - j) * tap_c) + c * BK;
     };
+    auto koffA = [&](int kt) -> int { return koff(kt >> rsh); };                                     // physical K-tile -> offset into A's rows
+    auto koffW = [&](int kt) -> int { return (koff(kt >> rsh) << rsh) + ((kt & rsh) << 6); };        //                 -> offset into W's rows
     // train-mode dropout is a compile-time variant: in the runtime-switched form its mask / scale registers and the branch in
     // the store loop cost the plain instantiations 4 % (rocprofv3, r01 v6 -> v7)
     const uint32_t drop_thr = DROP ? (uint32_t)(p.drop_p * 65536.f + 0.5f) : 0u;
@@ -343,7 +349,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const sc_gemm_args p) {
 
         // ---- prologue: A(0), B(0) are in flight (issued before the previous epilogue); B(1) goes to the other buffer ----
         if (nk > 1) {
-            dma_B(base ^ 1, koff(1));
+            dma_B(base ^ 1, koffW(1));
             SC_WAIT_NBI();
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -378,7 +384,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const sc_gemm_args p) {
                 b1[ni][1] = ld_frag(bs, 2 + ni, 1);
             }
             if (LN != 0 && kt == 0) dma_ln(m0, n0);      // older than every later wait of this K loop: in LDS long before the epilogue
-            if (kt + 1 < nk) dma_A(par ^ 1, koff(kt + 1));
+            if (kt + 1 < nk) dma_A(par ^ 1, koffA(kt + 1));
             SC_BAR_L();
             SC_MFMA_QUAD(0, 0, b0);
             SC_MFMA_QUAD(0, 1, b1);
@@ -390,7 +396,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const sc_gemm_args p) {
                 af[mi][1] = ld_frag(as, 4 + mi, 1);
             }
             if (kt + 2 < nk) {
-                dma_B(par, koff(kt + 2));
+                dma_B(par, koffW(kt + 2));
                 SC_WAIT_NBI();
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -421,7 +427,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const sc_gemm_args p) {
                 b1[ni][1] = ld_frag(bs, 2 + ni, 1);
             }
             if (LN != 0 && kt == 0) dma_ln(m0, n0);      // older than every later wait of this K loop: in LDS long before the epilogue
-            if (kt + 1 < nk) dma_A(par ^ 1, koff(kt + 1));
+            if (kt + 1 < nk) dma_A(par ^ 1, koffA(kt + 1));
             SC_BAR();
             SC_MFMA_QUAD(0, 1, b1);
             SC_BAR();
@@ -436,7 +442,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const sc_gemm_args p) {
             SC_BAR();
             // ---------------- P3
             if (kt + 2 < nk) {
-                dma_B(par, koff(kt + 2));
+                dma_B(par, koffW(kt + 2));
                 SC_WAIT_NBI();
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -584,7 +590,7 @@ int sc_gemm256_launch(const sc_gemm_args& a_in, hipStream_t s) {
     // register-direct epilogue it must stay off: half-line non-temporal writes cost 25 % (75.7 vs 55.9 us on the out_proj shape).
     a.reserved = (a_in.reserved == 1 || (a_in.reserved == 0 && a_in.residual != nullptr)) ? 1 : 0;
     if (sc_option(1)) a.reserved = 0;      // A/B switch (tools/): plain stores everywhere
-    a.reserved3 = sc_option(3);            // A/B switch (tools/): 1 = the round-3 block -> tile map (band-major list cut into 8 runs)
+    if (sc_option(3)) a.reserved |= 2;     // A/B switch (tools/): bit 1 = the round-3 block -> tile map (band-major list cut into 8 runs)
     if (a.tn) return launch256_<5, 256, 0, 0>(a, s);     // TN operands (weight gradients): checked by sc_gemm_bf16
 #ifdef SC_DIAG_BUILD
     if (a.tile == 32) return launch256<3, 256>(a, s);   // diagnostics only (tools/epi_probe.py, tools/epi_stamps.py)

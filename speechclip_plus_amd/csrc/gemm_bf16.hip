@@ -95,13 +95,13 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const sc_gemm_args p) {
     char* const As = smem;
     char* const Bs = smem + NS * Cfg::A_BYTES;
 
-    auto stage = [&](int buf, int k0) {
+    auto stage_ab = [&](int buf, int ka, int kw) {
 #pragma unroll
         for (int i = 0; i < A_INST; ++i)
-            glds16(a_src[i] + k0, As + buf * Cfg::A_BYTES + (i * 4 + wave) * 1024);
+            glds16(a_src[i] + ka, As + buf * Cfg::A_BYTES + (i * 4 + wave) * 1024);
 #pragma unroll
         for (int i = 0; i < B_INST; ++i)
-            glds16(b_src[i] + k0, Bs + buf * Cfg::B_BYTES + (i * 4 + wave) * 1024);
+            glds16(b_src[i] + kw, Bs + buf * Cfg::B_BYTES + (i * 4 + wave) * 1024);
     };
 
     // ---- fragment read offsets (bytes inside a tile) ----------------------------------------------------
@@ -119,7 +119,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const sc_gemm_args p) {
         for (int kk = 0; kk < 2; ++kk) b_off[ni][kk] = row * ROWB + (((kk * 4 + (lane >> 4)) ^ ((row >> 1) & 7)) << 4);
     }
 
-    const int nk = p.K / BK;
+    // a_rep = 2 (split weights, see gemm256_bf16.hip): 2 K / 64 physical K-tiles; physical tile kt = A tile of logical tile kt / 2
+    // (staged again) x W tile 2 koff(kt / 2) + 64 (kt & 1) of the [N, 2K] hi / lo interleave.  rsh = 0: kt is the logical tile.
+    const int rsh = p.a_rep == 2 ? 1 : 0;
+    const int nk = (p.K / BK) << rsh;
     // K-tile order of conv-shaped problems (sc_gemm_args.tap_c, see gemm256_bf16.hip): the same order in every kernel, so the
     // result does not depend on which tile family the dispatcher picks for a given row count
     const int tap_c = p.tap_c;
@@ -128,13 +131,17 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const sc_gemm_args p) {
         const int c = kt / 3, j = kt - 3 * c;
         return (j == 0 ? 0 : (3 - j) * tap_c) + c * BK;
     };
+    auto stage = [&](int buf, int kt) {          // physical K-tile kt -> ring slot buf
+        const int ka = koff(kt >> rsh);
+        stage_ab(buf, ka, (ka << rsh) + ((kt & rsh) << 6));
+    };
     // the first NS - 1 K-tiles go into flight here, ahead of the optional statistics prologue
     if constexpr (NS == 2) {
-        stage(0, 0);
+        stage_ab(0, 0, 0);
     } else {
 #pragma unroll
         for (int j = 0; j < NS - 1; ++j)
-            if (j < nk) stage(j, koff(j));
+            if (j < nk) stage(j, j);
     }
 
     // ---- LayerNorm in the PROLOGUE (round 6; the text tower's LN -> QKV and LN -> fc1 pairs: K = the model width, so a tile holds whole
@@ -216,7 +223,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const sc_gemm_args p) {
         __syncthreads();   // hipcc drains the DMA (vmcnt(0)) in front of the barrier
         for (int kt = 0; kt < nk; ++kt) {
             const int buf = kt & 1;
-            if (kt + 1 < nk) stage(buf ^ 1, koff(kt + 1));
+            if (kt + 1 < nk) stage(buf ^ 1, kt + 1);
             mma_tile(buf);
             __syncthreads();
         }
@@ -231,7 +238,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const sc_gemm_args p) {
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            if (kt + NS - 1 < nk) stage((kt + NS - 1) % NS, koff(kt + NS - 1));
+            if (kt + NS - 1 < nk) stage((kt + NS - 1) % NS, kt + NS - 1);
             mma_tile(kt % NS);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -384,6 +391,17 @@ extern "C" int32_t sc_gemm_stats_strips(const sc_gemm_args* a) {
 extern "C" int sc_gemm_bf16(const sc_gemm_args* args, void* stream) {
     SC_CHECK(args != nullptr, "sc_gemm_bf16: null args");
     sc_gemm_args a = *args;
+    // split weights (a_rep = 2): checked ahead of the operands, so the argument rules can be exercised without a device
+    SC_CHECK(a.a_rep >= 0 && a.a_rep <= 2, "sc_gemm_bf16: a_rep=%d (0 / 1: W is [N, K]; 2: W is the [N, 2K] hi / lo interleave)", a.a_rep);
+    if (a.a_rep == 2) {
+        SC_CHECK(!a.tn, "sc_gemm_bf16: a_rep = 2 (split weights) is not built into the TN form");
+        SC_CHECK(!a.ln_stats && !a.ln_colsum && !a.stats_out && !a.res_stats,
+                 "sc_gemm_bf16: a_rep = 2 (split weights) does not combine with LayerNorm folding (ln_stats / ln_colsum / stats_out / res_stats)");
+        SC_CHECK(!(a.drop_p > 0.f), "sc_gemm_bf16: a_rep = 2 (split weights) is an evaluation mode: no dropout (drop_p=%f)", (double)a.drop_p);
+        SC_CHECK(a.ldw >= 2 * (int64_t)a.K, "sc_gemm_bf16: a_rep = 2 (split weights) reads 2K = %d columns of every W row: ldw=%lld is too small",
+                 2 * a.K, (long long)a.ldw);
+        SC_CHECK(a.tile != 32 && a.tile != 34, "sc_gemm_bf16: a_rep = 2 (split weights) is not built into the diagnostic tiles (tile=%d)", a.tile);
+    }
     SC_CHECK(a.A && a.W && a.C, "sc_gemm_bf16: null operand");
     SC_CHECK(a.M > 0 && a.N > 0 && a.K > 0, "sc_gemm_bf16: bad shape M=%d N=%d K=%d", a.M, a.N, a.K);
     SC_CHECK(a.K % BK == 0, "sc_gemm_bf16: K=%d must be a multiple of %d", a.K, BK);

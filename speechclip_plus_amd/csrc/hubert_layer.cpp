@@ -14,7 +14,7 @@
 
 static int gemm(const sc_bf16* A, int64_t lda, const sc_bf16* W, int64_t ldw, void* C, int64_t ldc, int M, int N, int K, const float* bias,
                 const sc_bf16* residual, int64_t ldr, int act, float drop_p, uint32_t drop_seed, sc_bf16* Ct, int n_split, int R, int dh,
-                void* stream, const int32_t* seg_chunk = nullptr) {
+                void* stream, const int32_t* seg_chunk = nullptr, int a_rep = 0) {
     sc_gemm_args a;
     memset(&a, 0, sizeof(a));
     a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.C = C; a.ldc = ldc;
@@ -24,6 +24,7 @@ static int gemm(const sc_bf16* A, int64_t lda, const sc_bf16* W, int64_t ldw, vo
     a.nb1 = a.nb2 = 1;
     a.drop_p = drop_p; a.drop_seed = drop_seed;
     a.seg_chunk = seg_chunk;
+    a.a_rep = a_rep;
     return sc_gemm_bf16(&a, stream);
 }
 
@@ -41,11 +42,17 @@ extern "C" int64_t sc_workspace_bytes(int32_t what, int64_t a, int64_t b, int64_
 }
 
 extern "C" int sc_hubert_layer_fwd(const sc_hubert_layer_args* p, void* stream) {
+    SC_CHECK(p != nullptr, "sc_hubert_layer_fwd: null args");
+    // split weights: checked ahead of the pointers, so the rule can be exercised without a device
+    SC_CHECK(p->w_split == 0 || p->w_split == 1, "sc_hubert_layer_fwd: w_split=%d (0 / 1)", p->w_split);
+    SC_CHECK(!p->w_split || !p->fused_ln, "sc_hubert_layer_fwd: w_split = 1 (split weights) is not built into the fused_ln form");
     SC_CHECK(p && p->x && p->out && p->valid_len && p->qk && p->vt && p->ctx && p->pre && (p->x1 || p->fused_ln) && p->ffn,
              "sc_hubert_layer_fwd: null pointer");
     SC_CHECK(p->ffn_act == 0 || p->ffn_act == 2, "sc_hubert_layer_fwd: ffn_act=%d (0 erf-GELU, 2 QuickGELU)", p->ffn_act);
     SC_CHECK(p->ffn_act == 0 || !p->fused_ln, "sc_hubert_layer_fwd: ffn_act = 2 is not built into the fused_ln form");
     const int fc1_act = p->ffn_act == 2 ? 2 : 1;      // sc_gemm_args.act of FC1
+    // w_split: the weights are the [N, 2K] hi / lo interleaves (sc_gemm_args.a_rep = 2): twice the row stride, each A tile read twice
+    const int rep = p->w_split ? 2 : 0, ws = p->w_split ? 2 : 1;
     const sc_segments* seg = p->seg;
     if (seg) {
         SC_CHECK(seg->row0 && seg->chunk && seg->B > 0 && seg->rows > 0 && seg->rows % SC_SEG_ROWS == 0 && p->H > 0 && p->D == p->H * 64 && p->F > 0,
@@ -100,17 +107,17 @@ extern "C" int sc_hubert_layer_fwd(const sc_hubert_layer_args* p, void* stream) 
         if ((rc = sc_layernorm_bf16(p->x, D, p->ln1_g, p->ln1_b, p->x1, D, M, D, p->eps, 0, stream))) return rc;
         attn_in = p->x1;
     }
-    if ((rc = gemm(attn_in, D, p->qkv_w, D, p->qk, 2 * D, M, 3 * D, D, p->qkv_b, nullptr, 0, 0, 0.f, 0, p->vt, 2 * D, p->R, 64, stream, chunk))) return rc;
+    if ((rc = gemm(attn_in, D, p->qkv_w, ws * D, p->qk, 2 * D, M, 3 * D, D, p->qkv_b, nullptr, 0, 0, 0.f, 0, p->vt, 2 * D, p->R, 64, stream, chunk, rep))) return rc;
     if ((rc = attention())) return rc;
-    if ((rc = gemm(p->ctx, D, p->o_w, D, p->pre, D, M, D, D, p->o_b, p->x, D, 0, p->p_res, p->seed_o, nullptr, -1, 0, 0, stream))) return rc;
+    if ((rc = gemm(p->ctx, D, p->o_w, ws * D, p->pre, D, M, D, D, p->o_b, p->x, D, 0, p->p_res, p->seed_o, nullptr, -1, 0, 0, stream, nullptr, rep))) return rc;
     if (p->pre_ln) {                  // pre = x + attn ; x1 = LN2(pre) ; out = pre + ffn(x1)
         if ((rc = sc_layernorm_bf16(p->pre, D, p->ln2_g, p->ln2_b, p->x1, D, M, D, p->eps, 0, stream))) return rc;
-        if ((rc = gemm(p->x1, D, p->fc1_w, D, p->ffn, F, M, F, D, p->fc1_b, nullptr, 0, fc1_act, 0.f, 0, nullptr, -1, 0, 0, stream))) return rc;
-        return gemm(p->ffn, F, p->fc2_w, F, p->out, D, M, D, F, p->fc2_b, p->pre, D, 0, p->p_res, p->seed_fc2, nullptr, -1, 0, 0, stream);
+        if ((rc = gemm(p->x1, D, p->fc1_w, ws * D, p->ffn, F, M, F, D, p->fc1_b, nullptr, 0, fc1_act, 0.f, 0, nullptr, -1, 0, 0, stream, nullptr, rep))) return rc;
+        return gemm(p->ffn, F, p->fc2_w, ws * F, p->out, D, M, D, F, p->fc2_b, p->pre, D, 0, p->p_res, p->seed_fc2, nullptr, -1, 0, 0, stream, nullptr, rep);
     }
     // post-LN: x1 = LN1(x + attn) ; out = LN2(x1 + ffn(x1))
     if ((rc = sc_layernorm_bf16(p->pre, D, p->ln1_g, p->ln1_b, p->x1, D, M, D, p->eps, 0, stream))) return rc;
-    if ((rc = gemm(p->x1, D, p->fc1_w, D, p->ffn, F, M, F, D, p->fc1_b, nullptr, 0, fc1_act, 0.f, 0, nullptr, -1, 0, 0, stream))) return rc;
-    if ((rc = gemm(p->ffn, F, p->fc2_w, F, p->pre, D, M, D, F, p->fc2_b, p->x1, D, 0, p->p_res, p->seed_fc2, nullptr, -1, 0, 0, stream))) return rc;
+    if ((rc = gemm(p->x1, D, p->fc1_w, ws * D, p->ffn, F, M, F, D, p->fc1_b, nullptr, 0, fc1_act, 0.f, 0, nullptr, -1, 0, 0, stream, nullptr, rep))) return rc;
+    if ((rc = gemm(p->ffn, F, p->fc2_w, ws * F, p->pre, D, M, D, F, p->fc2_b, p->x1, D, 0, p->p_res, p->seed_fc2, nullptr, -1, 0, 0, stream, nullptr, rep))) return rc;
     return sc_layernorm_bf16(p->pre, D, p->ln2_g, p->ln2_b, p->out, D, M, D, p->eps, 0, stream);
 }

@@ -262,6 +262,14 @@ class KWClip_GeneralTransformer(nn.Module):
             _params += list(self.parallel_branch.parameters())
         return _params
 
+    def set_eval_weights(self, mode: str, hubert_state_dict: Optional[dict] = None):
+        """'bf16' (default) or 'split': what the frozen HuBERT GEMMs multiply in eval mode (``model.eval()``) - bf16(W), or W_hi + W_lo
+        without the common embedding shift of the weight rounding (config key ``audio_encoder.eval_weights``;
+        FairseqSpeechEncoder_Hubert.set_eval_weights).  Train mode is the same either way.  ``hubert_state_dict``: the fp32 HuBERT
+        weights, needed when the model was not built with ``audio_encoder.eval_weights: split``."""
+        self.audio_encoder.set_eval_weights(mode, state_dict=hubert_state_dict)
+        return self
+
     def forward_audio(self, wav, wav_len=[], return_hidden_states: bool = False):
         return self.audio_encoder(wav, wav_len, return_hidden_states=return_hidden_states)
 

@@ -140,11 +140,12 @@ def gemm_raw(A: torch.Tensor, lda: int, W: torch.Tensor, ldw: int, C: torch.Tens
              res_stats: Optional[torch.Tensor] = None, res_ns: int = 0, res_gamma: Optional[torch.Tensor] = None,
              res_beta: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None, ln_eps: float = 0.0,
              tn: bool = False, k_total: int = 0, aux: Optional[torch.Tensor] = None, aux_mode: int = 0,
-             seg: Optional["RowSegments"] = None) -> int:
+             seg: Optional["RowSegments"] = None, a_rep: int = 0) -> int:
     """C = epi(A . W^T); see sc_gemm_args in include/speechclip_hip.h.  Pointers are the tensors' data_ptr()
     (pass a sliced view to offset).  ``alg_rows``: rows that are algorithmic work (excludes layout padding),
     used only by the optional KernelTimer.  ``ln_*`` / ``res_*`` / ``stats_out``: LayerNorm folded into the GEMM (row-statistics
-    buffers are [M, 8, 2] fp32); returns the number of statistics strips written per row (0 without ``stats_out``)."""
+    buffers are [M, 8, 2] fp32); returns the number of statistics strips written per row (0 without ``stats_out``).
+    ``a_rep`` = 2: ``W`` is the [N, 2K] hi / lo interleave of ``split_weight_bf16`` and every A tile is read twice (``K`` stays A's)."""
     assert A.dtype == torch.bfloat16 and W.dtype == torch.bfloat16
     assert C.dtype == (torch.float32 if out_f32 else torch.bfloat16)
     if bias is not None:
@@ -168,6 +169,7 @@ def gemm_raw(A: torch.Tensor, lda: int, W: torch.Tensor, ldw: int, C: torch.Tens
     a.drop_p, a.drop_seed = float(drop_p), int(drop_seed) & 0xffffffff
     a.tap_c = int(tap_c)
     a.k_total = int(k_total)
+    a.a_rep = int(a_rep)
     if aux_mode == 3:       # forward-only twin of mode 1: the activation of the rounded pre-activation, which is not stored
         assert aux is None and Ct is None
         a.aux_mode = 3
@@ -210,14 +212,16 @@ def gemm_raw(A: torch.Tensor, lda: int, W: torch.Tensor, ldw: int, C: torch.Tens
 
 def hubert_layer_fwd(x: torch.Tensor, out: torch.Tensor, valid_len: torch.Tensor, w: dict, i: int, pl, B: int, R: int, T: int, D: int,
                      F_: int, H: int, pre_ln: bool, p_attn: float = 0.0, p_res: float = 0.0, seeds=(0, 0, 0), fused=None,
-                     seg: Optional["RowSegments"] = None, ffn_act: int = 0) -> None:
+                     seg: Optional["RowSegments"] = None, ffn_act: int = 0, w_split: bool = False) -> None:
     """One frozen HuBERT encoder layer in ONE C-ABI call (sc_hubert_layer_fwd: QKV -> attention -> out_proj -> LN -> FC1 -> FC2 ->
     LN on the caller's stream).  ``w``: the encoder's weight dict (keys l{i}_*), ``pl``: its plan (scratch buffers).
     ``fused`` = (x_stats or None, x_ns, out_stats): the LayerNorm-free form (the LayerNorms folded into the GEMMs; ``out`` receives
     raw rows + statistics); x_stats None = ``x`` is an ordinary, materialised input (layer 0).  ``ffn_act``: FC1 activation, 0 erf-GELU,
-    2 QuickGELU (the CLIP image tower's blocks, clip_image.py)."""
+    2 QuickGELU (the CLIP image tower's blocks, clip_image.py).  ``w_split``: the four GEMM weights in ``w`` are the [N, 2K] hi / lo
+    interleaves of ``split_weight_bf16`` (evaluation; not with ``fused``)."""
     a = HubertLayerArgs()
     a.ffn_act = int(ffn_act)
+    a.w_split = int(bool(w_split))
     a.x, a.out, a.valid_len = _p(x), _p(out), _p(valid_len)
     a.B, a.R, a.T, a.D, a.F, a.H, a.pre_ln = B, R, T, D, F_, H, int(pre_ln)
     a.qkv_w, a.o_w, a.fc1_w, a.fc2_w = _p(w[f"l{i}_qkv_w"]), _p(w[f"l{i}_o_w"]), _p(w[f"l{i}_fc1_w"]), _p(w[f"l{i}_fc2_w"])
@@ -252,21 +256,47 @@ def gemm_stats_strips(M: int, N: int) -> int:
 def linear_bf16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, act: int = 0, out_f32: bool = False,
                 alg_rows: Optional[int] = None, tile: int = 0, drop_p: float = 0.0, drop_seed: int = 0,
-                aux: Optional[torch.Tensor] = None, aux_mode: int = 0, ln_colsum: Optional[torch.Tensor] = None, ln_eps: float = 0.0) -> torch.Tensor:
+                aux: Optional[torch.Tensor] = None, aux_mode: int = 0, ln_colsum: Optional[torch.Tensor] = None, ln_eps: float = 0.0,
+                a_rep: int = 0) -> torch.Tensor:
     """y[M, N] = epi(x[M, K] . w[N, K]^T) for contiguous 2-D operands.  ``aux`` / ``aux_mode`` (small problems, 128-row tiles):
     1 = also store the pre-activation into ``aux`` and return act(it); 2 = return (x . w^T) * act'(aux); 3 = the values of 1, nothing
     stored (``aux`` None).
     ``ln_colsum`` / ``ln_eps``: y = epi(LayerNorm(x) . w0^T) with the LayerNorm in the GEMM's prologue - ``w`` = w0 diag(gamma),
-    ``ln_colsum[n]`` = sum_k w[n, k], ``bias[n]`` = sum_k beta[k] w0[n, k] + bias0[n] (``fold_layernorm``); K <= 1024."""
+    ``ln_colsum[n]`` = sum_k w[n, k], ``bias[n]`` = sum_k beta[k] w0[n, k] + bias0[n] (``fold_layernorm``); K <= 1024.
+    ``a_rep`` = 2: ``w`` is the [N, 2K] hi / lo interleave of ``split_weight_bf16``."""
     M, K = x.shape
     N = w.shape[0]
-    assert w.shape[1] == K and x.stride(1) == 1 and w.stride(1) == 1
+    assert w.shape[1] == (2 * K if a_rep == 2 else K) and x.stride(1) == 1 and w.stride(1) == 1
     if out is None:
         out = torch.empty(M, N, device=x.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
     gemm_raw(x, x.stride(0), w, w.stride(0), out, out.stride(0), M, N, K, bias=bias, residual=residual,
              ldr=residual.stride(0) if residual is not None else 0, act=act, out_f32=out_f32, alg_rows=alg_rows, tile=tile,
-             drop_p=drop_p, drop_seed=drop_seed, aux=aux, aux_mode=aux_mode, ln_colsum=ln_colsum, ln_eps=ln_eps)
+             drop_p=drop_p, drop_seed=drop_seed, aux=aux, aux_mode=aux_mode, ln_colsum=ln_colsum, ln_eps=ln_eps, a_rep=a_rep)
     return out
+
+
+SPLIT_BK = 64       # K-tile of the GEMM kernels: the granularity of the hi / lo interleave
+
+
+def split_weight_bf16(w: torch.Tensor) -> torch.Tensor:
+    """fp32 weight [..., N, K] (K % 64 == 0) -> the [..., N, 2K] bf16 operand of sc_gemm_args.a_rep = 2: W_hi = bf16(W),
+    W_lo = bf16(W - W_hi), interleaved by 64-column K-tile [hi tile 0 | lo tile 0 | hi tile 1 | ...].  W_hi + W_lo is exact in fp32 and
+    carries ~16 significant bits of W.  Plain torch, on whatever device ``w`` lives (run once per weight, on load)."""
+    w = w.detach().float()
+    K = w.shape[-1]
+    assert K % SPLIT_BK == 0, f"split_weight_bf16: K={K} must be a multiple of {SPLIT_BK}"
+    hi = w.to(torch.bfloat16)
+    lo = (w - hi.float()).to(torch.bfloat16)
+    lead = w.shape[:-1]
+    both = torch.stack((hi.reshape(*lead, K // SPLIT_BK, SPLIT_BK), lo.reshape(*lead, K // SPLIT_BK, SPLIT_BK)), dim=-2)
+    return both.reshape(*lead, 2 * K).contiguous()
+
+
+def split_weight_sum(ws: torch.Tensor) -> torch.Tensor:
+    """The fp32 weight W_hi + W_lo (exact) that a [..., N, 2K] interleave of ``split_weight_bf16`` stands for."""
+    lead, K2 = ws.shape[:-1], ws.shape[-1]
+    t = ws.float().reshape(*lead, K2 // (2 * SPLIT_BK), 2, SPLIT_BK)
+    return (t[..., 0, :] + t[..., 1, :]).reshape(*lead, K2 // 2)
 
 
 def fold_layernorm(w0: torch.Tensor, bias0: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor):

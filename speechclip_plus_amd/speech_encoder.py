@@ -305,7 +305,7 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
                  feat_select_idx: Union[str, list] = "all", layer_drop: Union[str, float] = 0.0, max_audio_len: int = -1,
                  reinit_layers: List[int] = [], unfreeze_layers: List[int] = [], normalize_hiddenstates: bool = False,
                  normalize_type: str = "s3prl", state_dict: Optional[Dict[str, torch.Tensor]] = None,
-                 arch: Optional[HubertArch] = None, seed: int = 7122, **kwargs):
+                 arch: Optional[HubertArch] = None, seed: int = 7122, eval_weights: str = "bf16", **kwargs):
         super().__init__()
         assert name in ARCHS, "Model name({}) should be in {}".format(name, ARCHS.keys())
         self.name = name
@@ -350,6 +350,13 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
         self.out_dim = self.arch.embed_dim
         self.upstream_model_hiddenstates_len = self.arch.layers + 1
         self._dev = torch.device(device)
+        # eval_weights = "split" (round 9): in eval mode the frozen GEMMs multiply W_hi + W_lo (two bf16 addends, ~16 significant bits;
+        # sc_gemm_args.a_rep = 2) instead of bf16(W) - the embeddings lose the shift that the bf16 rounding of the weights adds to every
+        # utterance.  Train mode never reads the split forms.
+        self._w_split = None
+        self.eval_weights = "bf16"
+        self._check_eval_weights(eval_weights)
+        self.eval_weights = eval_weights
         if state_dict is None:
             if pretrained:
                 logger.warning("no checkpoint available offline: HuBERT weights are seeded random (seed %d)", seed)
@@ -444,7 +451,60 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
             w["lazy_gamma"] = f32(torch.stack([torch.ones(a.embed_dim)] + [sd[f"encoder.layers.{i}.final_layer_norm.weight"].float() for i in range(a.layers)]))
             w["lazy_beta"] = f32(torch.stack([torch.zeros(a.embed_dim)] + [sd[f"encoder.layers.{i}.final_layer_norm.bias"].float() for i in range(a.layers)]))
         self._w = w          # frozen device tensors (not nn.Parameters: no grads, no optimizer state)
+        self._w_split = self._split_weights(sd) if self.eval_weights == "split" else None
         self._weights_dirty = True       # _encode_overlapped: the encoder stream has to see these before its next forward
+
+    SPLIT_REASONS = {
+        "trainable": "eval_weights='split' is an evaluation mode of the FROZEN encoder: a trainable or partly unfrozen encoder "
+                     "(trainable / reinit_layers / unfreeze_layers) multiplies its own bf16 working copies, which have no split form",
+        "fused_ln": "eval_weights='split' does not combine with SC_FUSED_LN=1: the LayerNorm-folded GEMMs have no split-weight form "
+                    "(sc_gemm_args.a_rep = 2 is refused with ln_* / stats_out / res_stats)",
+    }
+
+    def _check_eval_weights(self, mode: str) -> None:
+        if mode not in ("bf16", "split"):
+            raise ValueError(f"eval_weights = {mode!r}: 'bf16' or 'split'")
+        if mode == "split":
+            if self.trainable or self._train_ids:
+                raise NotImplementedError(self.SPLIT_REASONS["trainable"])
+            if _FUSED_LN:
+                raise NotImplementedError(self.SPLIT_REASONS["fused_ln"])
+
+    def _split_weights(self, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """The weight dict of the eval-mode split path: ``self._w`` with every frozen GEMM weight - conv 1-6, post_extract_proj, each
+        layer's qkv / out / fc1 / fc2 - replaced by its [N, 2K] hi / lo interleave (ops.split_weight_bf16) built from the fp32 state
+        dict.  Everything else (conv 0, pos_conv on the slab kernel, norms, biases) is shared with ``self._w``."""
+        a, dev = self.arch, self._dev
+        sp = lambda t: ops.split_weight_bf16(t.detach().to(device=dev, dtype=torch.float32))
+        w = dict(self._w)
+        for i in range(1, len(a.conv_kernels)):
+            cw = sd[f"feature_extractor.conv_layers.{i}.0.weight"]
+            w[f"conv{i}_w"] = sp(cw.permute(0, 2, 1).reshape(cw.shape[0], -1))
+        w["proj_w"] = sp(sd["post_extract_proj.weight"])
+        for i in range(a.layers):
+            p = f"encoder.layers.{i}."
+            w[f"l{i}_qkv_w"] = sp(torch.cat([sd[p + f"self_attn.{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0))
+            w[f"l{i}_o_w"] = sp(sd[p + "self_attn.out_proj.weight"])
+            w[f"l{i}_fc1_w"] = sp(sd[p + "fc1.weight"])
+            w[f"l{i}_fc2_w"] = sp(sd[p + "fc2.weight"])
+        return w
+
+    def set_eval_weights(self, mode: str, state_dict: Optional[Dict[str, torch.Tensor]] = None) -> None:
+        """Switch the eval-mode weights between 'bf16' and 'split'.  The split forms are built from fp32 weights: an encoder that was
+        not constructed with eval_weights='split' needs ``state_dict`` (the fp32 weights it was loaded from) here; whenever a
+        ``state_dict`` is given the split forms are rebuilt from it.  It must hold the weights the encoder was loaded with: the
+        bf16 forms train mode reads are not touched."""
+        self._check_eval_weights(mode)
+        if mode == "split" and (self._w_split is None or state_dict is not None):       # a state dict handed over always rebuilds
+            if state_dict is None:
+                raise ValueError("set_eval_weights('split'): the split forms come from the fp32 weights, which the encoder does not keep - "
+                                 "pass state_dict=, or construct the encoder with eval_weights='split'")
+            self._w_split = self._split_weights(state_dict)
+            self._weights_dirty = True
+        self.eval_weights = mode
+
+    def _split_active(self) -> bool:
+        return self.eval_weights == "split" and not self.training
 
     def trainable_params(self) -> list:
         """speech_encoder_plus.py:478-494.  Frozen encoder: only the weighted-sum weights train; with ``reinit_layers`` the
@@ -726,6 +786,9 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
     @torch.no_grad()
     def _encode_kernels(self, pl: _Plan, padded: torch.Tensor, save: bool) -> None:
         a, w = self.arch, self._w
+        a_rep = 0
+        if self._split_active():                # eval mode, eval_weights = "split": the [N, 2K] hi / lo forms, every A tile read twice
+            w, a_rep = self._w_split, 2
         seeds = self._dropout_seeds()           # None in eval mode: every drop_p below is 0
         p_in, p_res, p_att = ((a.dropout_input, a.dropout, a.attention_dropout) if seeds else (0.0, 0.0, 0.0))
         if seeds and a.activation_dropout > 0.0:
@@ -749,12 +812,13 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
             self.frontend.refresh()
             self.frontend.forward_frontend(pl, L, p_in, p_res, sd(0), sd(1))
         else:
-            self._frontend_frozen(pl, w, seeds, sd, p_in, p_res, padded)
-        self._layers(pl, w, seeds, sd, p_res, p_att, save, scale, first_hidden_done=train_front)
+            self._frontend_frozen(pl, w, seeds, sd, p_in, p_res, padded, a_rep=a_rep)
+        self._layers(pl, w, seeds, sd, p_res, p_att, save, scale, first_hidden_done=train_front, a_rep=a_rep)
 
     @torch.no_grad()
-    def _frontend_frozen(self, pl, w, seeds, sd, p_in, p_res, padded=None) -> None:
+    def _frontend_frozen(self, pl, w, seeds, sd, p_in, p_res, padded=None, a_rep: int = 0) -> None:
         a = self.arch
+        ws = 2 if a_rep == 2 else 1             # row stride factor of the split ([N, 2K]) weights
         B, L = pl.B, pl.L
         C, D, F, H = a.conv_dim, a.embed_dim, a.ffn_dim, a.heads
         R, M, T = pl.R, pl.M, pl.T
@@ -779,9 +843,9 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
         for i in range(1, nl):
             k, s = a.conv_kernels[i], a.conv_strides[i]
             rows = M * (2 ** (nl - 1 - i)) if seg is not None else B * pl.R_l[i]
-            ops.gemm_raw(pl.conv[i - 1], s * C, w[f"conv{i}_w"], k * C, pl.conv[i], C, rows, C, k * C,
+            ops.gemm_raw(pl.conv[i - 1], s * C, w[f"conv{i}_w"], ws * k * C, pl.conv[i], C, rows, C, k * C,
                          bias=w[f"conv{i}_bias"], act=0 if ln_mode else 1, alg_rows=alg[i],
-                         tap_c=C if (k == 3 and s == 2) else 0)      # shared-tap K order: see sc_gemm_args.tap_c
+                         tap_c=C if (k == 3 and s == 2) else 0, a_rep=a_rep)      # shared-tap K order: see sc_gemm_args.tap_c
             if ln_mode:
                 ops.layernorm_bf16(pl.conv[i][:rows], w[f"conv{i}_ln_g"], w[f"conv{i}_ln_b"], out=pl.conv[i][:rows], act=1)
         if self._section_ev is not None:
@@ -789,7 +853,7 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
             self._section_ev["conv_done"].record()
         # a3: LayerNorm(512) -> post_extract_proj                                       (:78, :84-85)
         ops.layernorm_bf16(pl.conv[-1][:M], w["ln_feat_g"], w["ln_feat_b"], out=pl.feat_ln)
-        ops.linear_bf16(pl.feat_ln, w["proj_w"], w["proj_b"], out=pl.x_proj, alg_rows=alg[-1], drop_p=p_in, drop_seed=sd(0))   # dropout_input (:87)
+        ops.linear_bf16(pl.feat_ln, w["proj_w"], w["proj_b"], out=pl.x_proj, alg_rows=alg[-1], drop_p=p_in, drop_seed=sd(0), a_rep=a_rep)   # dropout_input (:87)
         # a4: zero padded frames, grouped pos_conv + GELU, residual, LayerNorm          (:32-40)
         G, Kp = a.pos_conv_groups, a.pos_conv_kernel
         Dg, Rp = D // G, R + 2 * pl.halo
@@ -817,8 +881,9 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
         tl.refresh()
         return True
 
-    def _layers(self, pl, w, seeds, sd, p_res, p_att, save, scale, first_hidden_done) -> None:
+    def _layers(self, pl, w, seeds, sd, p_res, p_att, save, scale, first_hidden_done, a_rep: int = 0) -> None:
         a = self.arch
+        split = a_rep == 2                      # w = the split weight dict (eval mode only: no unfrozen layer, no dropout)
         B, L = pl.B, pl.L
         C, D, F, H = a.conv_dim, a.embed_dim, a.ffn_dim, a.heads
         R, M, T = pl.R, pl.M, pl.T
@@ -828,8 +893,8 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
         alg_att = pl.alg_attn_flops if seg is not None else 4.0 * B * T * T * D
 
         def qkv_attn(x, i):
-            ops.gemm_raw(x, D, w[f"l{i}_qkv_w"], D, pl.qk, 2 * D, M, 3 * D, D, bias=w[f"l{i}_qkv_b"], Ct=pl.vt,
-                         n_split=2 * D, R=R, dh=D // H, alg_rows=alg_M, seg=seg)
+            ops.gemm_raw(x, D, w[f"l{i}_qkv_w"], 2 * D if split else D, pl.qk, 2 * D, M, 3 * D, D, bias=w[f"l{i}_qkv_b"], Ct=pl.vt,
+                         n_split=2 * D, R=R, dh=D // H, alg_rows=alg_M, seg=seg, a_rep=a_rep)
             ops.attn_fwd(pl.qk, pl.vt, pl.valid, pl.ctx, B, R, H, D, scale, alg_flops=alg_att,
                          drop_p=p_att, drop_seed=sd(3 * i + 2), seg=seg)
 
@@ -855,17 +920,17 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
                     continue
                 if ops._timer is None:          # one C-ABI call per frozen layer (sc_hubert_layer_fwd); the per-op path below is
                     ops.hubert_layer_fwd(x, pl.hidden[i + 1], pl.valid, w, i, pl, B, R, T, D, F, H, False, p_att, p_res,
-                                         (sd(3 * i + 2), sd(3 * i + 3), sd(3 * i + 4)), seg=seg)   # kept for bench.py's per-kernel timer
+                                         (sd(3 * i + 2), sd(3 * i + 3), sd(3 * i + 4)), seg=seg, w_split=split)   # kept for bench.py's per-kernel timer
                     continue
                 qkv_attn(x, i)
                 # train mode: dropout1 / dropout3 of fairseq's TransformerSentenceEncoderLayer in the GEMM epilogues (before the
                 # residual add), attention dropout inside the attention kernel
                 ops.linear_bf16(pl.ctx, w[f"l{i}_o_w"], w[f"l{i}_o_b"], out=pl.pre, residual=x, alg_rows=alg_M,
-                                drop_p=p_res, drop_seed=sd(3 * i + 3))
+                                drop_p=p_res, drop_seed=sd(3 * i + 3), a_rep=a_rep)
                 ops.layernorm_bf16(pl.pre, w[f"l{i}_ln1_g"], w[f"l{i}_ln1_b"], out=pl.x1)
-                ops.linear_bf16(pl.x1, w[f"l{i}_fc1_w"], w[f"l{i}_fc1_b"], out=pl.ffn, act=1, alg_rows=alg_M)
+                ops.linear_bf16(pl.x1, w[f"l{i}_fc1_w"], w[f"l{i}_fc1_b"], out=pl.ffn, act=1, alg_rows=alg_M, a_rep=a_rep)
                 ops.linear_bf16(pl.ffn, w[f"l{i}_fc2_w"], w[f"l{i}_fc2_b"], out=pl.pre, residual=pl.x1, alg_rows=alg_M,
-                                drop_p=p_res, drop_seed=sd(3 * i + 4))
+                                drop_p=p_res, drop_seed=sd(3 * i + 4), a_rep=a_rep)
                 ops.layernorm_bf16(pl.pre, w[f"l{i}_ln2_g"], w[f"l{i}_ln2_b"], out=pl.hidden[i + 1])
         else:
             # pre-LN layers (large): x = x + attn(LN1(x)); x = x + ffn(LN2(x)); layer_results are NOT passed through
@@ -886,16 +951,16 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
                     continue
                 if ops._timer is None:
                     ops.hubert_layer_fwd(x, pl.hidden[i + 1], pl.valid, w, i, pl, B, R, T, D, F, H, True, p_att, p_res,
-                                         (sd(3 * i + 2), sd(3 * i + 3), sd(3 * i + 4)), seg=seg)
+                                         (sd(3 * i + 2), sd(3 * i + 3), sd(3 * i + 4)), seg=seg, w_split=split)
                     continue
                 ops.layernorm_bf16(x, w[f"l{i}_ln1_g"], w[f"l{i}_ln1_b"], out=pl.x1)
                 qkv_attn(pl.x1, i)
                 ops.linear_bf16(pl.ctx, w[f"l{i}_o_w"], w[f"l{i}_o_b"], out=pl.pre, residual=x, alg_rows=alg_M,
-                                drop_p=p_res, drop_seed=sd(3 * i + 3))
+                                drop_p=p_res, drop_seed=sd(3 * i + 3), a_rep=a_rep)
                 ops.layernorm_bf16(pl.pre, w[f"l{i}_ln2_g"], w[f"l{i}_ln2_b"], out=pl.x1)
-                ops.linear_bf16(pl.x1, w[f"l{i}_fc1_w"], w[f"l{i}_fc1_b"], out=pl.ffn, act=1, alg_rows=alg_M)
+                ops.linear_bf16(pl.x1, w[f"l{i}_fc1_w"], w[f"l{i}_fc1_b"], out=pl.ffn, act=1, alg_rows=alg_M, a_rep=a_rep)
                 ops.linear_bf16(pl.ffn, w[f"l{i}_fc2_w"], w[f"l{i}_fc2_b"], out=pl.hidden[i + 1], residual=pl.pre,
-                                alg_rows=alg_M, drop_p=p_res, drop_seed=sd(3 * i + 4))
+                                alg_rows=alg_M, drop_p=p_res, drop_seed=sd(3 * i + 4), a_rep=a_rep)
 
     @torch.no_grad()
     def _layers_fused(self, pl, w, sd, p_res, p_att, scale) -> None:

@@ -110,6 +110,23 @@ def hubert_weights() -> Dict[str, torch.Tensor]:
 PLAN = ((1, 200), (3, 50), (7, 20), (14, 6))     # (images ranked above the own image, number of such ids)
 
 
+def split_emulation_weights(W: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The HuBERT weights as the split eval mode (audio_encoder.eval_weights: split) multiplies them: W_hi + W_lo = bf16(W) +
+    bf16(W - bf16(W)), exact in fp32, for every GEMM weight the mode splits (conv 1-6, post_extract_proj, q / k / v / out, fc1, fc2);
+    bf16(W) for pos_conv (slab kernel, bf16 weights); everything the HIP path holds in fp32 unchanged.  The one definition of the
+    treatment `w_split` (tools/storage_ablation.py, tests/split_cases.py, tests/golden/make_recall_splitw_fixture.py)."""
+    import oracle
+    rounded = oracle.bf16_weights(W)
+    out = {}
+    for k, v in W.items():
+        if torch.equal(rounded[k].float(), v.float()) or k.startswith("encoder.pos_conv."):
+            out[k] = rounded[k]
+        else:
+            hi = v.float().to(torch.bfloat16).float()
+            out[k] = hi + (v.float() - hi).to(torch.bfloat16).float()
+    return out
+
+
 def build_gallery(a_o: torch.Tensor, ids: torch.Tensor, n_ids: int, seed: int = SEED_DATA + 99, reg: float = 1.0, r_sub: int = 128,
                   safety: float = 1.45, vic_frac: float = 0.78, plan=PLAN):
     """The 1000 "frozen CLIP" image embeddings of the eval set, built from the ORACLE's unit audio embeddings ``a_o`` [5 n_ids, E]
@@ -227,11 +244,14 @@ def correct_rank(score: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     return (score > own).sum(1)
 
 
-def build_model(device: str = "cuda:0"):
-    """The product model (Parallel SpeechCLIP base) on the eval set's seeded weights."""
+def build_model(device: str = "cuda:0", eval_weights: str = "bf16"):
+    """The product model (Parallel SpeechCLIP base) on the eval set's seeded weights.  ``eval_weights``: 'bf16' | 'split'
+    (audio_encoder.eval_weights: what the frozen HuBERT GEMMs multiply in eval mode)."""
     from speechclip_plus_amd import KWClip_GeneralTransformer, base_parallel_config
     cfg = base_parallel_config()
     cfg.audio_encoder.max_audio_len = -1
+    if eval_weights != "bf16":
+        cfg.audio_encoder.eval_weights = eval_weights
     model = KWClip_GeneralTransformer(cfg, device=device, hubert_state_dict=hubert_weights()).eval()
     model.parallel_branch.load_state_dict(head_weights(), strict=True)
     with torch.no_grad():
@@ -352,3 +372,27 @@ def hip_recall(model, fixture: dict, dump: str = None, emb: torch.Tensor = None)
     e_f, e_e = F.normalize(T("emb_head_fp32"), dim=-1), F.normalize(T("emb_head_bf16emu"), dim=-1)
     out["emulation_distance_from_fp32"] = round(float((e_e - e_f).norm(dim=-1).mean()), 5)
     return out
+
+
+def main():
+    """python tools/recall_eval.py [--eval-weights split] [--out FILE]: the product model on the natural-margin galleries A and B"""
+    import argparse
+    import json
+    import numpy as np
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--eval-weights", choices=("bf16", "split"), default="bf16")
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
+    fx = {g: dict(np.load(os.path.join(golden, name))) for g, name in (("A", "recall_eval_natural.npz"), ("B", "recall_eval_natural_b.npz"))}
+    model = build_model(args.device, eval_weights=args.eval_weights)
+    emb = hip_embeddings(model, int(fx["A"]["n_ids"]), BATCH)
+    report = {"eval_weights": args.eval_weights, **{"gallery_" + g: natural_margin_report(emb, f) for g, f in fx.items()}}
+    print(json.dumps(report))
+    if args.out:
+        json.dump(report, open(args.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -9,6 +9,9 @@ This tool switches the rounding on for ONE site class at a time (oracle.SitedSto
 Configs: fp32 | all (= the emulation) | weights | conv | ln | proj | residual | qkv | p | ctx | ffn_act | wsum, and any "+"-joined set;
 weight GROUPS (round 6, after "weights" turned out to carry 0.0052 of the 0.0057): w_conv (conv layers 1-6) | w_proj (post_extract_proj,
 pos_conv) | w_attn (q / k / v / out projections) | w_ffn (fc1, fc2) | w_lo (encoder layers 0-5) | w_hi (layers 6-11).
+Weight TREATMENT w_split (round 9): every GEMM weight the split eval mode covers (conv 1-6, post_extract_proj, q / k / v / out, fc1, fc2) is
+replaced by W_hi + W_lo = bf16(W) + bf16(W - bf16(W)), exact in fp32; pos_conv keeps bf16(W) as in the product.  The two rows of the ceiling:
+"conv+ln+proj+residual+qkv+p+ctx+ffn_act+wsum" (every activation site, weights exact) and the same "+w_split".
 
     python tools/storage_ablation.py --cache /tmp/ablation --threads 6 [--configs weights conv ...] [--out profiles/r06_storage_ablation.json]
 
@@ -27,7 +30,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
-from recall_eval import BATCH, WS_WEIGHTS, embed_all, eval_set, head_weights, hubert_weights, rank_stats, recalls  # noqa: E402
+from recall_eval import BATCH, WS_WEIGHTS, embed_all, eval_set, head_weights, hubert_weights, rank_stats, recalls, split_emulation_weights  # noqa: E402
 
 SITES = ("conv", "ln", "proj", "residual", "qkv", "p", "ctx", "ffn_act")
 _layer = lambda k: int(k.split(".")[2]) if k.startswith("encoder.layers.") else -1
@@ -43,10 +46,13 @@ def embeddings(config: str, wavs, cache: str) -> torch.Tensor:
     if os.path.exists(path):
         return torch.from_numpy(np.load(path))
     on = set(SITES) | {"weights", "wsum"} if config == "all" else set() if config == "fp32" else set(config.split("+"))
-    assert on <= set(SITES) | {"weights", "wsum"} | set(WGROUPS), on
+    assert on <= set(SITES) | {"weights", "wsum", "w_split"} | set(WGROUPS), on
+    assert not ("w_split" in on and "weights" in on), "w_split and weights are two treatments of the same weights"
     Wh, Whead, arch = hubert_weights(), head_weights(), oracle.HubertArch.base()
     if "weights" in on:
         Wh = oracle.bf16_weights(Wh)
+    if "w_split" in on:                      # the split eval mode's weights: hi + lo where it splits, bf16 for pos_conv
+        Wh = split_emulation_weights(Wh)
     for grp in on & set(WGROUPS):            # the bf16 rounding on ONE group of GEMM weights
         rounded = oracle.bf16_weights(Wh)
         Wh = {k: (rounded[k] if WGROUPS[grp](k) else v) for k, v in Wh.items()}
