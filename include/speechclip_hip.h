@@ -29,7 +29,8 @@ extern "C" {
 typedef uint16_t sc_bf16;
 
 const char* sc_last_error(void);
-int sc_abi_version(void);     /* 6 (round 9, additive: sc_gemm_args.a_rep / sc_hubert_layer_args.w_split took the reserved3 / reserved2 slots - split
+int sc_abi_version(void);     /* 6 (round 10, additive: sc_attn_fwd_relbias_bf16, sc_attn_fwd_seg_relbias_bf16, sc_wavlm_gate_bf16 - WavLM's gated relative-
+                                 position bias; nothing else changed); 6 (round 9, additive: sc_gemm_args.a_rep / sc_hubert_layer_args.w_split took the reserved3 / reserved2 slots - split
                                  weights for evaluation; sizes unchanged); 6: one front-end entry point per kernel (sc_wav_prep, sc_conv0_stats, sc_conv0_gn_gelu, sc_conv0_ln_gelu take
                                  seg / wav_off / out_f32; their _seg, _crop, _len and _f32 symbols are gone); 5: sc_adam_f32 takes its betas as doubles; 4 since round 4 (sc_segments; sc_gemm_args / sc_hubert_layer_args grew the segment fields) */
 int sc_is_diag_build(void);   /* 1: libspeechclip_hip_diag.so - the same sources built with SC_DIAG_BUILD: also holds the diagnostic kernels
@@ -190,6 +191,34 @@ int sc_attn_fwd_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const i
 int sc_attn_fwd_seg_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
                          const sc_segments* seg, const int32_t* work, int32_t nwork, int32_t H, int32_t D, float scale, float* lse2,
                          int32_t causal, float drop_p, uint32_t drop_seed, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The same two with WavLM's gated relative-position bias:  softmax(scale q k^T + gate[h][i] table[h][j - i] + kpm(-inf)) v
+ *   replaces: microsoft/unilm wavlm/modules.py MultiheadAttention.forward with position_bias (the s3prl upstreams wavlm_base /
+ *             wavlm_base_plus / wavlm_large behind S3prlSpeechEncoderPlus, avssl/module/speech_encoder_plus.py:145,278-281) and
+ *             transformers WavLMAttention.forward step 4 + torch_multi_head_self_attention - both materialise
+ *             gate . position_bias as [B H, T, T] and hand it to the softmax as an additive mask; here it is never formed
+ *   gate  [H][rows] fp32, rows = B R (uniform) or seg->rows: one value per (head, query row) in the row layout of the call
+ *         (sc_wavlm_gate_bf16); pad rows may hold anything finite
+ *   table [H][2 tmax - 1] fp32, natural-log units: entry tmax - 1 + (j - i) = the bias of key j seen from query i; tmax >= the
+ *         (largest) row pitch, which is limited to 8064 rows (the workgroup's slice of the table sits in LDS)
+ *   causal must be 0 (error otherwise).  Dropout element index and hash as in the plain calls.  lse2 covers the biased values.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_attn_fwd_relbias_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
+                             int32_t B, int32_t R, int32_t H, int32_t D, float scale, const float* gate, const float* table, int32_t tmax,
+                             float* lse2, int32_t causal, float drop_p, uint32_t drop_seed, void* stream);
+int sc_attn_fwd_seg_relbias_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
+                                 const sc_segments* seg, const int32_t* work, int32_t nwork, int32_t H, int32_t D, float scale,
+                                 const float* gate, const float* table, int32_t tmax, float* lse2, int32_t causal, float drop_p,
+                                 uint32_t drop_seed, void* stream);
+
+/* The gate of that bias, one launch per layer.
+ *   replaces: unilm MultiheadAttention.forward's gru_rel_pos branch (grep_linear / grep_a) = transformers WavLMAttention.forward
+ *             steps 1-3 (gru_rel_pos_linear / gru_rel_pos_const)
+ *   x [rows, ldx] bf16: the rows the QKV GEMM reads, head h = columns h*64 .. h*64+63; wg [8, 64], bg [8], cst [H] fp32
+ *   p = wg . x_h + bg ; a = sigmoid(p[0..3] summed) ; b = sigmoid(p[4..7] summed) ; gate[h][row] = a (b cst[h] - 1) + 2   (fp32) */
+int sc_wavlm_gate_bf16(const sc_bf16* x, int64_t ldx, const float* wg, const float* bg, const float* cst, float* gate, int64_t rows,
+                       int32_t H, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Self-attention backward, head_dim 64 (fairseq MultiheadAttention / nn.MultiheadAttention / CLIP ResidualAttentionBlock

@@ -114,6 +114,11 @@ SIGNATURES = {
                          c_float, ctypes.c_uint32, c_void_p],
     "sc_attn_fwd_seg_bf16": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, ctypes.POINTER(Segments), c_void_p, c_int, c_int, c_int,
                              c_float, c_void_p, c_int, c_float, ctypes.c_uint32, c_void_p],
+    "sc_attn_fwd_relbias_bf16": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int,
+                                 c_void_p, c_int, c_float, ctypes.c_uint32, c_void_p],
+    "sc_attn_fwd_seg_relbias_bf16": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, ctypes.POINTER(Segments), c_void_p, c_int, c_int, c_int,
+                                     c_float, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, ctypes.c_uint32, c_void_p],
+    "sc_wavlm_gate_bf16": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p],
     "sc_posconv_prep_seg": [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_void_p],
     "sc_posconv_seg_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_void_p],
     "sc_wsum_fwd_seg": [c_void_p, c_void_p, c_int, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_int, c_void_p],

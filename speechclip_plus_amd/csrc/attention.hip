@@ -9,7 +9,20 @@
 // is two 8-byte LDS reads.  K and V^T tiles (64 keys) are staged through LDS with register prefetch
 // (global loads for tile t+1 are issued before tile t's MFMAs, written to LDS after them).
 // LDS images are XOR-swizzled so the b128 (K) and b64 (V^T) fragment reads are bank-conflict free.
+//
+// BIAS (round 10, WavLM's gated relative-position bias): score(i, j) . scale + gate[h][i] . table[h][j - i].  The [B H, T, T] bias every
+// public implementation materialises is one scalar per query row times a 1-D per-head table, so it never exists here: a lane loads
+// its query's gate once, and the workgroup stages the slice of the head's table its 128 queries can reach - offsets
+// -(q-block end) .. (last key tile's end) - q-block start, (key tiles x 64 + 127) floats, already multiplied by log2(e) - into dynamic
+// LDS behind the K / V^T buffers, once.  Entry (key j, local query iq) sits at  j + 127 - iq:  a lane reads its 16 keys of a 32-key
+// block as 16 ds_read_b32 at constant offsets from one base, and the 32 lanes of a lane half (consecutive queries) read 32
+// CONSECUTIVE dwords (descending) = 32 different banks: ds_read_b32 serves lanes 0-31 and 32-63 in one LDS cycle each with bank =
+// dword address mod 32, so the reads are conflict free at every base; the two halves (keys + 8) never share a cycle.  The biased
+// value is formed in the log2 domain (fma(s, scale log2 e, gate . table log2 e)); running maximum, deferred rescale, exp2 and the
+// dropout hash see it exactly as the plain instances see s, with the factor c of those replaced by 1.
 #include "sc_common.h"
+
+extern __shared__ __attribute__((aligned(16))) float sc_attn_bias_tab[];      // BIAS instances only (dynamic LDS: sized by the call's pitch)
 
 namespace {
 
@@ -36,7 +49,7 @@ __device__ __forceinline__ int vsw(int row) { return sc_tr_swizzle(row); }
 // of block 0 (waits for its S^T), 3 P.V of block 0 issued, 4 softmax of block 1, 5 P.V of block 1 issued, 6 closing barrier, 7 total.
 // s_memtime needs an s_waitcnt lgkmcnt(0), i.e. the LDS reads in flight at a landmark are drained there: the stamped kernel is slower
 // than the production one (tools/attn_stamps.py prints both) - the SPLIT between the sections is what it is for.
-template <int DROP, int STAMP = 0>   // DROP: train-mode probability dropout as a compile-time variant: the eval kernel carries none of its registers
+template <int DROP, int STAMP = 0, int BIAS = 0>   // DROP: train-mode probability dropout as a compile-time variant: the eval kernel carries none of its registers
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restrict__ qk, int64_t ldqk,
                                                         const uint16_t* __restrict__ vt,
                                                         const int32_t* __restrict__ valid_len,
@@ -44,7 +57,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restric
                                                         float c /* scale * log2(e) */, float* __restrict__ lse2, int causal,
                                                         float drop_p, uint32_t drop_seed, const int32_t* __restrict__ row0,
                                                         const int32_t* __restrict__ work, int npairs, int rows_total, int max_pitch,
-                                                        long long* __restrict__ stamps = nullptr) {
+                                                        long long* __restrict__ stamps = nullptr,
+                                                        const float* __restrict__ gate = nullptr /* BIAS: [H][rows_total] */,
+                                                        const float* __restrict__ table = nullptr /* BIAS: [H][2 tmax - 1] */, int tmax = 0) {
     // Round 5: two K and two V^T tile buffers (32 KiB), filled by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write)
     // one tile ahead; ONE barrier per tile.  Both images are [64 rows][128 B] with the 16-byte chunk index XOR (row >> 1) & 7 - the
     // swizzle sits in the DMA's per-lane source address.
@@ -143,6 +158,21 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restric
     if (causal) n_valid = min(n_valid, qblk * 128 + 128);           // keys beyond the block's last query are all masked
     const int ntiles = (n_valid + KT - 1) / KT;
     stage(0, 0);
+    // BIAS: cs = the factor between the values the softmax works on and the log2 domain (the plain instances keep raw scores and c)
+    const float cs = BIAS ? 1.0f : c;
+    float gate_q = 0.f;
+    const float* tab_q = nullptr;
+    if (BIAS) {
+        // the gate of this lane's query (lanes past the pitch / the last row: clamped, their result is not stored)
+        gate_q = gate[(int64_t)h * rows_total + min(r0 + qrow, rows_total - 1)];
+        // table slice of this (head, q-block): entry e = offset e - (qblk * 128 + 127); offsets the head's table does not hold (reached
+        // by masked keys and by queries past the pitch only) are clamped to its ends
+        const float* th = table + (int64_t)h * (2 * tmax - 1);
+        const int nwin = ntiles * KT + 127, d0 = tmax - 1 - (qblk * 128 + 127);
+        for (int e = tid; e < nwin; e += 256) sc_attn_bias_tab[e] = th[min(max(d0 + e, 0), 2 * tmax - 2)] * 1.4426950408889634f;
+        __syncthreads();
+        tab_q = sc_attn_bias_tab + (8 * half + 127 - (wave * 32 + l31));
+    }
     long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev = 0, st_first = 0;
 #define SC_ST(K)                                         \
     do {                                                 \
@@ -188,6 +218,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restric
             }
         }
         auto softmax_block = [&](f32x16& sv, int kbase, bf16x8 (&pf)[2]) {
+            if (BIAS) {      // register r = key kbase + (r & 7) + 8 half + 16 (r >> 3): the biased value, log2 domain
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sv[r] = fmaf(sv[r], c, gate_q * tab_q[kbase + (r & 7) + 16 * (r >> 3)]);
+            }
             // causal > 1: causal inside aligned segments of `causal` rows (32 / 64) - short sequences packed back to back into one
             // 128-row block attend to their own segment only
             if (kbase + 32 > n_valid || (causal && kbase + 31 > q0) || causal > 1) {
@@ -209,21 +243,21 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restric
             // lane of the wave needs it the rescale code runs, but a query that does not need it multiplies by exp2(0) = 1 exactly
             // and keeps its max - so a query's bits do not depend on which other queries share its wave (ragged vs padded rows)
             const float m_cand = fmaxf(m_run, mloc);
-            const bool grow = (m_cand - m_run) * c > 6.0f;
+            const bool grow = (m_cand - m_run) * cs > 6.0f;
             if (__any(grow)) {
                 const float m_new = grow ? m_cand : m_run;
-                const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
+                const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * cs);
                 l_run *= alpha;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
                 m_run = m_new;
             }
-            const float mc = m_run * c;
+            const float mc = m_run * cs;
             float psum = 0.f;
             float pv[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                pv[r] = __builtin_amdgcn_exp2f(fmaf(sv[r], c, -mc));
+                pv[r] = __builtin_amdgcn_exp2f(fmaf(sv[r], cs, -mc));
                 psum += pv[r];
             }
             l_run += psum;
@@ -301,7 +335,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restric
     const float inv = DROP ? sc_drop8_scale(drop_thr) / l_tot : 1.0f / l_tot;
     if (qrow >= R) return;                                          // lanes past the pitch: the next utterance's rows
     if (lse2 && half == 0)
-        lse2[row0 ? (int64_t)h * rows_total + r0 + qrow : ((int64_t)b * H + h) * R + qrow] = m_run * c + __builtin_amdgcn_logf(l_tot);   // log2 domain
+        lse2[row0 ? (int64_t)h * rows_total + r0 + qrow : ((int64_t)b * H + h) * R + qrow] = m_run * cs + __builtin_amdgcn_logf(l_tot);   // log2 domain
     uint16_t* op = out + ((int64_t)r0 + q0 + l31) * ldo + h * 64 + 4 * half;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -365,6 +399,75 @@ extern "C" int sc_attn_fwd_seg_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf
     else
         hipLaunchKernelGGL(attn_fwd_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, seg->max_pitch,
                            H, D, scale * 1.4426950408889634f, lse2, causal, drop_p, drop_seed, seg->row0, work, npairs, seg->rows, seg->max_pitch);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- WavLM: the same kernel with the gated relative-position bias (BIAS = 1)
+namespace {
+int relbias_check(const char* who, const float* gate, const float* table, int32_t tmax, int32_t max_pitch, int32_t causal) {
+    SC_CHECK(gate && table, "%s: null gate / table", who);
+    SC_CHECK(causal == 0, "%s: causal=%d - the relative-position bias is built without a causal mask", who, causal);
+    SC_CHECK(tmax >= max_pitch, "%s: the table holds offsets up to +-(%d - 1), the row pitch is %d", who, tmax, max_pitch);
+    // dynamic LDS behind the 32 KiB of K / V^T buffers: (key tiles x 64 + 127) floats, kept within the 64 KiB a launch gets by default
+    SC_CHECK(((max_pitch + 63) / 64 * 64 + 127) * 4 <= 32 * 1024, "%s: pitch %d needs more than 32 KiB of table", who, max_pitch);
+    return 0;
+}
+}  // namespace
+
+extern "C" int sc_attn_fwd_relbias_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
+                                        int32_t B, int32_t R, int32_t H, int32_t D, float scale, const float* gate, const float* table,
+                                        int32_t tmax, float* lse2, int32_t causal, float drop_p, uint32_t drop_seed, void* stream) {
+    SC_CHECK(qk && vt && valid_len && out, "sc_attn_fwd_relbias_bf16: null pointer");
+    SC_CHECK(B > 0 && H > 0 && R > 0 && R % 8 == 0, "sc_attn_fwd_relbias_bf16: R=%d must be a positive multiple of 8", R);
+    SC_CHECK(D == H * 64, "sc_attn_fwd_relbias_bf16: head_dim must be 64 (D=%d, H=%d)", D, H);
+    if (relbias_check("sc_attn_fwd_relbias_bf16", gate, table, tmax, R, causal)) return -1;
+    SC_CHECK((int64_t)B * R < ((int64_t)1 << 31), "sc_attn_fwd_relbias_bf16: B*R=%lld rows", (long long)B * R);
+    SC_CHECK(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || (int64_t)B * H * R * R < ((int64_t)1 << 32)),
+             "sc_attn_fwd_relbias_bf16: drop_p=%f (needs B*H*R*R < 2^32)", (double)drop_p);
+    SC_CHECK(ldqk % 8 == 0 && ldo % 4 == 0 && ldqk >= 2 * D && ldo >= D, "sc_attn_fwd_relbias_bf16: bad leading dims");
+    SC_CHECK(((uintptr_t)qk % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)out % 8) == 0, "sc_attn_fwd_relbias_bf16: alignment");
+    dim3 grid(((R + 127) / 128) * H * B);
+    const size_t lds = (size_t)((R + 63) / 64 * 64 + 127) * 4;
+    // rows_total = B R: the kernel's gate index (the uniform plain instances never read it)
+    if (drop_p > 0.f)
+        hipLaunchKernelGGL((attn_fwd_kernel<1, 0, 1>), grid, dim3(256), lds, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, R, H, D,
+                           scale * 1.4426950408889634f, lse2, 0, drop_p, drop_seed, (const int32_t*)nullptr, (const int32_t*)nullptr, 0, B * R, 0,
+                           (long long*)nullptr, gate, table, tmax);
+    else
+        hipLaunchKernelGGL((attn_fwd_kernel<0, 0, 1>), grid, dim3(256), lds, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, R, H, D,
+                           scale * 1.4426950408889634f, lse2, 0, drop_p, drop_seed, (const int32_t*)nullptr, (const int32_t*)nullptr, 0, B * R, 0,
+                           (long long*)nullptr, gate, table, tmax);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sc_attn_fwd_seg_relbias_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
+                                            const sc_segments* seg, const int32_t* work, int32_t nwork, int32_t H, int32_t D, float scale,
+                                            const float* gate, const float* table, int32_t tmax, float* lse2, int32_t causal, float drop_p,
+                                            uint32_t drop_seed, void* stream) {
+    SC_CHECK(qk && vt && valid_len && out && seg && seg->row0, "sc_attn_fwd_seg_relbias_bf16: null pointer");
+    SC_CHECK(!work || ((uintptr_t)work % 16) == 0, "sc_attn_fwd_seg_relbias_bf16: the work list must be 16-byte aligned");
+    SC_CHECK(seg->B > 0 && seg->B < 65536 && H > 0 && seg->rows > 0 && seg->max_pitch > 0 && seg->max_pitch % SC_SEG_ROWS == 0 && (!work || nwork > 0),
+             "sc_attn_fwd_seg_relbias_bf16: B=%d rows=%d max_pitch=%d", seg->B, seg->rows, seg->max_pitch);
+    SC_CHECK(D == H * 64, "sc_attn_fwd_seg_relbias_bf16: head_dim must be 64 (D=%d, H=%d)", D, H);
+    if (relbias_check("sc_attn_fwd_seg_relbias_bf16", gate, table, tmax, seg->max_pitch, causal)) return -1;
+    SC_CHECK(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || (int64_t)H * seg->rows * seg->max_pitch < ((int64_t)1 << 32)),
+             "sc_attn_fwd_seg_relbias_bf16: drop_p=%f (needs H*rows*max_pitch < 2^32)", (double)drop_p);
+    SC_CHECK(ldqk % 8 == 0 && ldo % 4 == 0 && ldqk >= 2 * D && ldo >= D, "sc_attn_fwd_seg_relbias_bf16: bad leading dims");
+    SC_CHECK(((uintptr_t)qk % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)out % 8) == 0, "sc_attn_fwd_seg_relbias_bf16: alignment");
+    const int nqb = (seg->max_pitch + 127) / 128;
+    const int npairs = work ? nwork : seg->B * nqb;
+    dim3 grid(npairs * H);
+    const size_t lds = (size_t)((seg->max_pitch + 63) / 64 * 64 + 127) * 4;
+    if (drop_p > 0.f)
+        hipLaunchKernelGGL((attn_fwd_kernel<1, 0, 1>), grid, dim3(256), lds, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, seg->max_pitch,
+                           H, D, scale * 1.4426950408889634f, lse2, 0, drop_p, drop_seed, seg->row0, work, npairs, seg->rows, seg->max_pitch,
+                           (long long*)nullptr, gate, table, tmax);
+    else
+        hipLaunchKernelGGL((attn_fwd_kernel<0, 0, 1>), grid, dim3(256), lds, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, seg->max_pitch,
+                           H, D, scale * 1.4426950408889634f, lse2, 0, drop_p, drop_seed, seg->row0, work, npairs, seg->rows, seg->max_pitch,
+                           (long long*)nullptr, gate, table, tmax);
     SC_LAUNCH_CHECK();
     return 0;
 }

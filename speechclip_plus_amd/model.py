@@ -22,7 +22,7 @@ from .clip_image import ClipImageEncoder
 from .clip_text import ClipModel
 from .head_tail import unit_rows
 from .kw_branches import KW_CascadedBranchPlus, KW_HybridBranchPlus, KW_ParallelBranch
-from .speech_encoder import FairseqSpeechEncoder_Hubert
+from .speech_encoder import FairseqSpeechEncoder_Hubert, S3prlSpeechEncoderPlus
 
 logger = logging.getLogger(__name__)
 
@@ -175,12 +175,14 @@ class KWClip_GeneralTransformer(nn.Module):
         if text_encoder is not None and text_encoder != "clip":
             raise ValueError(f"text_encoder={text_encoder!r}: 'clip' (the frozen CLIP text tower) or None")
         self.audio_encoder_type = config.audio_encoder.type
-        if self.audio_encoder_type != "FairseqHubert":
-            raise NotImplementedError(f"audio_encoder.type = {self.audio_encoder_type}: only FairseqHubert is built "
-                                      "(every shipped config uses it)")
+        # kwClip.py:59-65: "FairseqHubert" -> FairseqSpeechEncoder_Hubert, "s3prl_plus" -> S3prlSpeechEncoderPlus (the WavLM upstreams the
+        # recipes name as alternatives).  A WavLM ``name`` under FairseqHubert builds the same encoder.
+        if self.audio_encoder_type not in ("FairseqHubert", "s3prl_plus"):
+            raise NotImplementedError(f"audio_encoder.type = {self.audio_encoder_type}: FairseqHubert and s3prl_plus are built "
+                                      "(every shipped config uses one of them)")
         enc_args = {k: v for k, v in config.audio_encoder.items() if k not in ("type", "optim", "scheduler", "device")}
-        self.audio_encoder = FairseqSpeechEncoder_Hubert(device=device, state_dict=hubert_state_dict, arch=hubert_arch,
-                                                         **enc_args)
+        enc_cls = S3prlSpeechEncoderPlus if self.audio_encoder_type == "s3prl_plus" else FairseqSpeechEncoder_Hubert
+        self.audio_encoder = enc_cls(device=device, state_dict=hubert_state_dict, arch=hubert_arch, **enc_args)
         self.audio_embd_dim = self.audio_encoder.out_dim
         self.image_encoder = image_encoder
         # CLIP joint embedding width (512 ViT-B/32, 768 ViT-L/14): width of image_feat and of the branch projection

@@ -313,14 +313,32 @@ def fold_layernorm(w0: torch.Tensor, bias0: Optional[torch.Tensor], gamma: torch
 
 def attn_fwd(qk: torch.Tensor, vt: torch.Tensor, valid_len: torch.Tensor, out: torch.Tensor, B: int, R: int, H: int,
              D: int, scale: float, alg_flops: float = 0.0, lse2: Optional[torch.Tensor] = None, causal: bool = False,
-             drop_p: float = 0.0, drop_seed: int = 0, seg: Optional["RowSegments"] = None, use_work: bool = True) -> None:
-    """``seg``: ragged rows (B / R are then ignored; vt = per utterance [H, 64, pitch] back to back, as gemm_raw(seg=...) writes it)."""
+             drop_p: float = 0.0, drop_seed: int = 0, seg: Optional["RowSegments"] = None, use_work: bool = True,
+             gate: Optional[torch.Tensor] = None, table: Optional[torch.Tensor] = None) -> None:
+    """``seg``: ragged rows (B / R are then ignored; vt = per utterance [H, 64, pitch] back to back, as gemm_raw(seg=...) writes it).
+    ``gate`` [H, rows] / ``table`` [H, 2 Tmax - 1] fp32 (both or neither): WavLM's gated relative-position bias
+    gate[h, i] * table[h, Tmax - 1 + j - i] on the scaled scores (sc_attn_fwd_relbias_bf16; ``wavlm_gate`` writes the gate)."""
     assert qk.dtype == torch.bfloat16 and vt.dtype == torch.bfloat16 and out.dtype == torch.bfloat16
     assert valid_len.dtype == torch.int32
+    assert (gate is None) == (table is None), "attn_fwd: gate and table come together"
     if _timer is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    if seg is not None:
+    if gate is not None:
+        rows = seg.rows if seg is not None else B * R
+        assert gate.dtype == torch.float32 and gate.is_contiguous() and gate.shape == (H, rows), (gate.shape, H, rows)
+        assert table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2 and table.shape[0] == H and table.shape[1] % 2 == 1
+        tmax = (table.shape[1] + 1) // 2
+        if seg is not None:
+            check(lib().sc_attn_fwd_seg_relbias_bf16(_p(qk), qk.stride(0), _p(vt), _p(valid_len), _p(out), out.stride(0), seg.ref(),
+                                                     _p(seg.work) if use_work else _p(None), seg.n_work if use_work else 0, H, D, float(scale),
+                                                     _p(gate), _p(table), tmax, _p(lse2), int(causal), float(drop_p),
+                                                     int(drop_seed) & 0xffffffff, _stream()), "sc_attn_fwd_seg_relbias_bf16")
+        else:
+            check(lib().sc_attn_fwd_relbias_bf16(_p(qk), qk.stride(0), _p(vt), _p(valid_len), _p(out), out.stride(0), B, R, H, D, float(scale),
+                                                 _p(gate), _p(table), tmax, _p(lse2), int(causal), float(drop_p),
+                                                 int(drop_seed) & 0xffffffff, _stream()), "sc_attn_fwd_relbias_bf16")
+    elif seg is not None:
         check(lib().sc_attn_fwd_seg_bf16(_p(qk), qk.stride(0), _p(vt), _p(valid_len), _p(out), out.stride(0), seg.ref(),
                                          _p(seg.work) if use_work else _p(None), seg.n_work if use_work else 0, H, D, float(scale), _p(lse2),
                                          int(causal), float(drop_p), int(drop_seed) & 0xffffffff, _stream()), "sc_attn_fwd_seg_bf16")
@@ -330,7 +348,21 @@ def attn_fwd(qk: torch.Tensor, vt: torch.Tensor, valid_len: torch.Tensor, out: t
               "sc_attn_fwd_bf16")
     if _timer is not None:
         ev1.record()
-        _timer.add("attn_fwd", ev0, ev1, float(alg_flops))
+        _timer.add("attn_fwd_relbias" if gate is not None else "attn_fwd", ev0, ev1, float(alg_flops))
+
+
+def wavlm_gate(x: torch.Tensor, wg: torch.Tensor, bg: torch.Tensor, const: torch.Tensor, H: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """WavLM's gate of the relative-position bias for every (head, row) of ``x`` [rows, >= H 64] bf16 -> ``out`` [H, rows] fp32:
+    a (b const[h] - 1) + 2 with a, b = sigmoid of the two 4-sums of wg [8, 64] . x_head + bg [8] (sc_wavlm_gate_bf16)."""
+    assert x.dtype == torch.bfloat16 and x.stride(1) == 1 and x.shape[1] >= 64 * H
+    for t, n in ((wg, 512), (bg, 8), (const, H)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n, (t.shape, n)
+    rows = x.shape[0]
+    if out is None:
+        out = torch.empty(H, rows, device=x.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (H, rows)
+    check(lib().sc_wavlm_gate_bf16(_p(x), x.stride(0), _p(wg), _p(bg), _p(const), _p(out), rows, H, _stream()), "sc_wavlm_gate_bf16")
+    return out
 
 
 def head_transpose(x: torch.Tensor, B: int, R: int, H: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -59,6 +59,10 @@ class HubertArch:
     dropout_input: float = 0.1         # on post_extract_proj's output
     feature_grad_mult: float = 0.1     # fairseq GradMultiply on the conv extractor's output (hubert_base_librispeech.yaml: 0.1;
                                        # hubert_large_librivox.yaml: 1.0); acts only on the backward of a fully trainable encoder
+    # WavLM (microsoft/unilm wavlm/WavLM.py WavLMConfig: relative_position_embedding + gru_rel_pos): buckets of the relative-position
+    # bias, 0 = HuBERT (no bias); offsets beyond max_distance share the last bucket of their sign
+    rel_pos_buckets: int = 0
+    rel_pos_max_distance: int = 800
 
 
 ARCHS = {
@@ -69,6 +73,19 @@ ARCHS = {
                                      attention_dropout=0.0, activation_dropout=0.0, dropout_input=0.0,
                                      feature_grad_mult=1.0),
 }
+# WavLM = the HuBERT stack + the gated relative-position bias in every layer's attention scores (num_buckets 320, max_distance 800,
+# bias embedding on layer 0, shared by all layers).  Dropouts: the ``cfg`` dict stored in the released checkpoints (WavLM-Base.pt /
+# WavLM-Base+.pt / WavLM-Large.pt - what s3prl's wavlm upstream builds its WavLMConfig from): base and base+ dropout 0.1,
+# attention_dropout 0.1, activation_dropout 0.0, dropout_input 0.1, feature_grad_mult 0.1; large all 0.0, feature_grad_mult 1.0,
+# normalize true - the HuBERT base / large recipes they were trained from.  (transformers' microsoft/wavlm-* config.json carry the
+# WavLMConfig defaults instead - 0.1 everywhere - because the conversion script does not read the checkpoint's cfg.)
+# encoder_layerdrop (0.05 in the base checkpoints) is not applied: see docs/rounds/r10_wavlm.md.
+ARCHS["wavlm_base"] = HubertArch(rel_pos_buckets=320)
+ARCHS["wavlm_base_plus"] = HubertArch(rel_pos_buckets=320)
+ARCHS["wavlm_large"] = HubertArch(embed_dim=1024, ffn_dim=4096, layers=24, heads=16, extractor_mode="layer_norm", conv_bias=True,
+                                  layer_norm_first=True, normalize_wav=True, dropout=0.0, attention_dropout=0.0, activation_dropout=0.0,
+                                  dropout_input=0.0, feature_grad_mult=1.0, rel_pos_buckets=320)
+WAVLM_NAMES = ("wavlm_base", "wavlm_base_plus", "wavlm_large")
 
 
 def conv_out_lengths(L: int, arch: HubertArch) -> List[int]:
@@ -148,6 +165,87 @@ def random_hubert_state_dict(arch: HubertArch, seed: int = 7122) -> Dict[str, to
         W[p + "fc2.bias"] = randn(D, s=0.05)
         norm(p + "final_layer_norm", D)
     return W
+
+
+def random_wavlm_state_dict(arch: HubertArch, seed: int = 7122) -> Dict[str, torch.Tensor]:
+    """``random_hubert_state_dict`` + WavLM's attention extras under the unilm / s3prl key names: per layer grep_linear [8, 64] / [8]
+    and grep_a [1, H, 1, 1], on layer 0 relative_attention_bias [buckets, H] (N(0, 1) as nn.Embedding initialises it)."""
+    assert arch.rel_pos_buckets > 0
+    W = random_hubert_state_dict(arch, seed)
+    g = torch.Generator(device="cpu").manual_seed(seed + 1)
+    dh = arch.embed_dim // arch.heads
+    for i in range(arch.layers):
+        p = f"encoder.layers.{i}.self_attn."
+        W[p + "grep_linear.weight"] = torch.randn(8, dh, generator=g) * dh ** -0.5
+        W[p + "grep_linear.bias"] = torch.randn(8, generator=g) * 0.1
+        W[p + "grep_a"] = 1.0 + 0.3 * torch.randn(1, arch.heads, 1, 1, generator=g)
+    W["encoder.layers.0.self_attn.relative_attention_bias.weight"] = torch.randn(arch.rel_pos_buckets, arch.heads, generator=g)
+    return W
+
+
+# The ONE key map (INTEGRATION.md "WavLM weights"): transformers' WavLMModel names -> the unilm / s3prl (fairseq-style) names
+# ``_load_weights`` reads.  Regular expressions, applied to whole keys; keys that match none pass through unchanged.
+WAVLM_HF_KEY_MAP = (
+    (r"^(?:wavlm\.)?feature_extractor\.conv_layers\.(\d+)\.conv\.(weight|bias)$", r"feature_extractor.conv_layers.\1.0.\2"),
+    (r"^(?:wavlm\.)?feature_extractor\.conv_layers\.(\d+)\.layer_norm\.(weight|bias)$", "feature_extractor.conv_layers.\\1.{norm}.\\2"),
+    (r"^(?:wavlm\.)?feature_projection\.layer_norm\.(weight|bias)$", r"layer_norm.\1"),
+    (r"^(?:wavlm\.)?feature_projection\.projection\.(weight|bias)$", r"post_extract_proj.\1"),
+    (r"^(?:wavlm\.)?encoder\.pos_conv_embed\.conv\.bias$", "encoder.pos_conv.0.bias"),
+    (r"^(?:wavlm\.)?encoder\.pos_conv_embed\.conv\.(?:parametrizations\.weight\.original0|weight_g)$", "encoder.pos_conv.0.weight_g"),
+    (r"^(?:wavlm\.)?encoder\.pos_conv_embed\.conv\.(?:parametrizations\.weight\.original1|weight_v)$", "encoder.pos_conv.0.weight_v"),
+    (r"^(?:wavlm\.)?encoder\.layer_norm\.(weight|bias)$", r"encoder.layer_norm.\1"),
+    (r"^(?:wavlm\.)?encoder\.layers\.(\d+)\.attention\.(q_proj|k_proj|v_proj|out_proj)\.(weight|bias)$", r"encoder.layers.\1.self_attn.\2.\3"),
+    (r"^(?:wavlm\.)?encoder\.layers\.(\d+)\.attention\.gru_rel_pos_linear\.(weight|bias)$", r"encoder.layers.\1.self_attn.grep_linear.\2"),
+    (r"^(?:wavlm\.)?encoder\.layers\.(\d+)\.attention\.gru_rel_pos_const$", r"encoder.layers.\1.self_attn.grep_a"),
+    (r"^(?:wavlm\.)?encoder\.layers\.(\d+)\.attention\.rel_attn_embed\.weight$", r"encoder.layers.\1.self_attn.relative_attention_bias.weight"),
+    (r"^(?:wavlm\.)?encoder\.layers\.(\d+)\.layer_norm\.(weight|bias)$", r"encoder.layers.\1.self_attn_layer_norm.\2"),
+    (r"^(?:wavlm\.)?encoder\.layers\.(\d+)\.feed_forward\.intermediate_dense\.(weight|bias)$", r"encoder.layers.\1.fc1.\2"),
+    (r"^(?:wavlm\.)?encoder\.layers\.(\d+)\.feed_forward\.output_dense\.(weight|bias)$", r"encoder.layers.\1.fc2.\2"),
+    (r"^(?:wavlm\.)?encoder\.layers\.(\d+)\.final_layer_norm\.(weight|bias)$", r"encoder.layers.\1.final_layer_norm.\2"),
+)
+
+
+def wavlm_state_dict_keys(sd: Dict[str, torch.Tensor], arch: HubertArch) -> Dict[str, torch.Tensor]:
+    """A WavLM state dict under either naming -> the unilm / s3prl names (``WAVLM_HF_KEY_MAP``; unilm keys pass through).  The
+    extractor's norm sits at index 2 (GroupNorm of conv 0, "default" mode) or 2.1 (LayerNorm of every conv, "layer_norm" mode) of
+    fairseq's conv block."""
+    import re
+    norm = "2.1" if arch.extractor_mode == "layer_norm" else "2"
+    rules = [(re.compile(a), b.format(norm=norm) if "{norm}" in b else b) for a, b in WAVLM_HF_KEY_MAP]
+    out = {}
+    for k, v in sd.items():
+        for rx, to in rules:
+            if rx.match(k):
+                k = rx.sub(to, k)
+                break
+        out[k] = v
+    return out
+
+
+def wavlm_bucket_index(T: int, num_buckets: int = 320, max_distance: int = 800) -> torch.Tensor:
+    """Bucket of every offset j - i in -(T - 1) .. T - 1 (int64 [2 T - 1]) - WavLM's ``_relative_positions_bucket``, bidirectional:
+    num_buckets / 2 per sign, exact below a quarter of them, logarithmic up to ``max_distance``, clamped to the sign's last bucket.
+    The SAME fp32 torch expression as transformers' WavLMAttention (and unilm's MultiheadAttention): the bucket is a discrete
+    decision, a second ``log`` implementation could put an offset on the other side of a boundary."""
+    rel = torch.arange(-(T - 1), T, dtype=torch.long)
+    nb = num_buckets // 2
+    buckets = (rel > 0).to(torch.long) * nb
+    rel = torch.abs(rel)
+    max_exact = nb // 2
+    is_small = rel < max_exact
+    large = torch.log(rel.float() / max_exact)
+    large = large / math.log(max_distance / max_exact)
+    large = large * (nb - max_exact)
+    large = (max_exact + large).to(torch.long)
+    large = torch.min(large, torch.full_like(large, nb - 1))
+    return buckets + torch.where(is_small, rel, large)
+
+
+def wavlm_bias_table(rel_embed: torch.Tensor, T: int, num_buckets: int = 320, max_distance: int = 800) -> torch.Tensor:
+    """[H, 2 T - 1] fp32: entry T - 1 + (j - i) of row h = position_bias[h, i, j] of layer 0's relative_attention_bias /
+    rel_attn_embed ``rel_embed`` [num_buckets, H] - the 1-D table the attention kernel reads instead of the [H, T, T] matrix."""
+    idx = wavlm_bucket_index(T, num_buckets, max_distance).to(rel_embed.device)
+    return rel_embed.float().index_select(0, idx).t().contiguous()
 
 
 _USE_GRAPH = os.environ.get("SC_ENCODER_GRAPH", "0") == "1"      # opt-in: measured +-0 on one GPU (DESIGN.md section 7)
@@ -275,6 +373,12 @@ class _Plan:
             self._seg_cache = (key, ops.RowSegments(pitch, keys, device, keys_known=keys_known))
         return self._seg_cache[1]
 
+    def gate_rows(self, H: int, M: int) -> torch.Tensor:
+        """WavLM: the [H, M] fp32 gate of the relative-position bias for the batch in flight (a view of one capacity-sized buffer)"""
+        if getattr(self, "_gate", None) is None:
+            self._gate = torch.zeros(H * self.B * self.R, device=self.hidden.device, dtype=torch.float32)
+        return self._gate[: H * M].view(H, M)
+
     def release(self) -> None:
         """Called by the backward that read this plan's resident buffers last (weighted_sum / head_tail), on the stream it ran on:
         from the recorded event on, the encoder stream may overwrite them."""
@@ -299,7 +403,15 @@ class _Plan:
 
 
 class FairseqSpeechEncoder_Hubert(nn.Module):
-    MODEL_DOWNSAMPLE_RATE = {"hubert": 320, "hubert_base": 320, "hubert_large_ll60k": 320}
+    MODEL_DOWNSAMPLE_RATE = {"hubert": 320, "hubert_base": 320, "hubert_large_ll60k": 320,
+                             "wavlm_base": 320, "wavlm_base_plus": 320, "wavlm_large": 320}
+    WAVLM_REASONS = {
+        "trainable": "WavLM is built as a FROZEN encoder, forward only (every shipped recipe freezes the audio encoder): trainable / "
+                     "reinit_layers / unfreeze_layers would need the backward of the biased attention and of the gate, which do not exist",
+        "split": "eval_weights='split' is not built for WavLM: the gate reads the bf16 rows of the bf16 path and has no split form",
+        "fused_ln": "SC_FUSED_LN=1 (the LayerNorm-folded opt-in path) is not built for WavLM: its layers run op by op with the gate "
+                    "kernel between the QKV GEMM and the attention",
+    }
 
     def __init__(self, name: str = "hubert", pretrained: bool = False, trainable: bool = False, device: str = "cuda",
                  feat_select_idx: Union[str, list] = "all", layer_drop: Union[str, float] = 0.0, max_audio_len: int = -1,
@@ -324,6 +436,14 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
         self._train_ids = train_ids
         assert self.arch.extractor_mode in ("default", "layer_norm"), self.arch.extractor_mode
         assert self.arch.embed_dim == self.arch.heads * 64, "the attention kernel is built for head_dim 64"
+        self._wavlm = self.arch.rel_pos_buckets > 0
+        if self._wavlm:
+            if trainable or train_ids:
+                raise NotImplementedError(self.WAVLM_REASONS["trainable"])
+            if eval_weights == "split":
+                raise NotImplementedError(self.WAVLM_REASONS["split"])
+            if _FUSED_LN:
+                raise NotImplementedError(self.WAVLM_REASONS["fused_ln"])
         if not (isinstance(layer_drop, float) and layer_drop == 0.0) and layer_drop != "original":
             raise ValueError(f"layer_drop = {layer_drop} is not supported.")
         self.feat_select_idx = feat_select_idx
@@ -359,8 +479,8 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
         self.eval_weights = eval_weights
         if state_dict is None:
             if pretrained:
-                logger.warning("no checkpoint available offline: HuBERT weights are seeded random (seed %d)", seed)
-            state_dict = random_hubert_state_dict(self.arch, seed)
+                logger.warning("no checkpoint available offline: %s weights are seeded random (seed %d)", "WavLM" if self._wavlm else "HuBERT", seed)
+            state_dict = random_wavlm_state_dict(self.arch, seed) if self._wavlm else random_hubert_state_dict(self.arch, seed)
         self._load_weights(state_dict)
         self.train_layers = None
         if train_ids:
@@ -391,6 +511,8 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
         a, dev = self.arch, self._dev
         bf = lambda t: t.detach().to(device=dev, dtype=torch.bfloat16).contiguous()
         f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if a.rel_pos_buckets > 0:
+            sd = wavlm_state_dict_keys(sd, a)           # transformers names -> unilm / s3prl names (WAVLM_HF_KEY_MAP)
         if "encoder.pos_conv.0.weight" not in sd:
             g, v = sd["encoder.pos_conv.0.weight_g"], sd["encoder.pos_conv.0.weight_v"]
             pos_w = g * v / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()     # weight_norm(dim=2)
@@ -430,7 +552,14 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
             w[f"l{i}_fc1_w"], w[f"l{i}_fc1_b"] = bf(sd[p + "fc1.weight"]), f32(sd[p + "fc1.bias"])
             w[f"l{i}_fc2_w"], w[f"l{i}_fc2_b"] = bf(sd[p + "fc2.weight"]), f32(sd[p + "fc2.bias"])
             w[f"l{i}_ln2_g"], w[f"l{i}_ln2_b"] = f32(sd[p + "final_layer_norm.weight"]), f32(sd[p + "final_layer_norm.bias"])
-        if not a.layer_norm_first:
+            if a.rel_pos_buckets > 0:           # the gate of the relative-position bias: its own projection and constant per layer
+                w[f"l{i}_gate_w"], w[f"l{i}_gate_b"] = f32(sd[p + "self_attn.grep_linear.weight"]), f32(sd[p + "self_attn.grep_linear.bias"])
+                w[f"l{i}_gate_c"] = f32(sd[p + "self_attn.grep_a"].reshape(-1))
+                assert w[f"l{i}_gate_w"].shape == (8, 64) and w[f"l{i}_gate_c"].numel() == a.heads
+        if a.rel_pos_buckets > 0:               # layer 0 owns the bucket embedding, every layer adds the same (differently gated) bias
+            w["rel_embed"] = f32(sd["encoder.layers.0.self_attn.relative_attention_bias.weight"])
+            assert w["rel_embed"].shape == (a.rel_pos_buckets, a.heads), w["rel_embed"].shape
+        if not a.layer_norm_first and a.rel_pos_buckets == 0:
             # LayerNorm folded into the consumer GEMM (csrc/gemm256_bf16.hip "LN"): W' = W diag(gamma) in bf16, s_n = sum_k W'[n,k] (of
             # the bf16 values the kernel multiplies), c_n = sum_k beta_k W[n,k] + b_n; fc1 with the layer's own LN1, QKV of layer i >= 1
             # with layer i - 1's final LayerNorm
@@ -465,6 +594,8 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
         if mode not in ("bf16", "split"):
             raise ValueError(f"eval_weights = {mode!r}: 'bf16' or 'split'")
         if mode == "split":
+            if self.arch.rel_pos_buckets > 0:
+                raise NotImplementedError(self.WAVLM_REASONS["split"])
             if self.trainable or self._train_ids:
                 raise NotImplementedError(self.SPLIT_REASONS["trainable"])
             if _FUSED_LN:
@@ -892,11 +1023,19 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
         alg_M = pl.alg_rows_l[-1] if seg is not None else B * T                       # rows / flops that are algorithmic work
         alg_att = pl.alg_attn_flops if seg is not None else 4.0 * B * T * T * D
 
+        # WavLM: the layers run op by op (no one-call driver) - QKV GEMM, the gate of the relative-position bias from the same input
+        # rows, attention with gate x table added to the scores; the table [H, 2 R - 1] is the plan's (built once, _rel_table)
+        wavlm = a.rel_pos_buckets > 0
+        per_op = ops._timer is not None or wavlm
+        bias = dict(gate=pl.gate_rows(H, M), table=self._rel_table(pl, w)) if wavlm else {}
+
         def qkv_attn(x, i):
             ops.gemm_raw(x, D, w[f"l{i}_qkv_w"], 2 * D if split else D, pl.qk, 2 * D, M, 3 * D, D, bias=w[f"l{i}_qkv_b"], Ct=pl.vt,
                          n_split=2 * D, R=R, dh=D // H, alg_rows=alg_M, seg=seg, a_rep=a_rep)
+            if wavlm:
+                ops.wavlm_gate(x, w[f"l{i}_gate_w"], w[f"l{i}_gate_b"], w[f"l{i}_gate_c"], H, out=bias["gate"])
             ops.attn_fwd(pl.qk, pl.vt, pl.valid, pl.ctx, B, R, H, D, scale, alg_flops=alg_att,
-                         drop_p=p_att, drop_seed=sd(3 * i + 2), seg=seg)
+                         drop_p=p_att, drop_seed=sd(3 * i + 2), seg=seg, **bias)
 
         if not a.layer_norm_first:
             # a5: post-LN layers (base): x = LN1(x + attn(x)); x = LN2(x + ffn(x))       (:39-40, :49-53)
@@ -918,7 +1057,7 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
                     tl.layer_forward(i, x, pl.hidden[i + 1], pl, save,
                                      drops=(p_res, p_att, sd(3 * i + 2), sd(3 * i + 3), sd(3 * i + 4)) if seeds else None)
                     continue
-                if ops._timer is None:          # one C-ABI call per frozen layer (sc_hubert_layer_fwd); the per-op path below is
+                if not per_op:                  # one C-ABI call per frozen layer (sc_hubert_layer_fwd); the per-op path below is
                     ops.hubert_layer_fwd(x, pl.hidden[i + 1], pl.valid, w, i, pl, B, R, T, D, F, H, False, p_att, p_res,
                                          (sd(3 * i + 2), sd(3 * i + 3), sd(3 * i + 4)), seg=seg, w_split=split)   # kept for bench.py's per-kernel timer
                     continue
@@ -949,7 +1088,7 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
                     tl.layer_forward(i, x, pl.hidden[i + 1], pl, save,
                                      drops=(p_res, p_att, sd(3 * i + 2), sd(3 * i + 3), sd(3 * i + 4)) if seeds else None)
                     continue
-                if ops._timer is None:
+                if not per_op:
                     ops.hubert_layer_fwd(x, pl.hidden[i + 1], pl.valid, w, i, pl, B, R, T, D, F, H, True, p_att, p_res,
                                          (sd(3 * i + 2), sd(3 * i + 3), sd(3 * i + 4)), seg=seg, w_split=split)
                     continue
@@ -961,6 +1100,19 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
                 ops.linear_bf16(pl.x1, w[f"l{i}_fc1_w"], w[f"l{i}_fc1_b"], out=pl.ffn, act=1, alg_rows=alg_M, a_rep=a_rep)
                 ops.linear_bf16(pl.ffn, w[f"l{i}_fc2_w"], w[f"l{i}_fc2_b"], out=pl.hidden[i + 1], residual=pl.pre,
                                 alg_rows=alg_M, drop_p=p_res, drop_seed=sd(3 * i + 4), a_rep=a_rep)
+            if wavlm:
+                # unilm's TransformerEncoder.forward normalises its OUTPUT with encoder.layer_norm in the pre-LN order, and s3prl's
+                # wavlm upstream takes the last hidden state from there (hooks: every layer's input + the encoder's output);
+                # transformers' WavLMEncoderStableLayerNorm does the same.  (HuBERT above: the reference reads layer_results, un-normalised)
+                ops.layernorm_bf16(pl.hidden[a.layers], w["ln_enc_g"], w["ln_enc_b"], out=pl.hidden[a.layers])
+
+    def _rel_table(self, pl, w) -> torch.Tensor:
+        """WavLM: the [H, 2 R - 1] table of the plan (R = its largest pitch, so every offset a batch of this plan can form is in it),
+        gathered once per plan from layer 0's bucket embedding - not per layer, not per forward; a plan for longer batches builds its own"""
+        if getattr(pl, "_rel_tab", None) is None or pl._rel_tab[0] is not w["rel_embed"]:
+            a = self.arch
+            pl._rel_tab = (w["rel_embed"], wavlm_bias_table(w["rel_embed"], pl.R, a.rel_pos_buckets, a.rel_pos_max_distance))
+        return pl._rel_tab[1]
 
     @torch.no_grad()
     def _layers_fused(self, pl, w, sd, p_res, p_att, scale) -> None:
@@ -1136,3 +1288,24 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
         if return_hidden_states:
             return_list.append(feat["hidden_states"])
         return tuple(return_list)
+
+
+class S3prlSpeechEncoderPlus(FairseqSpeechEncoder_Hubert):
+    """Host-side mirror of the reference's ``S3prlSpeechEncoderPlus`` (avssl/module/speech_encoder_plus.py:110-316, chosen by
+    ``audio_encoder.type: s3prl_plus``) for the upstreams this library runs: wavlm_base, wavlm_base_plus, wavlm_large.  Same
+    constructor keywords, same ``forward(wav, wav_len, feat_select_idx, return_hidden_states)`` returns, ``out_dim``,
+    ``downsample_rate`` (320, what the upstream's get_downsample_rates gives), ``upstream_model_hiddenstates_len`` and
+    ``trainable_params()``.  It IS the frozen encoder above with a WavLM arch: s3prl's upstream pads the batch, masks by the same
+    chunk rule, and collects every layer's input plus the encoder's output - the 13 / 25 states ``forward`` hands out here.
+    Differences, all raised or documented: frozen only; s3prl's default device "cpu" does not exist here (HIP kernels only)."""
+
+    def __init__(self, name: str, pretrained: bool = False, trainable: bool = False, device: str = "cuda",
+                 feat_select_idx: Union[str, list] = "all", layer_drop: Union[str, float] = 0.0, max_audio_len: int = -1,
+                 reinit_layers: List[int] = [], unfreeze_layers: List[int] = [], **kwargs):
+        if name not in WAVLM_NAMES:
+            raise NotImplementedError(f"s3prl upstream {name!r}: S3prlSpeechEncoderPlus is built for {', '.join(WAVLM_NAMES)} (the alternatives the "
+                                      "SpeechCLIP+ recipes name); HuBERT runs as audio_encoder.type FairseqHubert, other s3prl upstreams "
+                                      "(wav2vec2, data2vec, ...) have no kernels here")
+        # (the reference applies layer_drop to names that start with "hubert" only; for WavLM it is ignored there too)
+        super().__init__(name=name, pretrained=pretrained, trainable=trainable, device=device, feat_select_idx=feat_select_idx,
+                         layer_drop=0.0, max_audio_len=max_audio_len, reinit_layers=reinit_layers, unfreeze_layers=unfreeze_layers, **kwargs)
