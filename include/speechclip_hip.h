@@ -795,6 +795,32 @@ int sc_vit_embed_ln_bf16(const float* G, const float* cls, const float* pos, con
                          const sc_segments* seg, int32_t tokens, int32_t W, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Raw-image input of the CLIP image tower: CLIP's preprocessing on the device - bicubic Resize(S) of a PIL image, CenterCrop(S),
+ * ToTensor, Normalize (ClipModel.prep_image, avssl/module/clip_official.py:153-166; the data sets' clip_image_transform,
+ * avssl/data/base_dataset.py:93-106), S = 224.  Pillow's 8-bit resampling restated exactly: per pass and output
+ *     clip8((2^21 + sum_t pixel[first + t] * k[t]) >> 22)      int32 accumulation, arithmetic shift, clip to 0 .. 255
+ * with 22-bit fixed-point coefficients, the horizontal pass first, a uint8 intermediate image, then the vertical pass.  The sources are
+ * B images of unequal sizes in one byte buffer (image b: [h_b][w_b][3] uint8 at its offset); geometry, tap bounds and coefficients are
+ * host-built (speechclip_plus_amd/image_prep.py).  Tables, in one int32 buffer `tab`:
+ *   desc   [B][8] int64: source byte offset, source width (pixels), intermediate byte offset, intermediate rows, first source row of the
+ *          intermediate, horizontal table, vertical table (offsets into tab, int32 units), ksize_h | ksize_v << 32
+ *   table  bounds [S][2] int32 (first tap, tap count <= ksize) then coef [S][ksize] int32, for the S columns / rows of the crop window;
+ *          vertical firsts are relative to the intermediate's first row.  A pass Pillow skips (equal sizes) is the one-tap table k = 2^22.
+ * The kernels reach src and mid only through the tables and skip any access the tables would place outside src_bytes / mid_bytes.
+ *   sc_image_resample_h_u8:   mid [rows_b][S][3] uint8 per image <- the horizontal pass over the S crop columns of the source rows the
+ *       crop window's vertical pass reads.  max_rows = max_b rows_b (grid sizing).
+ *   sc_image_resample_v_norm: the vertical pass over mid, then the look-up in lut [3][256] fp32 (channel, byte value).  Two optional
+ *       outputs, NULL = not wanted, at least one: out fp32 [B][3][S][S], and A [seg.rows][Kp] bf16, the patch GEMM's operand in the
+ *       layout and rounding of sc_vit_patchify_bf16 (pad columns, class and pad rows zero, every element written); A needs seg, P even
+ *       dividing S, Kp as there, and every image's pitch >= 1 + (S / P)^2.
+ * S even, <= 256.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_image_resample_h_u8(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int32_t* tab, uint8_t* mid, int64_t mid_bytes,
+                           int32_t B, int32_t max_rows, int32_t S, void* stream);
+int sc_image_resample_v_norm(const uint8_t* mid, int64_t mid_bytes, const int64_t* desc, const int32_t* tab, const float* lut, float* out,
+                             sc_bf16* A, int32_t Kp, const sc_segments* seg, int32_t P, int32_t B, int32_t S, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser step on a flat fp32 parameter buffer: torch.optim.Adam semantics (L2 weight decay added to
  * the gradient), gradient clipping by global norm folded in (avssl/model/kwClip.py:646-674 +
  * trainer.gradient_clip_val).  sumsq: partial sums of squares for the global norm.

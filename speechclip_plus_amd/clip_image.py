@@ -14,6 +14,10 @@ patchify (csrc/vit.hip) -> patch GEMM (sc_gemm_bf16, fp32 out) -> class / positi
 sc_hubert_layer_fwd per block (pre_ln = 1, ffn_act = 2: QuickGELU in the fc1 epilogue) over the images' ragged rows -> the class
 rows (sc_rows_gather_bf16) -> ln_post (fp32 row LayerNorm) -> ``@ proj`` (exact-fp32 matrix-pipe GEMM).  The nn modules are
 parameter containers with no arithmetic of their own: there is no stock-op or CPU path.
+
+Raw images (a list of uint8 [H, W, 3] images of any size, or a packed ragged batch) are accepted wherever pixels are: CLIP's
+resize + centre crop + normalise (ClipModel.prep_image, clip_official.py:153-166) runs on the device (image_prep.py,
+csrc/image_prep.hip) and writes the patch GEMM's operand directly; ``prep_image`` returns the fp32 pixels themselves.
 """
 from types import SimpleNamespace
 
@@ -164,22 +168,68 @@ class ClipImageEncoder(nn.Module):
         if not images.is_cuda:
             raise RuntimeError("the CLIP image tower runs on the HIP kernels: device tensors only")
 
+    # ------------------------------------------------------------------------------------------------ raw images
+    @staticmethod
+    def _is_raw(images) -> bool:
+        from .image_prep import RawImageBatch
+        return isinstance(images, (list, tuple, RawImageBatch))
+
+    def _raw(self, images):
+        """list of raw images / (packed, image_hw) pair / RawImageBatch -> what image_prep.run takes, validated before any launch"""
+        from . import image_prep
+        if self.resolution != image_prep.N_PX:
+            raise ValueError(f"raw-image input is CLIP's {image_prep.N_PX} x {image_prep.N_PX} preprocessing, this tower takes {self.resolution}")
+        if isinstance(images, image_prep.RawImageBatch):
+            raw = images
+        elif isinstance(images, tuple) and len(images) == 2 and isinstance(images[0], torch.Tensor) and images[0].dim() == 1:
+            raw = image_prep.RawImageBatch(images[0], images[1])
+        else:
+            raw = image_prep.as_entries(images)
+        dev = self.positional_embedding.device
+        if dev.type != "cuda":
+            raise RuntimeError("the CLIP image tower runs on the HIP kernels: move it to the device first (raw images are resized there)")
+        return raw, dev
+
+    def prep_image(self, images) -> torch.Tensor:
+        """ClipModel.prep_image (avssl/module/clip_official.py:153-166): a list of raw images - uint8 [H, W, 3] tensors (host or device),
+        numpy arrays, PIL images (any mode: converted to RGB) or paths - or a packed raw batch (image_prep.RawImageBatch) -> fp32
+        [B, 3, 224, 224] on the device: bicubic resize of the shorter side to 224, centre crop, /255, normalise, bit for bit what
+        Pillow + torch give on the host (csrc/image_prep.hip).  No device synchronisation."""
+        from . import image_prep
+        raw, dev = self._raw(images)
+        with torch.no_grad():
+            return image_prep.run(raw, dev, pixels=True)[0]
+
     # ------------------------------------------------------------------------------------------------ forward
-    def encode_hidden(self, images: torch.Tensor):
+    def encode_hidden(self, images):
         """-> (X [B * pitch, W] bf16: the last block's output rows in the segment layout, segments).  Row b * pitch is image b's class
-        token, rows b * pitch + 1 .. + g^2 its patches."""
+        token, rows b * pitch + 1 .. + g^2 its patches.  ``images``: normalised pixels [B, 3, S, S] on the device, or raw images (as
+        prep_image takes them): those go raw -> the patch GEMM's operand directly, the fp32 image is never formed."""
         from . import ops
-        from ._lib import lib
+        if self._is_raw(images):
+            from . import image_prep
+            raw, dev = self._raw(images)
+            B = len(raw)
+            seg, _ = self.segments(B, dev)
+            A = image_prep.run(raw, dev, pixels=False, seg=seg, patch=self.patch, Kp=self.Kp)[1]
+            return self._encode_patches(A, B, dev)
         self.check_images(images)
         dev = images.device
-        B, W, F = images.shape[0], self.width, 4 * self.width
         x = images if images.dtype == torch.float32 else images.float()
         if x.stride(3) != 1:
             x = x.contiguous()
+        seg, _ = self.segments(images.shape[0], dev)
+        A = ops.vit_patchify(x, seg, self.patch, self.Kp)
+        return self._encode_patches(A, images.shape[0], dev)
+
+    def _encode_patches(self, A: torch.Tensor, B: int, dev):
+        """the tower from the patch GEMM's operand A [seg.rows, Kp] bf16 on"""
+        from . import ops
+        from ._lib import lib
+        W, F = self.width, 4 * self.width
         w = self._weights(dev)
         seg, valid_len = self.segments(B, dev)
         rows = seg.rows
-        A = ops.vit_patchify(x, seg, self.patch, self.Kp)
         G = torch.empty(rows, W, device=dev, dtype=torch.float32)
         ops.gemm_raw(A, self.Kp, w["conv1"], self.Kp, G, W, rows, W, self.Kp, out_f32=True)
         X = ops.vit_embed_ln(G, w["cls"], w["pos"], w["ln_pre_g"], w["ln_pre_b"], seg)
@@ -196,12 +246,13 @@ class ClipImageEncoder(nn.Module):
             X, Y = Y, X
         return X, seg
 
-    def forward(self, images: torch.Tensor) -> torch.Tensor:
-        """[B, 3, S, S] normalised pixels on the device -> fp32 [B, E] image embeddings (not normalised, as encode_image)"""
+    def forward(self, images) -> torch.Tensor:
+        """[B, 3, S, S] normalised pixels on the device, or raw images (a list / packed raw batch, as prep_image takes them) -> fp32
+        [B, E] image embeddings (not normalised, as encode_image)"""
         from . import ops
         with torch.no_grad():
             X, seg = self.encode_hidden(images)
-            w = self._weights(images.device)
+            w = self._weights(X.device)
             cls_rows = ops.rows_gather(X, seg.row0[: seg.B])
             y, _, _ = ops.rowln_fwd(cls_rows, None, 0, w["ln_post_g"], w["ln_post_b"], self.ln_post.eps)
             return ops.sgemm_mfma(y, w["proj"], b_kmajor=True)

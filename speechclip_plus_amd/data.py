@@ -2,7 +2,9 @@
 ``KWClip_GeneralTransformer.forward`` consumes - mirror of avssl/data/collate_function.py:7-36.
 
 Semantics kept: a ``wav_len`` key is derived from the un-padded waveforms, ``wav`` is zero-padded to the longest
-utterance of the batch (batch first), other tensors are stacked, non-tensor fields (ids, lengths) become int64 tensors.
+utterance of the batch (batch first), other tensors are stacked, non-tensor fields (ids, lengths) become int64 tensors.  One
+addition: an ``image`` column of raw ``uint8 [H, W, 3]`` tensors of UNEQUAL sizes (which the reference's stack refuses) is packed into
+``image`` (1-D uint8) + ``image_hw`` (int64 [B, 2], with a host twin) for the device-side CLIP preprocessing (image_prep.py).
 
 Round 5 - the way a batch reaches the device (avssl/model/kwClip.py:145-147 receives what Lightning's transfer produced):
 ``transfer_batch_to_device`` is the body of the LightningModule hook of the same name.  It keeps what a plain ``.to(device)`` of
@@ -44,6 +46,8 @@ def transfer_batch_to_device(batch: dict, device, copy_stream: Optional["torch.c
         device = torch.device("cuda", torch.cuda.current_device())
     if device.type != "cuda":
         out = {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
+        if isinstance(batch.get("image_hw"), torch.Tensor):
+            _keep_sizes(out["image_hw"], batch["image_hw"])
         if isinstance(batch.get("wav_len"), torch.Tensor):
             host = getattr(batch["wav_len"], "_sc_host", None) or (batch["wav_len"].tolist() if not batch["wav_len"].is_cuda else None)
             if host is not None:
@@ -63,11 +67,15 @@ def transfer_batch_to_device(batch: dict, device, copy_stream: Optional["torch.c
                     out[k] = v.to(device, non_blocking=True)
                 if k == "wav_len" and getattr(v, "_sc_host", None) is not None:
                     attach_host_lengths(out[k], v._sc_host)
+                if k == "image_hw":
+                    _keep_sizes(out[k], v)
                 continue
             src = v if v.is_pinned() else v.pin_memory()
             d = src.to(device, non_blocking=True)
             if k == "wav_len":
                 attach_host_lengths(d, getattr(v, "_sc_host", None) or v.tolist())
+            if k == "image_hw":
+                _keep_sizes(d, v)
             out[k] = d
             moved.append(d)                    # host -> device copies only: these are what the event stands for
         ev = torch.cuda.Event()
@@ -79,6 +87,20 @@ def transfer_batch_to_device(batch: dict, device, copy_stream: Optional["torch.c
         if isinstance(out.get("wav"), torch.Tensor) and any(d is out["wav"] for d in moved):
             out["wav"]._sc_ready = ev
     return out
+
+
+def _keep_sizes(moved: torch.Tensor, image_hw: torch.Tensor) -> None:
+    """the host twin of ``image_hw`` (the raw images' sizes: the resize tables are host decisions) follows the tensor to the device"""
+    from .image_prep import attach_host_sizes
+    host = getattr(image_hw, "_sc_host", None)
+    if host is not None or not image_hw.is_cuda:
+        attach_host_sizes(moved, host if host is not None else image_hw.tolist())
+
+
+def _ragged_raw_images(vals) -> bool:
+    """an "image" column of uint8 [H, W, 3] tensors of unequal sizes: raw images for the device-side CLIP preprocessing"""
+    return (all(isinstance(v, torch.Tensor) and v.dtype == torch.uint8 and v.dim() == 3 and v.shape[2] == 3 for v in vals)
+            and len({tuple(v.shape) for v in vals}) > 1)
 
 
 def collate_general(batch: Sequence[dict], pin_memory: bool = False) -> Dict[str, torch.Tensor]:
@@ -102,6 +124,18 @@ def collate_general(batch: Sequence[dict], pin_memory: bool = False) -> Dict[str
                 for i, v in enumerate(vals):
                     padded[i, : v.shape[0]] = v
                 out[k] = padded
+            elif k == "image" and _ragged_raw_images(vals):
+                # packed bytes + sizes; model.forward hands the pair to forward_image, which resizes on the device (image_prep)
+                from .image_prep import as_entries, attach_host_sizes
+                as_entries(vals)                                   # the size limits, here rather than at the first launch
+                hw = [(int(v.shape[0]), int(v.shape[1])) for v in vals]
+                packed = torch.empty(sum(3 * h * w for h, w in hw), dtype=torch.uint8, pin_memory=pin(vals[0]), device=vals[0].device)
+                at = 0
+                for v in vals:
+                    packed[at: at + v.numel()] = v.reshape(-1)
+                    at += v.numel()
+                out[k] = packed
+                out["image_hw"] = attach_host_sizes(torch.tensor(hw, dtype=torch.long, pin_memory=pin(None)))
             else:
                 out[k] = torch.stack(vals, dim=0)
                 if pin(out[k]):

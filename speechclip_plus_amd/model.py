@@ -284,7 +284,14 @@ class KWClip_GeneralTransformer(nn.Module):
         if isinstance(images, torch.Tensor) and (images.dim() != 4 or images.shape[1] != 3):
             raise ValueError(f"Incorrect image tensor shape {images.shape}")
         with torch.no_grad():
-            return self.image_encoder(images)
+            return self.image_encoder(images)                  # pixels [B, 3, 224, 224], or raw images (kwClip.py:484-507: a list)
+
+    def prep_image(self, images: list) -> torch.Tensor:
+        """ClipModel.prep_image (clip_official.py:153-166): raw images -> normalised fp32 [B, 3, 224, 224] on the device
+        (ClipImageEncoder.prep_image)"""
+        if not hasattr(self.image_encoder, "prep_image"):
+            raise RuntimeError("prep_image needs the frozen CLIP image tower: construct with image_encoder=\"clip\"")
+        return self.image_encoder.prep_image(images)
 
     def forward_text(self, sents: Union[list, torch.Tensor]) -> torch.Tensor:
         """kwClip.py:509-527: sentences (through ``clip.prep_text``: needs a tokenizer) or a 2-D tensor of ORIGINAL CLIP token ids ->
@@ -335,6 +342,8 @@ class KWClip_GeneralTransformer(nn.Module):
         """kwClip.py:839-963."""
         wav, wav_len, image, id = batch["wav"], batch["wav_len"], batch["image"], batch["id"]
         audio_feat, audio_feat_len = self.forward_audio(wav, wav_len, return_hidden_states=False)
+        if batch.get("image_hw") is not None:                  # ragged raw images (data.collate_general): packed bytes + host sizes
+            image = (image, batch["image_hw"])
         image_feat = self.forward_image(image)
         image_feat = unit_rows(image_feat.float())
         if self.cascaded_branch is not None:                                       # kwClip.py:859-880

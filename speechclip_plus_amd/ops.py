@@ -1676,6 +1676,37 @@ def vit_embed_ln(G: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, gamma: t
     return out
 
 
+def image_resample_h(src: torch.Tensor, tab: torch.Tensor, mid: torch.Tensor, plan) -> torch.Tensor:
+    """mid (uint8, plan.mid_bytes) <- the horizontal pass of CLIP's bicubic resize over the packed raw images ``src`` (1-D uint8), only the
+    crop window's columns and the source rows its vertical pass reads (sc_image_resample_h_u8).  ``tab``: the plan's descriptor /
+    coefficient tables on the device (image_prep.Plan)."""
+    for t, dt in ((src, torch.uint8), (mid, torch.uint8), (tab, torch.int32)):
+        assert t.dtype == dt and t.dim() == 1 and t.is_contiguous()
+    assert tab.numel() == plan.tab.numel() and mid.numel() >= plan.mid_bytes and src.numel() >= plan.src_end and tab.data_ptr() % 8 == 0
+    check(lib().sc_image_resample_h_u8(_p(src), src.numel(), _p(tab), _p(tab), _p(mid), mid.numel(), plan.B, plan.max_rows, plan.n_px, _stream()),
+          "sc_image_resample_h_u8")
+    return mid
+
+
+def image_resample_v_norm(mid: torch.Tensor, tab: torch.Tensor, lut: torch.Tensor, plan, out: Optional[torch.Tensor] = None,
+                          A: Optional[torch.Tensor] = None, seg: Optional["RowSegments"] = None, P: int = 0, Kp: int = 0):
+    """The vertical pass over ``mid`` + the normalisation look-up (sc_image_resample_v_norm) into ``out`` fp32 [B, 3, S, S] and / or
+    ``A`` [seg.rows, Kp] bf16 - what vit_patchify makes of ``out``, bit for bit - whichever is given."""
+    S, B = plan.n_px, plan.B
+    assert mid.dtype == torch.uint8 and mid.is_contiguous() and mid.numel() >= plan.mid_bytes
+    assert tab.dtype == torch.int32 and tab.numel() == plan.tab.numel() and tab.data_ptr() % 8 == 0
+    assert lut.dtype == torch.float32 and lut.is_contiguous() and tuple(lut.shape) == (3, 256)
+    assert out is not None or A is not None
+    if out is not None:
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, 3, S, S)
+    if A is not None:
+        assert seg is not None and seg.B == B and min(seg.pitch) >= 1 + (S // P) ** 2
+        assert A.dtype == torch.bfloat16 and A.is_contiguous() and tuple(A.shape) == (seg.rows, Kp)
+    check(lib().sc_image_resample_v_norm(_p(mid), mid.numel(), _p(tab), _p(tab), _p(lut), _p(out), _p(A), Kp, seg.ref() if A is not None else None,
+                                         P, B, S, _stream()), "sc_image_resample_v_norm")
+    return out, A
+
+
 def rows_scatter(d: torch.Tensor, row: torch.Tensor, M: int, SEG: int) -> torch.Tensor:
     """dX [M, W] bf16: zero except dX[row[b]] = bf16(d[b]) (row[b] inside segment b of SEG rows)"""
     B, W = d.shape
