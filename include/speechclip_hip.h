@@ -29,7 +29,7 @@ extern "C" {
 typedef uint16_t sc_bf16;
 
 const char* sc_last_error(void);
-int sc_abi_version(void);     /* 6 (round 10, additive: sc_attn_fwd_relbias_bf16, sc_attn_fwd_seg_relbias_bf16, sc_wavlm_gate_bf16 - WavLM's gated relative-
+int sc_abi_version(void);     /* 6 (round 12, additive: sc_kw_pool_fwd / _bwd / _max_rows, sc_bn_eachkw_fwd / _bwd - the fixed-keyword cascaded branch); 6 (round 10, additive: sc_attn_fwd_relbias_bf16, sc_attn_fwd_seg_relbias_bf16, sc_wavlm_gate_bf16 - WavLM's gated relative-
                                  position bias; nothing else changed); 6 (round 9, additive: sc_gemm_args.a_rep / sc_hubert_layer_args.w_split took the reserved3 / reserved2 slots - split
                                  weights for evaluation; sizes unchanged); 6: one front-end entry point per kernel (sc_wav_prep, sc_conv0_stats, sc_conv0_gn_gelu, sc_conv0_ln_gelu take
                                  seg / wav_off / out_f32; their _seg, _crop, _len and _f32 symbols are gone); 5: sc_adam_f32 takes its betas as doubles; 4 since round 4 (sc_segments; sc_gemm_args / sc_hubert_layer_args grew the segment fields) */
@@ -409,6 +409,30 @@ int sc_cls_pool_bwd(const sc_bf16* X, const float* p, const float* dp, const flo
                     const float* mult, const float* cbias, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Constant-query attention pooling of the fixed-keyword cascaded branch (csrc/kwpool.hip).  Replaces
+ * avssl/model/kw_branches.py:365-374 (cat([cls] * bsz) ; self_att ; [:, :keyword_num]) over
+ * avssl/module/kw_modules/TransformerModels.py:120-126, for the K keyword rows the branch keeps:
+ *   s[b,q,:] = [ c[q, 0..C) ; a[q] . X[b, row0 + t], t < flen[b] ]      a[q] = Wk^T q_q * dh^-.5, c = a . crow^T  (host side, tiny)
+ *   p = softmax(s) ; w = p * mult ; m[b,q,:] = sum_j w_j crow[j] + sum_t w_t X[b, row0 + t] ; psum[b,q] = sum w
+ *   X [B, R, D] bf16 (frames of utterance b at rows row0 .. row0 + flen[b] - 1; no other row is read) ; a [Q, D], c [Q, C],
+ *   crow [C, D] fp32 ; flen [B] int32, 0 allowed ; mult [B, Q, C + R] fp32 or NULL ; Q, C in 1..16 ; D % 64 == 0, D <= 1024.
+ *   p [B, Q, C + R]: C constant keys, then one entry per row of X (zero outside the frames) ; m [B, Q, D] ; psum [B, Q] or NULL.
+ *   scores / dpw [B, Q, R]: workspace.
+ * backward (dm [B,Q,D]; cbias [B,Q] or NULL = the gradient of psum):
+ *   dw = dm . key + cbias ; ds = p (dw mult - sum p dw mult) ; dX [B, R, D] fp32 or bf16 (dx_bf16) = sum_q w dm + ds a on the frame rows,
+ *   zero elsewhere ; da [Q, D] = sum_b sum_t ds X ; dc [Q, C] = sum_b ds of the constant keys, both summed over b in index order from
+ *   da_part [B, Q, D] / dc_part [B, Q, C].  The gradient of crow is sum_{b,q} w[b,q,j] dm[b,q,:] (from p, host side).
+ * R is limited by the Q x (C + R) probabilities kept in LDS (twice in the backward): sc_kw_pool_max_rows; past it the entries fail
+ * with the numbers.  No atomics: equal inputs give equal bits. */
+int sc_kw_pool_max_rows(int32_t Q, int32_t C, int32_t backward);
+int sc_kw_pool_fwd(const sc_bf16* X, const float* a, const float* c, const float* crow, const int32_t* flen, float* scores, float* p,
+                   float* m, float* psum, const float* mult, int32_t B, int32_t R, int32_t D, int32_t Q, int32_t C, int32_t row0,
+                   void* stream);
+int sc_kw_pool_bwd(const sc_bf16* X, const float* a, const float* crow, const int32_t* flen, const float* p, const float* mult,
+                   const float* dm, const float* cbias, float* dpw, void* dX, int32_t dx_bf16, float* da_part, float* dc_part, float* da,
+                   float* dc, int32_t B, int32_t R, int32_t D, int32_t Q, int32_t C, int32_t row0, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Row softmax of the GEMM-based attention core (attention block of the cascaded+/hybrid+ branches,
  * avssl/module/kw_modules/TransformerModels.py:101-126 -> nn.MultiheadAttention with head_dim 768 / 128):
  *   forward   P = softmax(scale * scores | key mask)   scores fp32 [rows, n] contiguous (a batched sc_gemm_bf16 output), P bf16;
@@ -552,6 +576,13 @@ int sc_bn_rows_fwd(const float* x, int64_t ldx, int32_t N, int32_t E, const floa
                    float* save_rstd, void* stream);
 int sc_bn_rows_bwd(const float* x, int64_t ldx, const float* dy, int64_t ldg, int32_t N, int32_t E, const float* gamma,
                    const float* save_mean, const float* save_rstd, float* dx, int64_t ldd, float* dgamma, float* dbeta, void* stream);
+/* The fixed-count form (kw_bn.py:47-49,115-123: `eachKw` + `parallel`, nn.BatchNorm1d(Ed * K) over keywords.permute(0, 2, 1).reshape(B, -1)):
+ *   x, y, dy, dx [B, K, Ed] fp32 contiguous; one statistic per (keyword slot k, channel d) over the B rows; gamma, beta, run_mean, run_var,
+ *   save_mean, save_rstd, dgamma, dbeta hold (k, d) at index d * K + k - the reference checkpoint's layout, read in place. */
+int sc_bn_eachkw_fwd(const float* x, int32_t B, int32_t K, int32_t Ed, const float* gamma, const float* beta, float* run_mean, float* run_var,
+                     int32_t training, float momentum, float eps, float* y, float* save_mean, float* save_rstd, void* stream);
+int sc_bn_eachkw_bwd(const float* x, const float* dy, int32_t B, int32_t K, int32_t Ed, const float* gamma, const float* save_mean,
+                     const float* save_rstd, float* dx, float* dgamma, float* dbeta, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * fp32 strided GEMM  C[i,j] = alpha * sum_k A[i*sai + k*sak] * Bm[j*sbj + k*sbk]  (+ bias[j])

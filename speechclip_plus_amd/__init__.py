@@ -50,16 +50,17 @@ def warn_if_hw_queues_short() -> None:
 
 
 from .config import load_config
-from .model import (Config, KWClip_GeneralTransformer, base_parallel_config, cascaded_plus_base_config,
-                    hybrid_plus_large_config, large_parallel_config, set_dropout)
+from .model import (Config, KWClip_GeneralTransformer, base_parallel_config, cascaded_base_config, cascaded_large_config,
+                    cascaded_plus_base_config, hybrid_plus_large_config, large_parallel_config, set_dropout)
 from .speech_encoder import FairseqSpeechEncoder_Hubert, HubertArch, S3prlSpeechEncoderPlus, random_hubert_state_dict, random_wavlm_state_dict
-from .kw_branches import KW_CascadedBranchPlus, KW_HybridBranchPlus, KW_ParallelBranch
+from .kw_branches import KW_CascadedBranch, KW_CascadedBranchPlus, KW_HybridBranchPlus, KW_ParallelBranch
 from .transformer_models import MultiheadAttentionAndNorm, TransformerEncoder
 from .weighted_sum import WeightedSumLayer
 from .losses import MaskedContrastiveLoss
 from .retrieval import mutualRetrieval
 
-__all__ = ["Config", "load_config", "KWClip_GeneralTransformer", "base_parallel_config", "large_parallel_config", "cascaded_plus_base_config", "hybrid_plus_large_config", "KW_CascadedBranchPlus",
+__all__ = ["Config", "load_config", "KWClip_GeneralTransformer", "base_parallel_config", "large_parallel_config", "cascaded_plus_base_config", "hybrid_plus_large_config", "cascaded_base_config",
+           "cascaded_large_config", "KW_CascadedBranch", "KW_CascadedBranchPlus",
            "KW_HybridBranchPlus", "FairseqSpeechEncoder_Hubert", "HubertArch",
            "random_hubert_state_dict", "random_wavlm_state_dict", "S3prlSpeechEncoderPlus", "KW_ParallelBranch", "TransformerEncoder", "MultiheadAttentionAndNorm",
            "WeightedSumLayer", "MaskedContrastiveLoss", "mutualRetrieval", "set_dropout", "hw_queue_status"]

@@ -190,6 +190,12 @@ SIGNATURES = {
     "sc_cls_pool_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "sc_cls_pool_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                         c_void_p, c_void_p],
+    "sc_kw_pool_max_rows": [c_int, c_int, c_int],
+    "sc_kw_pool_fwd": [c_void_p] * 10 + [c_int] * 6 + [c_void_p],
+    "sc_kw_pool_bwd": [c_void_p] * 10 + [c_int] + [c_void_p] * 4 + [c_int] * 6 + [c_void_p],
+    "sc_bn_eachkw_fwd": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p,
+                         c_void_p, c_void_p],
+    "sc_bn_eachkw_bwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sc_sgemm_f32": [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
     "sc_infonce_fwd": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                        c_void_p, c_void_p, c_void_p],

@@ -434,7 +434,10 @@ __global__ __launch_bounds__(256) void vq_norm_bwd_kernel(const float* __restric
 // permute(0, 2, 1) view feeds them), statistics per channel.  One workgroup per BN_CB = 8 channels, 1024 threads = 128 row lanes x 8
 // columns: 64 - 96 workgroups and a 13-row serial walk per pass at N = 1600 (32 channels x 32 row lanes: 16 - 24 workgroups, 50 rows,
 // 30 - 39 us; 8 row lanes: 102 us); two-pass mean / variance, then the normalisation, all out of the L2.  The row lanes are added in
-// fixed order.
+// fixed order.  ``kw`` > 0 (sc_bn_eachkw_*): column e = k * (E / kw) + d of the [B, K x Ed] view of the keywords reads its parameters and
+// statistics at d * kw + k, the layout of the reference's nn.BatchNorm1d(Ed * K) over permute(0, 2, 1).reshape(B, -1) (kw_bn.py:47-49,
+// 115-123); kw = 0: index e.
+__device__ __forceinline__ int bn_param_index(int e, int E, int kw) { return kw > 0 ? (e % (E / kw)) * kw + e / (E / kw) : e; }
 constexpr int BN_CB = 8, BN_RL = 1024 / BN_CB;                                    // channels per workgroup, row lanes
 __device__ __forceinline__ float col_reduce8(float v, float (*red)[BN_CB + 1]) {  // sum over the row lanes of a column
     const int c = threadIdx.x % BN_CB, r = threadIdx.x / BN_CB;
@@ -451,11 +454,12 @@ __global__ __launch_bounds__(1024) void bn_fwd_kernel(const float* __restrict__ 
                                                      const float* __restrict__ beta, float* __restrict__ run_mean,
                                                      float* __restrict__ run_var, int training, float momentum, float eps,
                                                      float* __restrict__ y, int64_t ldy, float* __restrict__ save_mean,
-                                                     float* __restrict__ save_rstd) {
+                                                     float* __restrict__ save_rstd, int kw) {
     __shared__ float red[BN_RL][BN_CB + 1];
     const int c = threadIdx.x % BN_CB, r = threadIdx.x / BN_CB;
     const int e = blockIdx.x * BN_CB + c;
     const bool ok = e < E;
+    const int pe = ok ? bn_param_index(e, E, kw) : 0;
     float mean, rstd;
     if (training) {
         float s = 0.f;
@@ -469,17 +473,17 @@ __global__ __launch_bounds__(1024) void bn_fwd_kernel(const float* __restrict__ 
         const float var = col_reduce8(q, red) / (float)N;
         rstd = rsqrtf(var + eps);
         if (ok && r == 0) {
-            save_mean[e] = mean;
-            save_rstd[e] = rstd;
-            run_mean[e] = (1.f - momentum) * run_mean[e] + momentum * mean;
-            run_var[e] = (1.f - momentum) * run_var[e] + momentum * var * ((float)N / (float)max(N - 1, 1));
+            save_mean[pe] = mean;
+            save_rstd[pe] = rstd;
+            run_mean[pe] = (1.f - momentum) * run_mean[pe] + momentum * mean;
+            run_var[pe] = (1.f - momentum) * run_var[pe] + momentum * var * ((float)N / (float)max(N - 1, 1));
         }
     } else {
-        mean = ok ? run_mean[e] : 0.f;
-        rstd = ok ? rsqrtf(run_var[e] + eps) : 0.f;
+        mean = ok ? run_mean[pe] : 0.f;
+        rstd = ok ? rsqrtf(run_var[pe] + eps) : 0.f;
     }
     if (!ok) return;
-    const float g = gamma[e] * rstd, b = beta[e] - mean * gamma[e] * rstd;
+    const float g = gamma[pe] * rstd, b = beta[pe] - mean * gamma[pe] * rstd;
     for (int n = r; n < N; n += BN_RL) y[(int64_t)n * ldy + e] = fmaf(x[(int64_t)n * ldx + e], g, b);
 }
 
@@ -487,12 +491,13 @@ __global__ __launch_bounds__(1024) void bn_fwd_kernel(const float* __restrict__ 
 __global__ __launch_bounds__(1024) void bn_bwd_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ dy, int64_t ldg,
                                                      int N, int E, const float* __restrict__ gamma, const float* __restrict__ save_mean,
                                                      const float* __restrict__ save_rstd, float* __restrict__ dx, int64_t ldd,
-                                                     float* __restrict__ dgamma, float* __restrict__ dbeta) {
+                                                     float* __restrict__ dgamma, float* __restrict__ dbeta, int kw) {
     __shared__ float red[BN_RL][BN_CB + 1];
     const int c = threadIdx.x % BN_CB, r = threadIdx.x / BN_CB;
     const int e = blockIdx.x * BN_CB + c;
     const bool ok = e < E;
-    const float mean = ok ? save_mean[e] : 0.f, rstd = ok ? save_rstd[e] : 0.f;
+    const int pe = ok ? bn_param_index(e, E, kw) : 0;
+    const float mean = ok ? save_mean[pe] : 0.f, rstd = ok ? save_rstd[pe] : 0.f;
     float sb = 0.f, sg = 0.f;
     for (int n = r; n < N; n += BN_RL) {
         const float g = ok ? dy[(int64_t)n * ldg + e] : 0.f;
@@ -504,10 +509,10 @@ __global__ __launch_bounds__(1024) void bn_bwd_kernel(const float* __restrict__ 
     sg = col_reduce8(sg, red);
     if (!ok) return;
     if (r == 0) {
-        dgamma[e] = sg;
-        dbeta[e] = sb;
+        dgamma[pe] = sg;
+        dbeta[pe] = sb;
     }
-    const float k = gamma[e] * rstd, mb = sb / (float)N, mg = sg / (float)N;
+    const float k = gamma[pe] * rstd, mb = sb / (float)N, mg = sg / (float)N;
     for (int n = r; n < N; n += BN_RL) {
         const float xh = (x[(int64_t)n * ldx + e] - mean) * rstd;
         dx[(int64_t)n * ldd + e] = k * (dy[(int64_t)n * ldg + e] - mb - xh * mg);
@@ -667,7 +672,19 @@ extern "C" int sc_bn_rows_fwd(const float* x, int64_t ldx, int32_t N, int32_t E,
     SC_CHECK(x && gamma && beta && run_mean && run_var && y, "sc_bn_rows_fwd: null pointer");
     SC_CHECK(N > 0 && E > 0 && (!training || (save_mean && save_rstd)), "sc_bn_rows_fwd: bad arguments");
     hipLaunchKernelGGL(bn_fwd_kernel, dim3((E + BN_CB - 1) / BN_CB), dim3(BN_CB * BN_RL), 0, (hipStream_t)stream, x, ldx, N, E, gamma, beta, run_mean, run_var,
-                       training, momentum, eps, y, ldy, save_mean, save_rstd);
+                       training, momentum, eps, y, ldy, save_mean, save_rstd, 0);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sc_bn_eachkw_fwd(const float* x, int32_t B, int32_t K, int32_t Ed, const float* gamma, const float* beta, float* run_mean,
+                                float* run_var, int32_t training, float momentum, float eps, float* y, float* save_mean,
+                                float* save_rstd, void* stream) {
+    SC_CHECK(x && gamma && beta && run_mean && run_var && y, "sc_bn_eachkw_fwd: null pointer");
+    SC_CHECK(B > 0 && K > 0 && Ed > 0 && (!training || (save_mean && save_rstd)), "sc_bn_eachkw_fwd: bad arguments");
+    const int E = K * Ed;
+    hipLaunchKernelGGL(bn_fwd_kernel, dim3((E + BN_CB - 1) / BN_CB), dim3(BN_CB * BN_RL), 0, (hipStream_t)stream, x, (int64_t)E, B, E, gamma, beta, run_mean,
+                       run_var, training, momentum, eps, y, (int64_t)E, save_mean, save_rstd, K);
     SC_LAUNCH_CHECK();
     return 0;
 }
@@ -678,7 +695,18 @@ extern "C" int sc_bn_rows_bwd(const float* x, int64_t ldx, const float* dy, int6
     SC_CHECK(x && dy && gamma && save_mean && save_rstd && dx && dgamma && dbeta, "sc_bn_rows_bwd: null pointer");
     SC_CHECK(N > 0 && E > 0, "sc_bn_rows_bwd: bad arguments");
     hipLaunchKernelGGL(bn_bwd_kernel, dim3((E + BN_CB - 1) / BN_CB), dim3(BN_CB * BN_RL), 0, (hipStream_t)stream, x, ldx, dy, ldg, N, E, gamma, save_mean,
-                       save_rstd, dx, ldd, dgamma, dbeta);
+                       save_rstd, dx, ldd, dgamma, dbeta, 0);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sc_bn_eachkw_bwd(const float* x, const float* dy, int32_t B, int32_t K, int32_t Ed, const float* gamma, const float* save_mean,
+                                const float* save_rstd, float* dx, float* dgamma, float* dbeta, void* stream) {
+    SC_CHECK(x && dy && gamma && save_mean && save_rstd && dx && dgamma && dbeta, "sc_bn_eachkw_bwd: null pointer");
+    SC_CHECK(B > 0 && K > 0 && Ed > 0, "sc_bn_eachkw_bwd: bad arguments");
+    const int E = K * Ed;
+    hipLaunchKernelGGL(bn_bwd_kernel, dim3((E + BN_CB - 1) / BN_CB), dim3(BN_CB * BN_RL), 0, (hipStream_t)stream, x, (int64_t)E, dy, (int64_t)E, B, E, gamma,
+                       save_mean, save_rstd, dx, (int64_t)E, dgamma, dbeta, K);
     SC_LAUNCH_CHECK();
     return 0;
 }

@@ -18,7 +18,7 @@ from . import vector_quantizers
 from .cif import CIF
 from .linear_fn import linear_f32_autograd
 from .projections import MLPLayers
-from .vector_quantizers import Kw_BatchNorm_dynamic
+from .vector_quantizers import Kw_BatchNorm, Kw_BatchNorm_dynamic
 
 logger = logging.getLogger(__name__)
 
@@ -142,6 +142,60 @@ class KW_ParallelBranch(GeneralBranch):
                                         proj=getattr(self, "linear_proj", None))
         output["parallel_audio_feat"] = out
         return output
+
+
+class KW_CascadedBranch(GeneralBranch):
+    """kw_branches.py:285-382, the original SpeechCLIP cascaded branch: ``keyword.number`` learned queries in front of the frames ->
+    one MultiheadAttentionAndNorm block, of which only the query rows are kept -> keyword projection + fixed-count BatchNorm -> cosine
+    VQ against the CLIP token table -> frozen CLIP text encoder.  The query rows come from the constant-query pooling
+    (MultiheadAttentionAndNorm.query_forward, csrc/kwpool.hip); the tail is the plus branches'."""
+
+    def __init__(self, config, audio_dim: int, text_dim: int, clip) -> None:
+        super().__init__(config, audio_dim, text_dim)
+        self.clip = clip
+        cb = _get(_get(config, "model_settings"), "cascaded_branch")
+        kw = _get(cb, "keyword")
+        self.keyword_num = _get(kw, "number", 8)
+        self.cls = self._create_cls(length=self.keyword_num, cls_dim=_get(_get(cb, "transformer_args"), "d_model"))
+        self._create_self_attn_layer(cb)
+        if not hasattr(self.self_att, "query_forward"):
+            raise NotImplementedError(f"KW_CascadedBranch over {type(self.self_att).__name__}: every shipped recipe uses "
+                                      "MultiheadAttentionAndNorm")
+        self._create_kw_proj_layer()
+        self._create_vector_quantizer()
+        bn = _get(kw, "batchnorms", None)
+        if bn is not None:
+            emb = self.clip.model.token_embedding.weight
+            self.bn_layer = Kw_BatchNorm(kw_num=self.keyword_num, kw_dim=self.text_dim, batchnorm_type=_get(bn, "type"),
+                                         init_bias=torch.mean(emb, dim=0), init_scale=torch.std(emb, dim=0),
+                                         std_scale=_get(bn, "std_scale"), learnable=_get(bn, "learnable", True),
+                                         parallel=_get(bn, "parallel", False))
+
+    def _count(self, bsz: int, dev) -> torch.Tensor:
+        """the constant keyword count as the tensor clip.encode_keywords' kernel route takes (one upload per batch size)"""
+        c = getattr(self, "_sc_count", None)
+        if c is None or c.numel() != bsz or c.device != dev:
+            c = self._sc_count = torch.full((bsz,), self.keyword_num, device=dev, dtype=torch.int64)
+        return c
+
+    def forward(self, audio_feat: torch.Tensor, audio_feat_len: torch.Tensor, otherInputs: dict = None) -> dict:
+        output = defaultdict(lambda: None)
+        rows = self.self_att.query_forward(self.cls, audio_feat, audio_feat_len)          # [B, K, D] fp32
+        vq_results, keywords = self.vq_audio_features(rows)
+        output["vq_results"] = vq_results
+        output["keywords"] = keywords
+        output["cascaded_audio_feat"] = self.clip.encode_keywords(keywords, self._count(keywords.shape[0], keywords.device))
+        return output
+
+    def extract_hidden_states(self, audio_feat: torch.Tensor, audio_len: torch.Tensor) -> Tuple:
+        """kw_branches.py:320-347: hidden states of the block over [cls ; frames] with the query positions dropped (full-sequence
+        path).  The reference indexes the LAST state before its comprehension (``[-1]``) and so iterates over utterances; the tuple
+        of states, as the sibling branches return it, is what is built."""
+        bsz, T = audio_feat.shape[:2]
+        K = self.keyword_num
+        src = torch.cat([self.cls.expand(bsz, -1, -1).to(audio_feat.dtype), audio_feat], dim=1)
+        pad = get_keypadding_mask(T + K, audio_len.to(audio_feat.device), add=K)
+        return tuple(x[:, K:, ...] for x in self.self_att.extract_hidden_states(src=src, key_padding_mask=pad))
 
 
 class KW_CascadedBranchPlus(GeneralBranch):

@@ -21,7 +21,7 @@ from . import losses
 from .clip_image import ClipImageEncoder
 from .clip_text import ClipModel
 from .head_tail import unit_rows
-from .kw_branches import KW_CascadedBranchPlus, KW_HybridBranchPlus, KW_ParallelBranch
+from .kw_branches import KW_CascadedBranch, KW_CascadedBranchPlus, KW_HybridBranchPlus, KW_ParallelBranch
 from .speech_encoder import FairseqSpeechEncoder_Hubert, S3prlSpeechEncoderPlus
 
 logger = logging.getLogger(__name__)
@@ -57,6 +57,44 @@ def cascaded_plus_base_config(**overrides) -> Config:
     cfg.cl_loss.args.temperature_trainable = True
     cfg.retrieval.audio_feat_src = "cascaded"
     cfg.clip = Config({"name": "ViT-B/32", "embed_dim": 512, "reduce_subword_embbedding": synthetic_reduced_vocab(8112)})
+    for k, v in overrides.items():
+        cfg[k] = v
+    return cfg
+
+
+def cascaded_base_config(**overrides) -> Config:
+    """config/speechCLIP/model_base/spchclp_c.yaml (the original SpeechCLIP cascaded model, 8 learned keyword queries) restricted to
+    the keys the path reads (tests/test_cascaded_cpu.py holds every one of them against the yaml, tests/golden/recipes_cascaded.json)."""
+    cfg = base_parallel_config()
+    ms = cfg.model_settings
+    ms.cascaded_objective_weight, ms.parallel_objective_weight = 1.0, 0.0
+    ms.cascaded_branch = Config({
+        "type": "KW_CascadedBranch", "transformer_type": "MultiheadAttentionAndNorm",
+        "transformer_args": {"n_layers": 1, "d_model": 768, "nhead": 1, "dim_feedforward": 3072, "dropout": 0.1,
+                             "activation": "gelu", "layer_norm_eps": 1.0e-5, "batch_first": True, "norm_first": False},
+        "keyword": {"number": 8, "detokenized_K_neighbors": 5, "retrieve_method": "cosine",
+                    "batchnorms": {"type": "eachKw", "std_scale": 1.0, "learnable": True, "parallel": True}},
+        "vq": {"bn_before_vq": True, "activation": "gelu", "type": "SimpleVectorQuantizer",
+               "args": {"temp": "fixed=0.1", "time_first": True, "use_gumbel": False, "hard": True}}})
+    cfg.retrieval.audio_feat_src = "cascaded"
+    cfg.clip = Config({"name": "ViT-B/32", "embed_dim": 512, "image_encoder_trainable": False, "text_encoder_trainable": False,
+                       "reduce_subword_embbedding": synthetic_reduced_vocab(8112)})
+    for k, v in overrides.items():
+        cfg[k] = v
+    return cfg
+
+
+def cascaded_large_config(**overrides) -> Config:
+    """config/speechCLIP/model_large/flickr/spchclp_c.yaml: HuBERT-large ll60k with normalised hidden states, a 1024-wide block of one
+    head, CLIP ViT-L/14 (token width 768), trainable temperature.  (The coco yaml differs in the reduced vocabulary: 19787 sub-words.)"""
+    cfg = cascaded_base_config()
+    ms = cfg.model_settings
+    for ta in (ms.parallel_branch.transformer_args, ms.cascaded_branch.transformer_args):
+        ta.d_model, ta.dim_feedforward = 1024, 4096
+    cfg.audio_encoder.name = "hubert_large_ll60k"
+    cfg.audio_encoder.normalize_hiddenstates = True
+    cfg.cl_loss.args.temperature_trainable = True
+    cfg.clip.name, cfg.clip.embed_dim = "ViT-L/14", 768
     for k, v in overrides.items():
         cfg[k] = v
     return cfg
@@ -209,9 +247,18 @@ class KWClip_GeneralTransformer(nn.Module):
                 self.cascaded_branch = KW_HybridBranchPlus(config=config, audio_dim=self.audio_embd_dim,
                                                            text_dim=text_dim, out_dim=self.subword_embd_dim,
                                                            clip=self.clip)
+            elif cBranchType == "CascadedBranch":
+                # kwClip.py:722-740: the original SpeechCLIP cascaded branch, a fixed number of keywords
+                self.cascaded_branch = KW_CascadedBranch(config=config, audio_dim=self.audio_embd_dim, text_dim=text_dim,
+                                                         clip=self.clip)
+                self.keyword_num = self.cascaded_branch.keyword_num
+            elif cBranchType == "HybridBranch":
+                raise NotImplementedError("KW_HybridBranch (config/speechCLIP+/**/spchclip_h.yaml): the fixed-keyword hybrid branch - "
+                                          "its parallel_proj and two losses over the shared block - is not built; the pooling "
+                                          "kernel already takes its 9 queries (csrc/kwpool.hip)")
             else:
-                raise NotImplementedError(f"{cBranchType}: the non-plus cascaded / hybrid branches are out of scope "
-                                          "(not in BASELINE configs; SURVEY section 2)")
+                raise NotImplementedError(f"cascaded_branch.type = {ms.cascaded_branch.type}: KW_CascadedBranch, "
+                                          "KW_CascadedBranch_plus / _dynamic and KW_HybridBranch_plus / _dynamic are built")
             ds = ms.cascaded_branch.get("downsampling", None)
             if ds is not None and ds.type == "cif":
                 self.quantity_loss_weight = ds.cif.get("quantity_loss_weight", 1.0)
@@ -226,8 +273,8 @@ class KWClip_GeneralTransformer(nn.Module):
                                                      text_dim=self.subword_embd_dim)
         # frames behind feat_len the encoder still has to compute (speech_encoder.segment_pitches): the CIF weight conv of the plus
         # branches looks conv_cif_width // 2 frames past the last valid one (avssl/module/cif.py:44-52); the CLS head reads none
-        if self.cascaded_branch is None:
-            self.audio_encoder.tail_rows = 0
+        if self.cascaded_branch is None or isinstance(self.cascaded_branch, KW_CascadedBranch):
+            self.audio_encoder.tail_rows = 0          # (the fixed-keyword branch pools the valid frames, like the CLS head)
         else:
             ds = ms.cascaded_branch.get("downsampling", None)
             width = ds.cif.get("conv_cif_width", 5) if (ds is not None and ds.type == "cif") else 5
@@ -252,6 +299,11 @@ class KWClip_GeneralTransformer(nn.Module):
             from .head_tail import cls_query
             with torch.no_grad():
                 cls_query(pb.self_att, pb.cls)
+        cb = self.cascaded_branch
+        if isinstance(cb, KW_CascadedBranch) and cb.cls.is_cuda:
+            from .kw_query import kw_query
+            with torch.no_grad():
+                kw_query(cb.self_att, cb.cls)
 
     def getTrainableParams(self) -> list:
         """kwClip.py:620-644 + :812-837."""

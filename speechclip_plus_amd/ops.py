@@ -990,6 +990,33 @@ def bn_rows_bwd(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, save_mea
     return dx, dg, db
 
 
+def bn_eachkw_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, run_mean: torch.Tensor, run_var: torch.Tensor,
+                  training: bool, momentum: float, eps: float):
+    """Fixed-count keyword BatchNorm: x [B, K, Ed] fp32, one statistic per (slot k, channel d) over B, parameters and running
+    buffers [Ed * K] indexed d * K + k (the reference checkpoint's layout) -> (y, save_mean, save_rstd)."""
+    B, K, Ed = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    for t in (gamma, beta, run_mean, run_var):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == K * Ed
+    y = torch.empty_like(x)
+    sm = torch.empty(K * Ed, device=x.device, dtype=torch.float32) if training else None
+    sr = torch.empty(K * Ed, device=x.device, dtype=torch.float32) if training else None
+    check(lib().sc_bn_eachkw_fwd(_p(x), B, K, Ed, _p(gamma), _p(beta), _p(run_mean), _p(run_var), int(training), float(momentum),
+                                 float(eps), _p(y), _p(sm), _p(sr), _stream()), "sc_bn_eachkw_fwd")
+    return y, sm, sr
+
+
+def bn_eachkw_bwd(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, save_mean: torch.Tensor, save_rstd: torch.Tensor):
+    B, K, Ed = x.shape
+    assert dy.dtype == torch.float32 and dy.is_contiguous() and dy.shape == x.shape
+    dx = torch.empty_like(x)
+    dg = torch.empty(K * Ed, device=x.device, dtype=torch.float32)
+    db = torch.empty(K * Ed, device=x.device, dtype=torch.float32)
+    check(lib().sc_bn_eachkw_bwd(_p(x), _p(dy), B, K, Ed, _p(gamma), _p(save_mean), _p(save_rstd), _p(dx), _p(dg), _p(db), _stream()),
+          "sc_bn_eachkw_bwd")
+    return dx, dg, db
+
+
 def softmax_fwd(scores: torch.Tensor, key_mask: torch.Tensor, rows_per_batch: int, scale: float, drop_p: float = 0.0,
                 drop_seed: int = 0):
     """P = softmax(scale * scores | key mask) as bf16 (+ the dropped copy in train mode); scores fp32 [..., n] contiguous,
@@ -1261,6 +1288,54 @@ def cls_pool_bwd(X: torch.Tensor, p: torch.Tensor, dp: torch.Tensor, dm: torch.T
     check(lib().sc_cls_pool_bwd(_p(X), _p(p), _p(dp), _p(dm), _p(a), _p(lens), _p(dX), _p(da), B, R, D, H, _p(mult), _p(cbias), _stream()),
           "sc_cls_pool_bwd")
     return dX, da
+
+
+def kw_pool_max_rows(Q: int, C: int, backward: bool = True) -> int:
+    """Largest R (rows of X per utterance) sc_kw_pool_fwd / _bwd accept for Q queries and C constant keys (LDS-bound)."""
+    return int(lib().sc_kw_pool_max_rows(int(Q), int(C), int(backward)))
+
+
+def kw_pool_fwd(X: torch.Tensor, a: torch.Tensor, c: torch.Tensor, crow: torch.Tensor, flen: torch.Tensor, row0: int,
+                mult: Optional[torch.Tensor] = None, want_psum: bool = False):
+    """Constant-query pooling (csrc/kwpool.hip): X [B, R, D] bf16 with the frames of utterance b at rows row0 .. row0 + flen[b] - 1,
+    a [Q, D], c [Q, C] (scores of the C constant keys), crow [C, D] (their rows), flen int32 [B] -> p [B, Q, C + R] (before ``mult``),
+    m [B, Q, D] (, psum [B, Q] = sum p mult)."""
+    B, R, D = X.shape
+    Q, C = c.shape
+    assert X.dtype == torch.bfloat16 and X.is_contiguous() and flen.dtype == torch.int32 and flen.numel() == B
+    for t, shape in ((a, (Q, D)), (c, (Q, C)), (crow, (C, D))):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, (tuple(t.shape), shape)
+    if mult is not None:
+        assert tuple(mult.shape) == (B, Q, C + R) and mult.dtype == torch.float32 and mult.is_contiguous()
+    scores = torch.empty(B, Q, R, device=X.device, dtype=torch.float32)
+    p = torch.empty(B, Q, C + R, device=X.device, dtype=torch.float32)
+    m = torch.empty(B, Q, D, device=X.device, dtype=torch.float32)
+    psum = torch.empty(B, Q, device=X.device, dtype=torch.float32) if want_psum else None
+    check(lib().sc_kw_pool_fwd(_p(X), _p(a), _p(c), _p(crow), _p(flen), _p(scores), _p(p), _p(m), _p(psum), _p(mult), B, R, D, Q, C,
+                               int(row0), _stream()), "sc_kw_pool_fwd")
+    return (p, m, psum) if want_psum else (p, m)
+
+
+def kw_pool_bwd(X: torch.Tensor, a: torch.Tensor, crow: torch.Tensor, flen: torch.Tensor, row0: int, p: torch.Tensor, dm: torch.Tensor,
+                mult: Optional[torch.Tensor] = None, cbias: Optional[torch.Tensor] = None, dx_dtype: torch.dtype = torch.float32):
+    """-> dX [B, R, D] (``dx_dtype`` fp32 or bf16; zero outside the frames), da [Q, D], dc [Q, C].  ``cbias`` [B, Q]: gradient of psum."""
+    B, R, D = X.shape
+    Q, C = a.shape[0], crow.shape[0]
+    assert tuple(p.shape) == (B, Q, C + R) and p.is_contiguous() and dm.dtype == torch.float32 and dm.is_contiguous()
+    assert tuple(dm.shape) == (B, Q, D) and dx_dtype in (torch.float32, torch.bfloat16)
+    if cbias is not None:
+        assert cbias.dtype == torch.float32 and cbias.is_contiguous() and cbias.numel() == B * Q
+    dev = X.device
+    dpw = torch.empty(B, Q, R, device=dev, dtype=torch.float32)
+    dX = torch.empty(B, R, D, device=dev, dtype=dx_dtype)
+    da_part = torch.empty(B, Q, D, device=dev, dtype=torch.float32)
+    dc_part = torch.empty(B, Q, C, device=dev, dtype=torch.float32)
+    da = torch.empty(Q, D, device=dev, dtype=torch.float32)
+    dc = torch.empty(Q, C, device=dev, dtype=torch.float32)
+    check(lib().sc_kw_pool_bwd(_p(X), _p(a), _p(crow), _p(flen), _p(p), _p(mult), _p(dm), _p(cbias), _p(dpw), _p(dX),
+                               int(dx_dtype == torch.bfloat16), _p(da_part), _p(dc_part), _p(da), _p(dc), B, R, D, Q, C, int(row0),
+                               _stream()), "sc_kw_pool_bwd")
+    return dX, da, dc
 
 
 def sgemm(A: torch.Tensor, sai: int, sak: int, Bm: torch.Tensor, sbj: int, sbk: int, M: int, N: int, K: int,

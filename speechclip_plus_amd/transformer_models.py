@@ -128,3 +128,46 @@ class MultiheadAttentionAndNorm(nn.Module):
 
     def extract_hidden_states(self, src: torch.Tensor, key_padding_mask: torch.Tensor):
         return tuple([src, self.forward(src, key_padding_mask)])
+
+    # ------------------------------------------------------------------------------------------------
+    query_path = None        # "pooled" / "full": force a route of query_forward (None: SC_KW_QUERY_PATH, else pooled where it applies)
+
+    def query_forward_full(self, cls: torch.Tensor, feat: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """The K query rows by the full-sequence block: ``self(cat([cls, feat], 1), mask(lens + K))[:, :K]`` - the yardstick of the
+        pooled route and its fallback."""
+        from .kw_branches import get_keypadding_mask
+        B, T = feat.shape[:2]
+        K = cls.shape[1]
+        src = torch.cat([cls.expand(B, -1, -1).to(feat.dtype), feat], dim=1)
+        pad = get_keypadding_mask(T + K, lens.to(feat.device).long(), add=K)
+        return self.forward(src, pad)[:, :K].float()
+
+    def query_forward(self, cls: torch.Tensor, feat: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """Rows 0 .. K-1 of ``self(cat([cls, feat], 1), key_padding_mask(lens + K))`` for K learned queries ``cls`` [1, K, D]:
+        -> [B, K, D] fp32 (kw_branches.py:365-374 of the reference keeps nothing else).  One autograd node on csrc/kwpool.hip
+        (kw_query.KwQueryFn): the queries are folded into the key projection and pool the frames, which are read in place from the
+        encoder's output buffer when ``feat`` carries its handle.  ``lens`` = frames per utterance (0 allowed).  Falls back to
+        query_forward_full when K x heads > 16 or the row pitch is past the kernel's LDS limit."""
+        import os
+        from .kw_query import KwQueryFn
+        att, norm = self.multihead_attn_layer, self.attentionBlock_Norm
+        path = self.query_path or os.environ.get("SC_KW_QUERY_PATH", "pooled")
+        if path not in ("pooled", "full"):
+            raise ValueError(f"query path {path!r}: 'pooled' or 'full'")
+        if not feat.is_cuda:
+            raise RuntimeError("MultiheadAttentionAndNorm runs on the HIP kernels: device tensors only")
+        D, K = att.embed_dim, cls.shape[1]
+        Q = K * att.num_heads
+        handle = getattr(feat, "_sc_handle", None)
+        if handle is not None and getattr(handle, "hidden", None) is None:      # (a branch-made view, not the encoder's handle)
+            handle = None
+        R = handle.R if handle is not None else feat.shape[1]
+        if path == "full" or Q > 16 or D % 64 or D > 1024 or R > ops.kw_pool_max_rows(Q, K, backward=True) or feat.shape[1] == 0:
+            return self.query_forward_full(cls, feat, lens)
+        if handle is not None:
+            X, row0, ws_w, feat_in = handle.src.detach(), 1, handle.ws_layer.weights, None
+        else:
+            X, row0, ws_w, feat_in = feat.detach().to(torch.bfloat16).contiguous(), 0, None, feat
+        flen = lens.to(device=X.device, dtype=torch.int32).contiguous()
+        return KwQueryFn.apply(cls, att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias, norm.weight,
+                               norm.bias, ws_w, feat_in, self, handle, X, flen, row0)

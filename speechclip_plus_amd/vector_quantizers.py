@@ -23,6 +23,7 @@ There is no CPU path: these modules take device tensors only (the CPU restatemen
 """
 import ast
 import logging
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -301,3 +302,80 @@ class Kw_BatchNorm_dynamic(nn.Module):
         y = _KwBNFn.apply(keywords.reshape(B * N, E), bn.weight, bn.bias, bn.running_mean, bn.running_var, training,
                           float(bn.momentum), float(bn.eps))
         return y.view(B, N, E).to(keywords.dtype)
+
+
+class _KwBNEachFn(torch.autograd.Function):
+    """The fixed-count form on sc_bn_eachkw_fwd / _bwd: x [B, K, E], parameters and buffers [E * K] at index d * K + k."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, run_mean, run_var, training: bool, momentum: float, eps: float):
+        x = x.detach().float().contiguous()
+        g, b = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        y, sm, sr = ops.bn_eachkw_fwd(x, g, b, run_mean, run_var, training, momentum, eps)
+        ctx.training = training
+        if training:
+            ctx.save_for_backward(x, g, sm, sr)
+        else:
+            ctx.save_for_backward(g, run_var.detach().clone())
+            ctx.eps = eps
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.float().contiguous()
+        if ctx.training:
+            x, g, sm, sr = ctx.saved_tensors
+            dx, dg, db = ops.bn_eachkw_bwd(x, dy, g, sm, sr)
+            return dx, dg, db, None, None, None, None, None
+        g, rv = ctx.saved_tensors                      # inference statistics are constants: a scale per (slot, channel), stored [E, K]
+        B, K, E = dy.shape
+        return dy * (g * torch.rsqrt(rv + ctx.eps)).view(E, K).t(), None, None, None, None, None, None, None
+
+
+class Kw_BatchNorm(nn.Module):
+    """BatchNorm for a fixed number of keywords (kw_bn.py:8-164), initialised from the CLIP token-embedding mean / std.
+    ``eachKw`` + ``parallel``: nn.BatchNorm1d(kw_dim * kw_num) over keywords.permute(0, 2, 1).reshape(B, -1) - one statistic per
+    (keyword slot k, channel d) over the batch, parameters and running buffers stored at d * kw_num + k as a reference checkpoint
+    holds them; read in that layout by sc_bn_eachkw_fwd / _bwd (no permuted copy per step).  ``same``: one nn.BatchNorm1d(kw_dim) over
+    every keyword position (sc_bn_rows_*).  ``bn_layer`` carries the reference's state-dict names."""
+
+    def __init__(self, kw_num: int, kw_dim: int, batchnorm_type: str, init_bias: torch.Tensor, init_scale: torch.Tensor,
+                 std_scale: int = 1, learnable: bool = True, parallel: bool = False) -> None:
+        super().__init__()
+        self.batchnorm_type, self.kw_num, self.kw_dim = batchnorm_type, kw_num, kw_dim
+        self.learnable, self.parallel = learnable, parallel
+        self.std_scale = std_scale if isinstance(std_scale, list) else [std_scale] * kw_num
+        if batchnorm_type == "eachKw":
+            if not parallel:
+                raise NotImplementedError("Kw_BatchNorm: eachKw with parallel = false (kw_num separate BatchNorm1d modules, state-dict "
+                                          "keys bn_layers.*) is selected by no shipped recipe and is not built")
+            self.bn_layer = nn.BatchNorm1d(kw_dim * kw_num)
+            self.bn_layer.weight.data.copy_((init_scale * self.std_scale[0]).repeat(kw_num))
+            self.bn_layer.bias.data.copy_(init_bias.repeat(kw_num))
+        elif batchnorm_type == "same":
+            self.bn_layer = nn.BatchNorm1d(kw_dim)
+            self.bn_layer.weight.data.copy_(init_scale * self.std_scale[0])
+            self.bn_layer.bias.data.copy_(init_bias)
+        else:
+            raise NotImplementedError(f"Kw_BatchNorm: batchnorm_type = {batchnorm_type!r} (eachKw or same)")
+        self.bn_layer.weight.requires_grad = learnable
+        self.bn_layer.bias.requires_grad = learnable
+
+    def forward(self, keywords: torch.Tensor, seq_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        assert keywords.dim() == 3 and keywords.shape[2] == self.kw_dim
+        if seq_lens is not None:
+            raise NotImplementedError("Kw_BatchNorm: seq_lens (a ragged keyword count) is the dynamic module's case: Kw_BatchNorm_dynamic")
+        assert keywords.shape[1] == self.kw_num
+        if not keywords.is_cuda:
+            raise RuntimeError("Kw_BatchNorm runs on the HIP kernels: device tensors only (CPU restatement: tests/kwpool_cases.py)")
+        bn = self.bn_layer
+        B, K, E = keywords.shape
+        training = self.training
+        if training:
+            bn.num_batches_tracked.add_(1)
+        args = (bn.weight, bn.bias, bn.running_mean, bn.running_var, training, float(bn.momentum), float(bn.eps))
+        if self.batchnorm_type == "eachKw":
+            y = _KwBNEachFn.apply(keywords, *args)
+        else:
+            y = _KwBNFn.apply(keywords.reshape(B * K, E), *args).view(B, K, E)
+        return y.to(keywords.dtype)
