@@ -29,7 +29,7 @@ extern "C" {
 typedef uint16_t sc_bf16;
 
 const char* sc_last_error(void);
-int sc_abi_version(void);     /* 6 (round 12, additive: sc_kw_pool_fwd / _bwd / _max_rows, sc_bn_eachkw_fwd / _bwd - the fixed-keyword cascaded branch); 6 (round 10, additive: sc_attn_fwd_relbias_bf16, sc_attn_fwd_seg_relbias_bf16, sc_wavlm_gate_bf16 - WavLM's gated relative-
+int sc_abi_version(void);     /* 6 (round 13, additive: sc_search_slabs, sc_search_topk_bf16 - gallery search); 6 (round 12, additive: sc_kw_pool_fwd / _bwd / _max_rows, sc_bn_eachkw_fwd / _bwd - the fixed-keyword cascaded branch); 6 (round 10, additive: sc_attn_fwd_relbias_bf16, sc_attn_fwd_seg_relbias_bf16, sc_wavlm_gate_bf16 - WavLM's gated relative-
                                  position bias; nothing else changed); 6 (round 9, additive: sc_gemm_args.a_rep / sc_hubert_layer_args.w_split took the reserved3 / reserved2 slots - split
                                  weights for evaluation; sizes unchanged); 6: one front-end entry point per kernel (sc_wav_prep, sc_conv0_stats, sc_conv0_gn_gelu, sc_conv0_ln_gelu take
                                  seg / wav_off / out_f32; their _seg, _crop, _len and _f32 symbols are gone); 5: sc_adam_f32 takes its betas as doubles; 4 since round 4 (sc_segments; sc_gemm_args / sc_hubert_layer_args grew the segment fields) */
@@ -566,6 +566,28 @@ int sc_topk_rows_f32(const float* scores, int64_t ld, int32_t rows, int32_t V, i
  * reported next to the tokens do not. */
 int sc_topk_rescore_cos_f32(const float* kw, int64_t ldk, const float* table, int64_t ldt, int32_t V, int32_t E, float eps,
                             const int32_t* idx, int32_t rows, int32_t k, float* vals, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Gallery search: the k best gallery rows of every query, the selection fused into the score GEMM (csrc/search.hip).
+ *   replaces: torch.argsort(score, descending=True) over the whole score matrix (avssl/module/retrieval.py:45-46) built at
+ *             avssl/model/kwClip.py:447-482 - here the [nQ, N] score matrix is never written.
+ *   sc_search_slabs      S for (nQ, N, k): the gallery axis is cut into S slabs of whole 128-column tiles, every slab but the last
+ *                        full (>= k valid columns), up to two (row tile, slab) workgroups per CU when nQ is small, 1 when the
+ *                        row tiles alone do or N fits one tile.
+ *   sc_search_topk_bf16  q_split [roundup(nQ, 128), K6] / g_split [roundup(N, 128), K6]: the side-0 / side-1 operands sc_split3_bf16
+ *                        writes (K6 = 6 Ep, Ep % 64 == 0, padding rows zero).  Scores = the six K-blocks summed in fp32 on the bf16
+ *                        MFMA, K-tiles in increasing order (the arithmetic of sc_gemm_bf16 on the same operands).  Writes, for
+ *                        every query and slab, the slab's k best as part_vals / part_idx [nQ, S, k] (fp32 / int32 global gallery
+ *                        row), best first, in sc_topk_rows_f32's order: larger value first, lower index first among equal values
+ *                        (-0 == +0), NaN above every number, fewer than k columns: -inf / -1 behind them.  Columns >= N never
+ *                        enter.  S = 1: the result itself.  S > 1: merge with sc_topk_rows_f32 over [nQ, S k] and gather part_idx
+ *                        (lower slab = lower columns, so position order is index order).  1 <= k <= 32; K6 % 384 == 0; S >= 1 and
+ *                        S - 1 slabs of ceil(tiles / S) tiles must end before the last tile; nQ == 0: no-op; N == 0: -inf / -1.
+ *                        No atomics; results do not depend on S.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_search_slabs(int32_t nQ, int32_t N, int32_t k);
+int sc_search_topk_bf16(const sc_bf16* q_split, const sc_bf16* g_split, int32_t nQ, int32_t N, int32_t K6, int32_t k, int32_t S,
+                        float* part_vals, int32_t* part_idx, void* stream);
 
 /* Keyword BatchNorm: nn.BatchNorm1d over the keyword positions (avssl/module/speechclip_c_modules/kw_bn.py:167-228).
  *   x [N, E] fp32 (N = batch x keyword slots), per-channel statistics.  training: batch statistics (biased variance for the

@@ -757,6 +757,35 @@ class KWClip_GeneralTransformer(nn.Module):
         return {"cascaded_audio_feat": output["cascaded_audio_feat"], "parallel_audio_feat": output["parallel_audio_feat"],
                 "vq_results": output["vq_results"], "keywords": output["keywords"]}
 
+    def retrieve(self, queries, gallery, k: Optional[int] = None, src: Optional[str] = None):
+        """Which gallery items a query retrieves: (vals [nQ, k] fp32, idx [nQ, k] int64), best first (retrieval.search; the
+        ranking avssl/module/retrieval.py:45-46 computes from the scores of kwClip.py:447-482 and drops).  ``queries``: a [nQ, E]
+        tensor of speech embeddings, or a list of waveforms - those go through ``encode_speech``, and ``src`` ("cascaded" /
+        "parallel"; None: ``config.retrieval.audio_feat_src``) picks the branch output.  ``gallery``: image or caption embeddings
+        [N, E] (what ``forward_image`` / ``forward_text`` return) or a retrieval.GalleryIndex built with ``cosine=True``.  Query
+        and gallery rows are brought to unit length as ``forward`` does, so the scores are cosines.  ``k``: None = max(recall_at)."""
+        from .retrieval import GalleryIndex, search
+        g_cuda = gallery.split.is_cuda if isinstance(gallery, GalleryIndex) else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
+        if not g_cuda or (isinstance(queries, torch.Tensor) and not queries.is_cuda):
+            raise RuntimeError("retrieve runs on the HIP kernels: device tensors only")
+        if isinstance(queries, (list, tuple)):
+            src = src if src is not None else self.config.retrieval.get("audio_feat_src", "parallel")
+            if src not in ("cascaded", "parallel"):
+                raise ValueError(f"retrieve: src = {src!r} (\"cascaded\" or \"parallel\")")
+            key = "cascaded_audio_feat" if src == "cascaded" else "parallel_audio_feat"
+            with torch.no_grad():
+                feat = self.encode_speech(list(queries))[key]
+            if feat is None:
+                raise RuntimeError(f"retrieve: this recipe has no {key} (src = {src!r})")
+            queries = feat
+        if not isinstance(queries, torch.Tensor) or queries.dim() != 2:
+            raise ValueError("retrieve: queries must be a [nQ, E] tensor of embeddings or a list of waveforms")
+        k = int(max(self.recall_at)) if k is None else int(k)
+        queries = unit_rows(queries.detach().float())
+        if not isinstance(gallery, GalleryIndex):
+            gallery = unit_rows(gallery.detach().float())
+        return search(queries, gallery, k)
+
     def extract_keywords(self, wav) -> dict:
         """kwClip.py:1093-1103, the inference entry of the keyword recipes: ``wav`` one 1-D waveform (or a list of them) ->
         ``{"vq_results", "dsample_results"}`` with ``vq_results["targets"]`` flattened to a list of ORIGINAL CLIP token ids

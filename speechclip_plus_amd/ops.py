@@ -890,6 +890,49 @@ def topk_rows(scores: torch.Tensor, V: int, k: int, vals: Optional[torch.Tensor]
     return vals, idx
 
 
+def search_slabs(nQ: int, N: int, k: int) -> int:
+    """Slabs the gallery axis of ``search_topk`` is cut into for (nQ, N, k) (sc_search_slabs)."""
+    return int(lib().sc_search_slabs(int(nQ), int(N), int(k)))
+
+
+def search_topk(q_split: torch.Tensor, g_split: torch.Tensor, nQ: int, N: int, k: int, slabs: Optional[int] = None,
+                vals: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None):
+    """The k best of N gallery rows for each of nQ queries, selection fused into the score GEMM (sc_search_topk_bf16, csrc/search.hip):
+    ``q_split`` = split3_bf16(queries, 0) [>= roundup(nQ, 128), 6 Ep], ``g_split`` = split3_bf16(gallery, 1) [>= roundup(N, 128), 6 Ep]
+    -> (vals [nQ, k] fp32, idx [nQ, k] int32), best first in ``topk_rows``' order (ties to the lower gallery row, NaN first, -inf / -1
+    behind the N-th entry).  The scores are those of ``cosine_scores_split``; no [nQ, N] matrix is written.  ``slabs``: how many slabs
+    the gallery axis is cut into (None: sc_search_slabs); the result does not depend on it.  More than one slab: the per-slab lists
+    [nQ, S, k] are merged by ``topk_rows`` and one gather.  ``vals`` / ``idx``: caller-owned contiguous outputs."""
+    if not (q_split.is_cuda and g_split.is_cuda):
+        raise RuntimeError("search_topk runs on the HIP kernels: no CPU path")
+    assert q_split.dtype == torch.bfloat16 and g_split.dtype == torch.bfloat16 and q_split.dim() == 2 and g_split.dim() == 2
+    assert q_split.is_contiguous() and g_split.is_contiguous()
+    K6 = q_split.shape[1]
+    assert g_split.shape[1] == K6, (q_split.shape, g_split.shape)
+    nQ, N, k = int(nQ), int(N), int(k)
+    assert q_split.shape[0] >= -(-nQ // 128) * 128 and g_split.shape[0] >= -(-N // 128) * 128, (q_split.shape, nQ, g_split.shape, N)
+    dev = q_split.device
+    if vals is None:
+        vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
+    if idx is None:
+        idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
+    assert tuple(vals.shape) == (nQ, k) and tuple(idx.shape) == (nQ, k)
+    S = search_slabs(nQ, N, k) if slabs is None else int(slabs)
+    if S == 1 or nQ == 0:
+        pv, pi = vals, idx
+    else:
+        pv = torch.empty(nQ, S * k, device=dev, dtype=torch.float32)
+        pi = torch.empty(nQ, S * k, device=dev, dtype=torch.int32)
+    null = ctypes.c_void_p(0)
+    check(lib().sc_search_topk_bf16(_p(q_split) if nQ else null, _p(g_split) if N else null, nQ, N, K6, k, S, _p(pv) if nQ else null,
+                                    _p(pi) if nQ else null, _stream()), "sc_search_topk_bf16")
+    if pv is not vals:
+        _, pos = topk_rows(pv, S * k, k, vals=vals)
+        torch.gather(pi, 1, pos.long(), out=idx)
+    return vals, idx
+
+
 def topk_rescore_cos(kw: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, vals: torch.Tensor, eps: float = 1e-8) -> torch.Tensor:
     """vals[r, j] <- cos(kw[r], table[idx[r, j]]) accumulated in fp64 (sc_topk_rescore_cos_f32): kw [rows, E], table [V, E] fp32, idx /
     vals [rows, k] int32 / fp32 contiguous (idx as ops.topk_rows wrote it; -1 -> -inf)."""

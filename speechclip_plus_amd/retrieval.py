@@ -10,9 +10,11 @@ unstable ``argsort`` - collapsed embeddings (all scores equal) then score about 
 AGAINST the query (a wrong candidate with the same score as the best correct one is ahead of it), a NaN candidate is ahead of
 everything (where the reference's sort puts it) and a query whose best correct score is not finite is a miss at every k: a
 diverged or collapsed model reports recall near 0, never 100, so a "keep the best validation recall" monitor cannot latch onto it."""
-from typing import Dict, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple, Union
 
 import torch
+
+__all__ = ["mutualRetrieval", "GalleryIndex", "search"]
 
 
 def _recall(score: torch.Tensor, query_ids: torch.Tensor, cand_ids: torch.Tensor, ks: Sequence[int], cand_title: str) -> Dict[str, float]:
@@ -48,3 +50,123 @@ def mutualRetrieval(score_per_A: torch.Tensor, score_per_B: torch.Tensor, AB_ans
     results_BA = _recall(score_per_B.to(score_per_A.device), b_ids, a_ids, recall_at, modality_A_title)
     results_mean = {key: 0.5 * (results_AB[key] + results_BA[key]) for key in results_AB}
     return results_AB, results_BA, results_mean
+
+
+# ------------------------------------------------------------------------------------------------ gallery search
+# What the reference does with its ranking: torch.argsort(score, descending=True) of the whole [nQ, N] matrix
+# (avssl/module/retrieval.py:45-46, scores from avssl/model/kwClip.py:447-482), read off into recall figures and dropped.  ``search``
+# returns the first k entries of every row of that ranking - items and scores - without the matrix: ops.search_topk selects inside
+# the score GEMM's epilogue (csrc/search.hip).
+_INDEX_CHUNK_ROWS = 16384          # gallery / query rows split per pass (a multiple of 128)
+
+
+def _rows_f32(x: torch.Tensor) -> torch.Tensor:
+    """fp32 rows with unit column stride (any row pitch: the split kernel takes one)"""
+    x = x.detach().float()
+    return x if x.stride(1) == 1 else x.contiguous()
+
+
+def _split_rows(x: torch.Tensor, side: int, cosine: bool, out: torch.Tensor) -> None:
+    """x [R, E] fp32 -> out[: roundup(R, 128)] = its three-way bf16 split (ops.split3_bf16); ``cosine``: rows scaled by
+    1 / max(|x|, 1e-8) (ops.vq_prep's rnorm as the split's row_scale)."""
+    from . import ops
+    R = x.shape[0]
+    rnorm = ops.vq_prep(x)[1] if cosine else None
+    ops.split3_bf16(x, side, row_scale=rnorm, out=out[: -(-R // 128) * 128])
+
+
+FUSED_MIN_GALLERY = 131072
+
+
+def default_route(nQ: int, N: int) -> str:
+    """"fused" (csrc/search.hip) or "composition" (ops.cosine_scores_split into a 128 MiB score scratch + ops.topk_rows, what
+    keyword_neighbors runs) for nQ queries against N gallery rows.  Measured (docs/rounds/r13_search.md): the fused kernel wins where
+    whole score rows stop fitting the scratch in useful numbers - a large gallery - and loses below, where the composition's GEMM
+    runs on the 256-row tiles and the score matrix stays in the Infinity Cache."""
+    return "fused" if N >= FUSED_MIN_GALLERY or N == 0 else "composition"
+
+
+class GalleryIndex:
+    """A gallery [N, E] prepared for ``search``: the side-1 three-way bf16 split of its rows ([roundup(N, 128), 6 Ep] bf16, Ep = E
+    rounded up to 64: 12 Ep bytes per gallery row), built in chunks of rows so that no second fp32 copy of a large gallery is made.
+    ``cosine=True``: every row is scaled by 1 / max(|g|, 1e-8) on the way in, so the scores against unit (or ``cosine=True``)
+    queries are cosines.  Build once, search with any number of query batches."""
+
+    def __init__(self, gallery: torch.Tensor, cosine: bool = False):
+        if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2:
+            raise ValueError("GalleryIndex: gallery must be a [N, E] tensor")
+        if not gallery.is_cuda:
+            raise RuntimeError("GalleryIndex runs on the HIP kernels: device tensors only")
+        self.N, self.E = int(gallery.shape[0]), int(gallery.shape[1])
+        assert self.E >= 1, gallery.shape
+        self.cosine = bool(cosine)
+        self.Ep = -(-self.E // 64) * 64
+        self.split = torch.empty(-(-self.N // 128) * 128, 6 * self.Ep, device=gallery.device, dtype=torch.bfloat16)
+        for r0 in range(0, self.N, _INDEX_CHUNK_ROWS):
+            r1 = min(self.N, r0 + _INDEX_CHUNK_ROWS)
+            _split_rows(_rows_f32(gallery[r0:r1]), 1, self.cosine, self.split[r0:])
+
+    @property
+    def device(self) -> torch.device:
+        return self.split.device
+
+    def __len__(self) -> int:
+        return self.N
+
+
+def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex], k: int, cosine: bool = False,
+           slabs: Optional[int] = None, route: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """queries [nQ, E], gallery [N, E] (or a GalleryIndex of it) -> (vals [nQ, k] fp32, idx [nQ, k] int64): for every query the k
+    gallery rows with the largest inner product, best first, on the device.  ``cosine=True`` scales query and gallery rows by
+    1 / max(|x|, 1e-8) first (a GalleryIndex carries its own choice; the flag then applies to the queries).  1 <= k <= 32.
+
+    Order: larger score first, the lower gallery index first among equal scores, NaN above every number; fewer than k gallery rows:
+    -inf / -1 behind them.  ``vals`` are the kernel's fp32 scores: the three-way bf16 splits of both rows multiplied on the bf16
+    matrix pipe, six K-blocks summed in fp32.  Accuracy: with Ep = E rounded up to 64, a score differs from the exact inner product
+    by at most (6 Ep + 8) 2^-24 sum_i |q_i| |g_i|; the returned order is the order of those fp32 scores, so two gallery rows whose
+    exact scores are closer than twice that bound can come back in either order, and a row within twice the bound of the k-th best
+    may take its place.  Non-finite inputs: an infinity becomes NaN in the split, so a row with a NaN or an infinity scores NaN
+    against every query and ranks first.  ``route``: None = ``default_route`` picks by the gallery size - "fused" (csrc/search.hip:
+    the selection runs in the score GEMM's epilogue, the [nQ, N] score matrix is never written, queries go in chunks of 16384
+    rows) or "composition" (the same score GEMM into one 128 MiB scratch per chunk of queries + ops.topk_rows; faster on small
+    galleries); both give the same lists.  ``slabs``: slabs of the gallery axis of the fused kernel (tests; implies "fused"; the
+    result does not depend on it)."""
+    from . import ops
+    if not isinstance(queries, torch.Tensor) or queries.dim() != 2:
+        raise ValueError("search: queries must be a [nQ, E] tensor")
+    g_cuda = gallery.split.is_cuda if isinstance(gallery, GalleryIndex) else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
+    if not queries.is_cuda or not g_cuda:
+        raise RuntimeError("search runs on the HIP kernels: device tensors only")
+    index = gallery if isinstance(gallery, GalleryIndex) else GalleryIndex(gallery, cosine=cosine)
+    nQ, E = queries.shape
+    assert E == index.E, (queries.shape, index.E)
+    k = int(k)
+    assert 1 <= k <= 32, f"k = {k}: the selection keeps at most 32 gallery rows per query"
+    dev = queries.device
+    vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
+    if route is None:
+        route = "fused" if slabs is not None else default_route(nQ, index.N)
+    if route not in ("fused", "composition"):
+        raise ValueError(f"search: route = {route!r} (\"fused\" or \"composition\")")
+    if nQ > 0:
+        q = _rows_f32(queries)
+        if route == "composition" and index.N > 0:
+            from .keyword_neighbors import default_chunk_rows
+            chunk = min(default_chunk_rows(index.N), -(-nQ // 128) * 128)
+            scores = torch.empty(chunk, index.split.shape[0], device=dev, dtype=torch.float32)   # the one score scratch of the call
+        else:
+            chunk = min(_INDEX_CHUNK_ROWS, -(-nQ // 128) * 128)
+            scores = None
+        split = torch.empty(chunk, 6 * index.Ep, device=dev, dtype=torch.bfloat16)       # the one query-split buffer of the call
+        for r0 in range(0, nQ, chunk):
+            r1 = min(nQ, r0 + chunk)
+            if scores is None:
+                _split_rows(q[r0:r1], 0, cosine, split)
+                ops.search_topk(split, index.split, r1 - r0, index.N, k, slabs=slabs, vals=vals[r0:r1], idx=idx[r0:r1])
+            else:
+                rp = -(-(r1 - r0) // 128) * 128
+                rnorm = ops.vq_prep(q[r0:r1])[1] if cosine else None
+                ops.cosine_scores_split(q[r0:r1], rnorm, index.split, index.split.shape[0], out=scores[:rp], split_out=split[:rp])
+                ops.topk_rows(scores[: r1 - r0], index.N, k, vals=vals[r0:r1], idx=idx[r0:r1])
+    return vals, idx.long()
