@@ -14,7 +14,7 @@
  *     global state.  Re-entrant per stream.
  *   - return 0 on success, <0 on error; sc_last_error() gives a thread-local message.
  *   - bf16 tensors are raw uint16 storage (`sc_bf16`); "rows" of activations live in the padded layout
- *     described in DESIGN.md: utterance b, frame t  ->  row  b*R + t (uniform pitch R), or - round 4, the `_seg` entry points -
+ *     described in DESIGN.md: utterance b, frame t  ->  row  b*R + t (uniform pitch R), or - round 4, a non-NULL `seg` argument -
  *     row  row0[b] + t  with a pitch per utterance (`sc_segments`): work follows the real lengths of a ragged batch.
  */
 #ifndef SPEECHCLIP_HIP_H
@@ -29,7 +29,8 @@ extern "C" {
 typedef uint16_t sc_bf16;
 
 const char* sc_last_error(void);
-int sc_abi_version(void);     /* 6 (round 13, additive: sc_search_slabs, sc_search_topk_bf16 - gallery search); 6 (round 12, additive: sc_kw_pool_fwd / _bwd / _max_rows, sc_bn_eachkw_fwd / _bwd - the fixed-keyword cascaded branch); 6 (round 10, additive: sc_attn_fwd_relbias_bf16, sc_attn_fwd_seg_relbias_bf16, sc_wavlm_gate_bf16 - WavLM's gated relative-
+int sc_abi_version(void);     /* 7: one encoder entry point per kernel (sc_attn_fwd_bf16 takes seg / work / nwork and gate / table / tmax; sc_posconv_bf16,
+                                 sc_posconv_prep, sc_wsum_fwd, sc_wsum_bwd take seg; their _seg and _relbias symbols are gone); 6 (round 13, additive: sc_search_slabs, sc_search_topk_bf16 - gallery search); 6 (round 12, additive: sc_kw_pool_fwd / _bwd / _max_rows, sc_bn_eachkw_fwd / _bwd - the fixed-keyword cascaded branch); 6 (round 10, additive: sc_attn_fwd_relbias_bf16, sc_attn_fwd_seg_relbias_bf16, sc_wavlm_gate_bf16 - WavLM's gated relative-
                                  position bias; nothing else changed); 6 (round 9, additive: sc_gemm_args.a_rep / sc_hubert_layer_args.w_split took the reserved3 / reserved2 slots - split
                                  weights for evaluation; sizes unchanged); 6: one front-end entry point per kernel (sc_wav_prep, sc_conv0_stats, sc_conv0_gn_gelu, sc_conv0_ln_gelu take
                                  seg / wav_off / out_f32; their _seg, _crop, _len and _f32 symbols are gone); 5: sc_adam_f32 takes its betas as doubles; 4 since round 4 (sc_segments; sc_gemm_args / sc_hubert_layer_args grew the segment fields) */
@@ -164,53 +165,45 @@ int sc_gemm_bf16(const sc_gemm_args* args, void* stream);
 uint32_t sc_hash32(uint32_t x);   /* host twin of the kernels' dropout hash (lowbias32): reconstructs a mask exactly */
 
 /* ------------------------------------------------------------------------------------------------
- * Self-attention forward (flash style, key-padding by length), head_dim 64.
+ * Self-attention forward (flash style, key-padding by length), head_dim 64, optionally with WavLM's gated relative-position bias.
  *   replaces: fairseq MultiheadAttention inside TransformerSentenceEncoderLayer, invoked at
- *             avssl/module/speech_encoder_plus.py:52  (softmax((q*dh^-.5) k^T + kpm(-inf)) v)
- *   qk   [B*R, ldqk] bf16 : columns [0, D) = q (unscaled), [D, 2D) = k ; head h owns 64 columns
- *   vt   [B, H, 64, R] bf16 : v transposed per head (written by sc_gemm_bf16's Ct path)
+ *             avssl/module/speech_encoder_plus.py:52  (softmax((q*dh^-.5) k^T + kpm(-inf)) v); with the bias, microsoft/unilm
+ *             wavlm/modules.py MultiheadAttention.forward with position_bias (the s3prl upstreams wavlm_base / wavlm_base_plus /
+ *             wavlm_large behind S3prlSpeechEncoderPlus, avssl/module/speech_encoder_plus.py:145,278-281) and transformers
+ *             WavLMAttention.forward step 4 + torch_multi_head_self_attention - both materialise gate . position_bias as
+ *             [B H, T, T] and hand it to the softmax as an additive mask; here it is never formed
+ *   qk   [rows, ldqk] bf16 : columns [0, D) = q (unscaled), [D, 2D) = k ; head h owns 64 columns
+ *   vt   bf16 : v transposed per head (written by sc_gemm_bf16's Ct path), see the row layout
  *   valid_len [B] int32 : keys t >= valid_len[b] are masked (-inf)
- *   out  [B*R, ldo] bf16, columns h*64..h*64+63
+ *   out  [rows, ldo] bf16, columns h*64..h*64+63
+ *   lse2 log2-domain log-sum-exp for the backward (covers the biased values), or NULL
  *   causal (CLIP text tower): 1 = key t visible to query q iff t <= q ; 32 / 64 = causal INSIDE aligned segments of that many
  *       rows (short sequences packed back to back into one 128-row block attend to their own segment only); same for the backward
- * ---------------------------------------------------------------------------------------------- */
-int sc_attn_fwd_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len,
-                     sc_bf16* out, int64_t ldo, int32_t B, int32_t R, int32_t H, int32_t D, float scale,
-                     float* lse2 /* [B,H,R] log2-domain log-sum-exp for the backward, or NULL */,
-                     int32_t causal /* 1: key t' > query t masked too (CLIP text tower) */,
-                     float drop_p, uint32_t drop_seed /* attention-probability dropout (train mode): P' = mask . P / (1 - p), element
-                     ((b*H + h)*R + q)*R + k hashed as in sc_gemm_args; 0 = off */, void* stream);
-
-/* The same over ragged rows (sc_segments): q / k rows of utterance b at row0[b] + t, vt = per utterance [H, 64, Rb] at element offset
- * D * row0[b] (what sc_gemm_bf16 writes with seg_chunk), out rows likewise; lse2 [H][rows].  One workgroup = 128 queries of one
- * (utterance, head); in a last, shorter block the waves (32 queries each) past the pitch idle and the rows past it are not stored.  work (optional, device
- * [nwork][4] int32, 16-byte aligned): the 128-query blocks to run, in launch order, one item = (utterance | q-block << 16, row0 of the
- * utterance, its pitch, its key count or -1 = read valid_len) - the host sorts them longest first (an utterance's cost grows with
- * its key count); NULL = every (b, q-block < max_pitch / 128), blocks past an utterance's pitch exit.  Dropout element index:
- * ((h * rows + row0[b] + q) * max_pitch + k).  Bit-identical to the uniform call on the rows they share. */
-int sc_attn_fwd_seg_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
-                         const sc_segments* seg, const int32_t* work, int32_t nwork, int32_t H, int32_t D, float scale, float* lse2,
-                         int32_t causal, float drop_p, uint32_t drop_seed, void* stream);
-
-/* ------------------------------------------------------------------------------------------------
- * The same two with WavLM's gated relative-position bias:  softmax(scale q k^T + gate[h][i] table[h][j - i] + kpm(-inf)) v
- *   replaces: microsoft/unilm wavlm/modules.py MultiheadAttention.forward with position_bias (the s3prl upstreams wavlm_base /
- *             wavlm_base_plus / wavlm_large behind S3prlSpeechEncoderPlus, avssl/module/speech_encoder_plus.py:145,278-281) and
- *             transformers WavLMAttention.forward step 4 + torch_multi_head_self_attention - both materialise
- *             gate . position_bias as [B H, T, T] and hand it to the softmax as an additive mask; here it is never formed
+ *   drop_p, drop_seed: attention-probability dropout (train mode): P' = mask . P / (1 - p), the element index below hashed as in
+ *       sc_gemm_args; 0 = off
+ * Row layout (seg).  One workgroup = 128 queries of one (utterance, head) in either layout.
+ *   NULL: uniform rows.  Utterance b's rows at b R (R a multiple of 8), vt [B, H, 64, R], lse2 [B, H, R], dropout element
+ *     ((b*H + h)*R + q)*R + k (B*H*R*R < 2^32).  work must be NULL and nwork 0.  causal: 0, 1, 32 or 64.
+ *   ragged rows (sc_segments): q / k rows of utterance b at row0[b] + t, vt = per utterance [H, 64, Rb] at element offset D * row0[b]
+ *     (what sc_gemm_bf16 writes with seg_chunk), out rows likewise; lse2 [H][rows]; B < 65536.  B and R are not read.  In a last,
+ *     shorter block the waves (32 queries each) past the pitch idle and the rows past it are not stored.  work (optional, device
+ *     [nwork][4] int32, 16-byte aligned): the 128-query blocks to run, in launch order, one item = (utterance | q-block << 16, row0 of
+ *     the utterance, its pitch, its key count or -1 = read valid_len) - the host sorts them longest first (an utterance's cost grows
+ *     with its key count); NULL = every (b, q-block < max_pitch / 128), blocks past an utterance's pitch exit.  Dropout element
+ *     ((h * rows + row0[b] + q) * max_pitch + k) (H*rows*max_pitch < 2^32).  causal: 0 or 1.  Bit-identical to the uniform call on
+ *     the rows they share.
+ * Bias (gate, table: both or neither; both NULL = the plain kernel, tmax is not read):
+ *     softmax(scale q k^T + gate[h][i] table[h][j - i] + kpm(-inf)) v
  *   gate  [H][rows] fp32, rows = B R (uniform) or seg->rows: one value per (head, query row) in the row layout of the call
  *         (sc_wavlm_gate_bf16); pad rows may hold anything finite
  *   table [H][2 tmax - 1] fp32, natural-log units: entry tmax - 1 + (j - i) = the bias of key j seen from query i; tmax >= the
  *         (largest) row pitch, which is limited to 8064 rows (the workgroup's slice of the table sits in LDS)
- *   causal must be 0 (error otherwise).  Dropout element index and hash as in the plain calls.  lse2 covers the biased values.
+ *   causal must be 0 (error otherwise).
  * ---------------------------------------------------------------------------------------------- */
-int sc_attn_fwd_relbias_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
-                             int32_t B, int32_t R, int32_t H, int32_t D, float scale, const float* gate, const float* table, int32_t tmax,
-                             float* lse2, int32_t causal, float drop_p, uint32_t drop_seed, void* stream);
-int sc_attn_fwd_seg_relbias_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
-                                 const sc_segments* seg, const int32_t* work, int32_t nwork, int32_t H, int32_t D, float scale,
-                                 const float* gate, const float* table, int32_t tmax, float* lse2, int32_t causal, float drop_p,
-                                 uint32_t drop_seed, void* stream);
+int sc_attn_fwd_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
+                     const sc_segments* seg, const int32_t* work, int32_t nwork, int32_t B, int32_t R, int32_t H, int32_t D, float scale,
+                     const float* gate, const float* table, int32_t tmax, float* lse2, int32_t causal, float drop_p, uint32_t drop_seed,
+                     void* stream);
 
 /* The gate of that bias, one launch per layer.
  *   replaces: unilm MultiheadAttention.forward's gru_rel_pos branch (grep_linear / grep_a) = transformers WavLMAttention.forward
@@ -319,29 +312,29 @@ int sc_conv0_ln_bwd(const float* wav, int64_t ldw, const float* w0, const float*
 
 /* ------------------------------------------------------------------------------------------------
  * pos_conv input: zero padded frames (speech_encoder_plus.py:32-33 index_put(x, padding_mask, 0)) and
- * regroup channels-last [B*R, D] into the group-major, halo-padded slab layout the grouped conv GEMM reads:
- *   xz  [B*R, D]              : masked copy (residual operand of the pos_conv epilogue)
- *   xg  [G, B, R + 2*halo, D/G] : rows [halo, halo+R) hold the masked frames, everything else 0
+ * regroup channels-last rows into the group-major, halo-padded slab layout the grouped conv reads:
+ *   xz  [rows, D] : masked copy (residual operand of the pos_conv epilogue)
+ *   xg  slabs of D/G channels: the masked frames between zero halos, see the row layout
+ * Row layout (seg).
+ *   NULL: uniform rows.  xz [B*R, D], xg [G, B, R + 2*halo, D/G] : rows [halo, halo+R) hold the masked frames, everything else 0.
+ *   ragged rows: xg [G][rows + 2 * halo * B][D / G], utterance b's slab at row  row0[b] + 2 * halo * b  (its frames at + halo); the
+ *     kernel reads seg->chunk (16-byte aligned), rows % 8 == 0, halo > 0.  B and R are not read.
  * ---------------------------------------------------------------------------------------------- */
-int sc_posconv_prep(const sc_bf16* x, const int32_t* valid_len, sc_bf16* xz, sc_bf16* xg, int32_t B, int32_t R,
+int sc_posconv_prep(const sc_bf16* x, const int32_t* valid_len, sc_bf16* xz, sc_bf16* xg, const sc_segments* seg, int32_t B, int32_t R,
                     int32_t D, int32_t G, int32_t halo, void* stream);
-
-/* ragged rows: xg [G][rows + 2 * halo * B][D / G], utterance b's slab at row  row0[b] + 2 * halo * b  (its frames at + halo) */
-int sc_posconv_prep_seg(const sc_bf16* x, const int32_t* valid_len, sc_bf16* xz, sc_bf16* xg, const sc_segments* seg, int32_t D,
-                        int32_t G, int32_t halo, void* stream);
 
 /* HuBERT positional convolution on the slab layout above + bias + GELU + residual (speech_encoder_plus.py:32-37: grouped Conv1d,
  * kernel Kp = 128, padding 64, SamePad drops the last frame):
  *   out[b*R + t, g*Dg + n] = gelu(bias[g*Dg + n] + sum_j sum_ci w[g][n][j*Dg + ci] * xg[g][b][t + j][ci]) + residual[b*R + t, g*Dg + n]
- * w [G, Dg, Kp*Dg] tap-major per group, Dg = D / G in {48, 64}, Rp = rows of an xg slab (>= R + Kp - 1).  The input slab of a
- * (group, utterance, 512-frame block) stays in LDS for all taps; only the weights stream.  Same arithmetic as the sc_gemm_bf16
- * formulation (lda = Dg, K = Kp*Dg, act = 1, residual): bit-identical results. */
-int sc_posconv_bf16(const sc_bf16* xg, const sc_bf16* w, const float* bias, const sc_bf16* residual, sc_bf16* out, int32_t B,
-                    int32_t R, int32_t D, int32_t G, int32_t Kp, int32_t Rp, void* stream);
-
-/* ragged rows: the slab layout of sc_posconv_prep_seg (halo = Kp / 2), out / residual rows row0[b] + t */
-int sc_posconv_seg_bf16(const sc_bf16* xg, const sc_bf16* w, const float* bias, const sc_bf16* residual, sc_bf16* out,
-                        const sc_segments* seg, int32_t D, int32_t G, int32_t Kp, void* stream);
+ * w [G, Dg, Kp*Dg] tap-major per group, Dg = D / G in {48, 64}.  The input slab of a (group, utterance, 512-frame block) stays in LDS
+ * for all taps; only the weights stream.  Same arithmetic as the sc_gemm_bf16 formulation (lda = Dg, K = Kp*Dg, act = 1, residual):
+ * bit-identical results.
+ * Row layout (seg).
+ *   NULL: uniform rows.  Rp = rows of an xg slab (>= R + Kp - 1).
+ *   ragged rows: the slab layout sc_posconv_prep writes with seg (halo = Kp / 2), out / residual rows row0[b] + t.  B, R and Rp are
+ *     not read. */
+int sc_posconv_bf16(const sc_bf16* xg, const sc_bf16* w, const float* bias, const sc_bf16* residual, sc_bf16* out, const sc_segments* seg,
+                    int32_t B, int32_t R, int32_t D, int32_t G, int32_t Kp, int32_t Rp, void* stream);
 
 /* Weight gradient of that convolution (fully trainable HuBERT; speech_encoder_plus.py:29-40 under trainable: true):
  *   part[z][g][co][tap*Dg + ci] = sum over the z-th slice of slab rows m of  du[g][m][co] * xg[g][m + tap][ci]
@@ -363,20 +356,19 @@ int sc_posconv_wgrad_bf16(const sc_bf16* du, const sc_bf16* xg, float* part, int
  *        (layers of a residual stream differ by 1e-1 .. 1e-2 of their norm; summing first would cost those digits)
  *   normalize != 0: every h[n, row, :] passes through a non-affine LayerNorm(D, eps 1e-5) first
  *        (normalize_features=True, weighted_sum.py:41-42; used by the HuBERT-large recipes), D <= 1024
+ * Row layout (seg; both directions).
+ *   NULL: uniform rows, as above.
+ *   ragged hidden states -> uniform-pitch output (round 4): h [NL, seg->rows, D] in the segment layout; out / g stay [B, R, D] with
+ *     utterance b's frame t at out[b, t + row_off] for t + row_off < min(pitch_b + row_off, R), every other row of out is ZEROED (the
+ *     consumers - the CLS pooling kernels, the cascaded+/hybrid+ branches - keep a uniform [B, R, D] view and mask by length).  B must
+ *     equal seg->B (error otherwise).
  * ---------------------------------------------------------------------------------------------- */
-int sc_wsum_fwd(const sc_bf16* h, const float* w, int32_t NL, sc_bf16* out, int32_t B, int32_t R, int32_t D,
+int sc_wsum_fwd(const sc_bf16* h, const float* w, int32_t NL, sc_bf16* out, const sc_segments* seg, int32_t B, int32_t R, int32_t D,
                 int32_t row_off, int32_t normalize, void* stream);
 /* bwd `flags`: bit 0 = normalize, bit 1 = g is bf16 [B, R, D] instead of fp32 (the attention block of the cascaded+/hybrid+ branches
  * returns its input gradient as the bf16 rows its GEMM wrote; g 16-byte aligned either way) */
-int sc_wsum_bwd(const sc_bf16* h, const void* g, int32_t NL, float* dw_partial /*[nblk, NL]*/, int32_t nblk,
+int sc_wsum_bwd(const sc_bf16* h, const void* g, int32_t NL, float* dw_partial /*[nblk, NL]*/, int32_t nblk, const sc_segments* seg,
                 int32_t B, int32_t R, int32_t D, int32_t row_off, int32_t flags, void* stream);
-/* Ragged hidden states -> uniform-pitch output (round 4): h [NL, seg->rows, D] in the segment layout; out / g [B, Rout, D] with
- * utterance b's frame t at out[b, t + row_off] for t + row_off < min(pitch_b + row_off, Rout), every other row of out is ZEROED (the
- * consumers - the CLS pooling kernels, the cascaded+/hybrid+ branches - keep a uniform [B, Rout, D] view and mask by length). */
-int sc_wsum_fwd_seg(const sc_bf16* h, const float* w, int32_t NL, sc_bf16* out, const sc_segments* seg, int32_t Rout, int32_t D,
-                    int32_t row_off, int32_t normalize, void* stream);
-int sc_wsum_bwd_seg(const sc_bf16* h, const void* g, int32_t NL, float* dw_partial /*[nblk, NL]*/, int32_t nblk,
-                    const sc_segments* seg, int32_t Rout, int32_t D, int32_t row_off, int32_t flags, void* stream);
 /* The same sums over RAW hidden states (LayerNorm folded into the encoder GEMMs, see sc_gemm_args): layers n >= first_lazy of h hold
  * the rows in FRONT of the layer's final LayerNorm; stats [NL][B*R][8][2] fp32 their row statistics (ns valid strips), gamma / beta
  * [NL][D] the LayerNorm affines (rows < first_lazy unused): the summed state is (raw - mean) rstd gamma_n + beta_n in fp32. */
@@ -818,7 +810,7 @@ typedef struct {
     const float *qkv_colsum, *fc1_colsum;
     float *stats1, *out_stats;
     /* ---- ragged rows (round 4): seg != NULL (host pointer, seg->row0 device) - x / out / scratch hold seg->rows rows in the
-     * segment layout (R, T are then ignored; vt = per utterance [H, 64, pitch]); attn_work / n_attn_work as in sc_attn_fwd_seg_bf16 */
+     * segment layout (R, T are then ignored; vt = per utterance [H, 64, pitch]); attn_work / n_attn_work = work / nwork of sc_attn_fwd_bf16 */
     const sc_segments* seg;
     const int32_t* attn_work;
     int32_t n_attn_work;

@@ -110,19 +110,9 @@ SIGNATURES = {
     "sc_set_option": [c_int, c_int],
     "sc_hubert_layer_fwd": [ctypes.POINTER(HubertLayerArgs), c_void_p],
     "sc_gemm_bf16": [ctypes.POINTER(GemmArgs), c_void_p],
-    "sc_attn_fwd_bf16": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int,
-                         c_float, ctypes.c_uint32, c_void_p],
-    "sc_attn_fwd_seg_bf16": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, ctypes.POINTER(Segments), c_void_p, c_int, c_int, c_int,
-                             c_float, c_void_p, c_int, c_float, ctypes.c_uint32, c_void_p],
-    "sc_attn_fwd_relbias_bf16": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int,
-                                 c_void_p, c_int, c_float, ctypes.c_uint32, c_void_p],
-    "sc_attn_fwd_seg_relbias_bf16": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, ctypes.POINTER(Segments), c_void_p, c_int, c_int, c_int,
-                                     c_float, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, ctypes.c_uint32, c_void_p],
+    "sc_attn_fwd_bf16": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, ctypes.POINTER(Segments), c_void_p, c_int, c_int, c_int, c_int, c_int,
+                         c_float, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, ctypes.c_uint32, c_void_p],
     "sc_wavlm_gate_bf16": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p],
-    "sc_posconv_prep_seg": [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_void_p],
-    "sc_posconv_seg_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_void_p],
-    "sc_wsum_fwd_seg": [c_void_p, c_void_p, c_int, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_int, c_void_p],
-    "sc_wsum_bwd_seg": [c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(Segments), c_int, c_int, c_int, c_int, c_void_p],
     "sc_attn_bwd_bf16": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int,
                          c_int, c_int, c_float, c_int, c_float, ctypes.c_uint32, c_void_p],
@@ -142,11 +132,11 @@ SIGNATURES = {
                          c_int, c_void_p],
     "sc_softmax_fwd_f32": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, ctypes.c_float, c_void_p],
     "sc_conv0_ln_bwd": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
-    "sc_posconv_prep": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "sc_posconv_prep": [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_int, c_int, c_void_p],
     "sc_dropout_mult_f32": [c_void_p, c_i64, c_float, ctypes.c_uint32, c_void_p],
-    "sc_posconv_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "sc_wsum_fwd": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "sc_wsum_bwd": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "sc_posconv_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "sc_wsum_fwd": [c_void_p, c_void_p, c_int, c_void_p, ctypes.POINTER(Segments), c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "sc_wsum_bwd": [c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(Segments), c_int, c_int, c_int, c_int, c_int, c_void_p],
     "sc_wsum_lazy_fwd": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
                          c_void_p],
     "sc_wsum_lazy_bwd": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,

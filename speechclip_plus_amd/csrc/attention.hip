@@ -351,123 +351,60 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restric
 
 }  // namespace
 
-extern "C" int sc_attn_fwd_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len,
-                                sc_bf16* out, int64_t ldo, int32_t B, int32_t R, int32_t H, int32_t D, float scale,
-                                float* lse2, int32_t causal, float drop_p, uint32_t drop_seed, void* stream) {
-    SC_CHECK(qk && vt && valid_len && out, "sc_attn_fwd_bf16: null pointer");
-    // R % 128 != 0 (round 4): a last q-block of 32 / 64 / 96 rows; the K / V^T tiles of 64 keys may then read up to 32 rows / 64
-    // elements past an utterance (into the next one, or - behind the last - into slack the caller provides: 64 rows of qk, 64
-    // elements of vt); what they read there is masked
-    SC_CHECK(B > 0 && H > 0 && R > 0 && R % 8 == 0, "sc_attn_fwd_bf16: R=%d must be a positive multiple of 8", R);
+// The one forward entry: seg == NULL is the uniform layout (utterance b at row b R; B and R are read), otherwise the ragged one (row0[b],
+// a pitch per utterance; B and R are not read).  gate / table (both or neither) select the BIAS instances (WavLM).  Every check of either
+// layout, the grid and the DROP x BIAS choice live here, once.
+extern "C" int sc_attn_fwd_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
+                                const sc_segments* seg, const int32_t* work, int32_t nwork, int32_t B, int32_t R, int32_t H, int32_t D,
+                                float scale, const float* gate, const float* table, int32_t tmax, float* lse2, int32_t causal, float drop_p,
+                                uint32_t drop_seed, void* stream) {
+    const bool bias = gate || table;
+    SC_CHECK(qk && vt && valid_len && out && (!seg || seg->row0), "sc_attn_fwd_bf16: null pointer");
+    SC_CHECK(seg || (!work && nwork == 0), "sc_attn_fwd_bf16: a work list needs the segment layout (seg)");
+    SC_CHECK(!work || ((uintptr_t)work % 16) == 0, "sc_attn_fwd_bf16: the work list must be 16-byte aligned");
+    if (seg)
+        SC_CHECK(seg->B > 0 && seg->B < 65536 && H > 0 && seg->rows > 0 && seg->max_pitch > 0 && seg->max_pitch % SC_SEG_ROWS == 0 && (!work || nwork > 0),
+                 "sc_attn_fwd_bf16: B=%d rows=%d max_pitch=%d", seg->B, seg->rows, seg->max_pitch);
+    else
+        // R % 128 != 0 (round 4): a last q-block of 32 / 64 / 96 rows; the K / V^T tiles of 64 keys may then read up to 32 rows / 64
+        // elements past an utterance (into the next one, or - behind the last - into slack the caller provides: 64 rows of qk, 64
+        // elements of vt); what they read there is masked
+        SC_CHECK(B > 0 && H > 0 && R > 0 && R % 8 == 0, "sc_attn_fwd_bf16: R=%d must be a positive multiple of 8", R);
     SC_CHECK(D == H * 64, "sc_attn_fwd_bf16: head_dim must be 64 (D=%d, H=%d)", D, H);
-    SC_CHECK(causal == 0 || causal == 1 || causal == 32 || causal == 64, "sc_attn_fwd_bf16: causal=%d (0, 1, or a segment of 32 / 64 rows)", causal);
-    SC_CHECK(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || (int64_t)B * H * R * R < ((int64_t)1 << 32)),
-             "sc_attn_fwd_bf16: drop_p=%f (needs B*H*R*R < 2^32)", (double)drop_p);
+    // what the kernel takes as R (uniform: the pitch; ragged: the largest one, which sizes the q-block rectangle), and its rows_total /
+    // max_pitch: the ragged dropout and lse2 index and the gate index of either layout - the uniform plain instances read neither
+    const int pitch = seg ? seg->max_pitch : R, max_pitch = seg ? seg->max_pitch : 0;
+    if (bias) {
+        SC_CHECK(gate && table, "sc_attn_fwd_bf16: null gate / table");
+        SC_CHECK(causal == 0, "sc_attn_fwd_bf16: causal=%d - the relative-position bias is built without a causal mask", causal);
+        SC_CHECK(tmax >= pitch, "sc_attn_fwd_bf16: the table holds offsets up to +-(%d - 1), the row pitch is %d", tmax, pitch);
+        // dynamic LDS behind the 32 KiB of K / V^T buffers: (key tiles x 64 + 127) floats, kept within the 64 KiB a launch gets by default
+        SC_CHECK(((pitch + 63) / 64 * 64 + 127) * 4 <= 32 * 1024, "sc_attn_fwd_bf16: pitch %d needs more than 32 KiB of table", pitch);
+        SC_CHECK(seg || (int64_t)B * R < ((int64_t)1 << 31), "sc_attn_fwd_bf16: B*R=%lld rows", (long long)B * R);
+    } else if (seg) {
+        SC_CHECK(causal == 0 || causal == 1, "sc_attn_fwd_bf16: causal=%d", causal);
+    } else {
+        SC_CHECK(causal == 0 || causal == 1 || causal == 32 || causal == 64, "sc_attn_fwd_bf16: causal=%d (0, 1, or a segment of 32 / 64 rows)", causal);
+    }
+    if (seg)
+        SC_CHECK(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || (int64_t)H * seg->rows * seg->max_pitch < ((int64_t)1 << 32)),
+                 "sc_attn_fwd_bf16: drop_p=%f (needs H*rows*max_pitch < 2^32)", (double)drop_p);
+    else
+        SC_CHECK(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || (int64_t)B * H * R * R < ((int64_t)1 << 32)),
+                 "sc_attn_fwd_bf16: drop_p=%f (needs B*H*R*R < 2^32)", (double)drop_p);
     SC_CHECK(ldqk % 8 == 0 && ldo % 4 == 0 && ldqk >= 2 * D && ldo >= D, "sc_attn_fwd_bf16: bad leading dims");
-    SC_CHECK(((uintptr_t)qk % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)out % 8) == 0,
-             "sc_attn_fwd_bf16: alignment");
-    dim3 grid(((R + 127) / 128) * H * B);
-    if (drop_p > 0.f)
-        hipLaunchKernelGGL(attn_fwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, R,
-                           H, D, scale * 1.4426950408889634f, lse2, causal, drop_p, drop_seed, (const int32_t*)nullptr, (const int32_t*)nullptr, 0, 0, 0);
-    else
-        hipLaunchKernelGGL(attn_fwd_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, R,
-                           H, D, scale * 1.4426950408889634f, lse2, causal, drop_p, drop_seed, (const int32_t*)nullptr, (const int32_t*)nullptr, 0, 0, 0);
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sc_attn_fwd_seg_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
-                                    const sc_segments* seg, const int32_t* work, int32_t nwork, int32_t H, int32_t D, float scale,
-                                    float* lse2, int32_t causal, float drop_p, uint32_t drop_seed, void* stream) {
-    SC_CHECK(qk && vt && valid_len && out && seg && seg->row0, "sc_attn_fwd_seg_bf16: null pointer");
-    SC_CHECK(!work || ((uintptr_t)work % 16) == 0, "sc_attn_fwd_seg_bf16: the work list must be 16-byte aligned");
-    SC_CHECK(seg->B > 0 && seg->B < 65536 && H > 0 && seg->rows > 0 && seg->max_pitch > 0 && seg->max_pitch % SC_SEG_ROWS == 0 && (!work || nwork > 0),
-             "sc_attn_fwd_seg_bf16: B=%d rows=%d max_pitch=%d", seg->B, seg->rows, seg->max_pitch);
-    SC_CHECK(D == H * 64, "sc_attn_fwd_seg_bf16: head_dim must be 64 (D=%d, H=%d)", D, H);
-    SC_CHECK(causal == 0 || causal == 1, "sc_attn_fwd_seg_bf16: causal=%d", causal);
-    SC_CHECK(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || (int64_t)H * seg->rows * seg->max_pitch < ((int64_t)1 << 32)),
-             "sc_attn_fwd_seg_bf16: drop_p=%f (needs H*rows*max_pitch < 2^32)", (double)drop_p);
-    SC_CHECK(ldqk % 8 == 0 && ldo % 4 == 0 && ldqk >= 2 * D && ldo >= D, "sc_attn_fwd_seg_bf16: bad leading dims");
-    SC_CHECK(((uintptr_t)qk % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)out % 8) == 0, "sc_attn_fwd_seg_bf16: alignment");
-    const int nqb = (seg->max_pitch + 127) / 128;
-    const int npairs = work ? nwork : seg->B * nqb;
-    dim3 grid(npairs * H);
-    if (drop_p > 0.f)
-        hipLaunchKernelGGL(attn_fwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, seg->max_pitch,
-                           H, D, scale * 1.4426950408889634f, lse2, causal, drop_p, drop_seed, seg->row0, work, npairs, seg->rows, seg->max_pitch);
-    else
-        hipLaunchKernelGGL(attn_fwd_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, seg->max_pitch,
-                           H, D, scale * 1.4426950408889634f, lse2, causal, drop_p, drop_seed, seg->row0, work, npairs, seg->rows, seg->max_pitch);
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---- WavLM: the same kernel with the gated relative-position bias (BIAS = 1)
-namespace {
-int relbias_check(const char* who, const float* gate, const float* table, int32_t tmax, int32_t max_pitch, int32_t causal) {
-    SC_CHECK(gate && table, "%s: null gate / table", who);
-    SC_CHECK(causal == 0, "%s: causal=%d - the relative-position bias is built without a causal mask", who, causal);
-    SC_CHECK(tmax >= max_pitch, "%s: the table holds offsets up to +-(%d - 1), the row pitch is %d", who, tmax, max_pitch);
-    // dynamic LDS behind the 32 KiB of K / V^T buffers: (key tiles x 64 + 127) floats, kept within the 64 KiB a launch gets by default
-    SC_CHECK(((max_pitch + 63) / 64 * 64 + 127) * 4 <= 32 * 1024, "%s: pitch %d needs more than 32 KiB of table", who, max_pitch);
-    return 0;
-}
-}  // namespace
-
-extern "C" int sc_attn_fwd_relbias_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
-                                        int32_t B, int32_t R, int32_t H, int32_t D, float scale, const float* gate, const float* table,
-                                        int32_t tmax, float* lse2, int32_t causal, float drop_p, uint32_t drop_seed, void* stream) {
-    SC_CHECK(qk && vt && valid_len && out, "sc_attn_fwd_relbias_bf16: null pointer");
-    SC_CHECK(B > 0 && H > 0 && R > 0 && R % 8 == 0, "sc_attn_fwd_relbias_bf16: R=%d must be a positive multiple of 8", R);
-    SC_CHECK(D == H * 64, "sc_attn_fwd_relbias_bf16: head_dim must be 64 (D=%d, H=%d)", D, H);
-    if (relbias_check("sc_attn_fwd_relbias_bf16", gate, table, tmax, R, causal)) return -1;
-    SC_CHECK((int64_t)B * R < ((int64_t)1 << 31), "sc_attn_fwd_relbias_bf16: B*R=%lld rows", (long long)B * R);
-    SC_CHECK(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || (int64_t)B * H * R * R < ((int64_t)1 << 32)),
-             "sc_attn_fwd_relbias_bf16: drop_p=%f (needs B*H*R*R < 2^32)", (double)drop_p);
-    SC_CHECK(ldqk % 8 == 0 && ldo % 4 == 0 && ldqk >= 2 * D && ldo >= D, "sc_attn_fwd_relbias_bf16: bad leading dims");
-    SC_CHECK(((uintptr_t)qk % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)out % 8) == 0, "sc_attn_fwd_relbias_bf16: alignment");
-    dim3 grid(((R + 127) / 128) * H * B);
-    const size_t lds = (size_t)((R + 63) / 64 * 64 + 127) * 4;
-    // rows_total = B R: the kernel's gate index (the uniform plain instances never read it)
-    if (drop_p > 0.f)
-        hipLaunchKernelGGL((attn_fwd_kernel<1, 0, 1>), grid, dim3(256), lds, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, R, H, D,
-                           scale * 1.4426950408889634f, lse2, 0, drop_p, drop_seed, (const int32_t*)nullptr, (const int32_t*)nullptr, 0, B * R, 0,
-                           (long long*)nullptr, gate, table, tmax);
-    else
-        hipLaunchKernelGGL((attn_fwd_kernel<0, 0, 1>), grid, dim3(256), lds, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, R, H, D,
-                           scale * 1.4426950408889634f, lse2, 0, drop_p, drop_seed, (const int32_t*)nullptr, (const int32_t*)nullptr, 0, B * R, 0,
-                           (long long*)nullptr, gate, table, tmax);
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sc_attn_fwd_seg_relbias_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
-                                            const sc_segments* seg, const int32_t* work, int32_t nwork, int32_t H, int32_t D, float scale,
-                                            const float* gate, const float* table, int32_t tmax, float* lse2, int32_t causal, float drop_p,
-                                            uint32_t drop_seed, void* stream) {
-    SC_CHECK(qk && vt && valid_len && out && seg && seg->row0, "sc_attn_fwd_seg_relbias_bf16: null pointer");
-    SC_CHECK(!work || ((uintptr_t)work % 16) == 0, "sc_attn_fwd_seg_relbias_bf16: the work list must be 16-byte aligned");
-    SC_CHECK(seg->B > 0 && seg->B < 65536 && H > 0 && seg->rows > 0 && seg->max_pitch > 0 && seg->max_pitch % SC_SEG_ROWS == 0 && (!work || nwork > 0),
-             "sc_attn_fwd_seg_relbias_bf16: B=%d rows=%d max_pitch=%d", seg->B, seg->rows, seg->max_pitch);
-    SC_CHECK(D == H * 64, "sc_attn_fwd_seg_relbias_bf16: head_dim must be 64 (D=%d, H=%d)", D, H);
-    if (relbias_check("sc_attn_fwd_seg_relbias_bf16", gate, table, tmax, seg->max_pitch, causal)) return -1;
-    SC_CHECK(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || (int64_t)H * seg->rows * seg->max_pitch < ((int64_t)1 << 32)),
-             "sc_attn_fwd_seg_relbias_bf16: drop_p=%f (needs H*rows*max_pitch < 2^32)", (double)drop_p);
-    SC_CHECK(ldqk % 8 == 0 && ldo % 4 == 0 && ldqk >= 2 * D && ldo >= D, "sc_attn_fwd_seg_relbias_bf16: bad leading dims");
-    SC_CHECK(((uintptr_t)qk % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)out % 8) == 0, "sc_attn_fwd_seg_relbias_bf16: alignment");
-    const int nqb = (seg->max_pitch + 127) / 128;
-    const int npairs = work ? nwork : seg->B * nqb;
-    dim3 grid(npairs * H);
-    const size_t lds = (size_t)((seg->max_pitch + 63) / 64 * 64 + 127) * 4;
-    if (drop_p > 0.f)
-        hipLaunchKernelGGL((attn_fwd_kernel<1, 0, 1>), grid, dim3(256), lds, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, seg->max_pitch,
-                           H, D, scale * 1.4426950408889634f, lse2, 0, drop_p, drop_seed, seg->row0, work, npairs, seg->rows, seg->max_pitch,
-                           (long long*)nullptr, gate, table, tmax);
-    else
-        hipLaunchKernelGGL((attn_fwd_kernel<0, 0, 1>), grid, dim3(256), lds, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, seg->max_pitch,
-                           H, D, scale * 1.4426950408889634f, lse2, 0, drop_p, drop_seed, seg->row0, work, npairs, seg->rows, seg->max_pitch,
-                           (long long*)nullptr, gate, table, tmax);
+    SC_CHECK(((uintptr_t)qk % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)out % 8) == 0, "sc_attn_fwd_bf16: alignment");
+    const int nqb = (pitch + 127) / 128;
+    const int npairs = !seg ? 0 : work ? nwork : seg->B * nqb;
+    const int rows_total = seg ? seg->rows : bias ? B * R : 0;
+    const dim3 grid(seg ? npairs * H : nqb * H * B);
+    const size_t lds = bias ? (size_t)((pitch + 63) / 64 * 64 + 127) * 4 : 0;
+    const bool drop = drop_p > 0.f;
+    auto* const kernel = !bias ? (drop ? attn_fwd_kernel<1, 0, 0> : attn_fwd_kernel<0, 0, 0>)
+                               : (drop ? attn_fwd_kernel<1, 0, 1> : attn_fwd_kernel<0, 0, 1>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, (hipStream_t)stream, qk, ldqk, vt, valid_len, out, ldo, pitch, H, D,
+                       scale * 1.4426950408889634f, lse2, causal, drop_p, drop_seed, seg ? seg->row0 : (const int32_t*)nullptr, work,
+                       npairs, rows_total, max_pitch, (long long*)nullptr, gate, table, bias ? tmax : 0);
     SC_LAUNCH_CHECK();
     return 0;
 }

@@ -64,11 +64,9 @@ extern "C" int sc_hubert_layer_fwd(const sc_hubert_layer_args* p, void* stream) 
     const int M = seg ? seg->rows : p->B * p->R, D = p->D, F = p->F, H = p->H;
     const float scale = 0.125f;       // head_dim 64
     const int32_t* chunk = seg ? seg->chunk : nullptr;
-    auto attention = [&]() -> int {
-        if (seg)
-            return sc_attn_fwd_seg_bf16(p->qk, 2 * D, p->vt, p->valid_len, p->ctx, D, seg, p->attn_work, p->n_attn_work, H, D, scale, nullptr, 0,
-                                        p->p_attn, p->seed_attn, stream);
-        return sc_attn_fwd_bf16(p->qk, 2 * D, p->vt, p->valid_len, p->ctx, D, p->B, p->R, H, D, scale, nullptr, 0, p->p_attn, p->seed_attn, stream);
+    auto attention = [&]() -> int {      // the work list belongs to the segment layout: uniform rows never read the two fields
+        return sc_attn_fwd_bf16(p->qk, 2 * D, p->vt, p->valid_len, p->ctx, D, seg, seg ? p->attn_work : nullptr, seg ? p->n_attn_work : 0, p->B, p->R,
+                                H, D, scale, nullptr, nullptr, 0, nullptr, 0, p->p_attn, p->seed_attn, stream);
     };
     int rc;
     if (p->fused_ln) {

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(NW * 64) void posconv_kernel(const uint16_t* __rest
 
 template <int DG, int NW>
 static int launch_posconv(const uint16_t* xg, const uint16_t* w, const float* bias, const uint16_t* res, uint16_t* out, int B, int R,
-                          int D, int G, int Kp, int Rp, hipStream_t s, const int32_t* row0 = nullptr, int seg_rows = 0) {
+                          int D, int G, int Kp, int Rp, hipStream_t s, const int32_t* row0 /* NULL: uniform rows */, int seg_rows) {
     constexpr int PC_ROWS = NW * 64;
     constexpr int LDS = (PC_ROWS + 128) * 128 + 3 * (2 * DG / 32) * DG * 64;
     static sc_lds_attr_once attr;
@@ -207,39 +207,33 @@ static int launch_posconv(const uint16_t* xg, const uint16_t* w, const float* bi
 
 }  // namespace
 
+// seg == NULL: uniform rows, xg [G, B, Rp, Dg].  seg: ragged rows on the slab layout of sc_posconv_prep (B / R / Rp are not read: the
+// kernel walks seg->B utterances of up to R = max_pitch frames, every slab carries R + Kp rows of address room)
 extern "C" int sc_posconv_bf16(const sc_bf16* xg, const sc_bf16* w, const float* bias, const sc_bf16* residual, sc_bf16* out,
-                               int32_t B, int32_t R, int32_t D, int32_t G, int32_t Kp, int32_t Rp, void* stream) {
-    SC_CHECK(xg && w && out, "sc_posconv_bf16: null pointer");
-    SC_CHECK(B > 0 && R > 0 && G > 0 && D % G == 0, "sc_posconv_bf16: bad shape B=%d R=%d D=%d G=%d", B, R, D, G);
+                               const sc_segments* seg, int32_t B, int32_t R, int32_t D, int32_t G, int32_t Kp, int32_t Rp, void* stream) {
+    SC_CHECK(xg && w && out && (!seg || seg->row0), "sc_posconv_bf16: null pointer");
+    if (seg)
+        SC_CHECK(seg->B > 0 && seg->max_pitch > 0 && seg->rows > 0 && G > 0 && D % G == 0, "sc_posconv_bf16: bad shape B=%d D=%d G=%d", seg->B, D, G);
+    else
+        SC_CHECK(B > 0 && R > 0 && G > 0 && D % G == 0, "sc_posconv_bf16: bad shape B=%d R=%d D=%d G=%d", B, R, D, G);
     const int DG = D / G;
     SC_CHECK(DG == 48 || DG == 64, "sc_posconv_bf16: channels per group must be 48 or 64 (D=%d, G=%d)", D, G);
-    SC_CHECK(Kp == 128 && Rp >= R + Kp - 1, "sc_posconv_bf16: kernel must be 128 taps and Rp >= R + 127 (Kp=%d, Rp=%d)", Kp, Rp);
+    if (seg)
+        SC_CHECK(Kp == 128, "sc_posconv_bf16: kernel must be 128 taps (Kp=%d)", Kp);
+    else
+        SC_CHECK(Kp == 128 && Rp >= R + Kp - 1, "sc_posconv_bf16: kernel must be 128 taps and Rp >= R + 127 (Kp=%d, Rp=%d)", Kp, Rp);
     SC_CHECK(((uintptr_t)xg % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)out % 8) == 0 &&
                  (!residual || ((uintptr_t)residual % 8) == 0) && (!bias || ((uintptr_t)bias % 16) == 0),
              "sc_posconv_bf16: alignment");
     hipStream_t s = (hipStream_t)stream;
     const uint16_t *xp = (const uint16_t*)xg, *wp = (const uint16_t*)w, *rp = (const uint16_t*)residual;
     uint16_t* op = (uint16_t*)out;
+    const int32_t* row0 = nullptr;
+    int seg_rows = 0;
+    if (seg) B = seg->B, R = seg->max_pitch, Rp = R + Kp, row0 = seg->row0, seg_rows = seg->rows;
     // Dg = 48: 256-frame workgroups of 4 waves, TWO per CU (76 KiB of LDS each; they drift apart, so one's operand waits and barrier
     // fall under the other's MFMAs: 283 vs 306 us at the step's shape); Dg = 64: its 96 KiB allow one workgroup per CU, 8 waves x 512 frames
     // (396 vs 514 us)
-    return DG == 48 ? launch_posconv<48, 4>(xp, wp, bias, rp, op, B, R, D, G, Kp, Rp, s) : launch_posconv<64, 8>(xp, wp, bias, rp, op, B, R, D, G, Kp, Rp, s);
-}
-
-extern "C" int sc_posconv_seg_bf16(const sc_bf16* xg, const sc_bf16* w, const float* bias, const sc_bf16* residual, sc_bf16* out,
-                                   const sc_segments* seg, int32_t D, int32_t G, int32_t Kp, void* stream) {
-    SC_CHECK(xg && w && out && seg && seg->row0, "sc_posconv_seg_bf16: null pointer");
-    SC_CHECK(seg->B > 0 && seg->max_pitch > 0 && seg->rows > 0 && G > 0 && D % G == 0, "sc_posconv_seg_bf16: bad shape B=%d D=%d G=%d", seg->B, D, G);
-    const int DG = D / G;
-    SC_CHECK(DG == 48 || DG == 64, "sc_posconv_seg_bf16: channels per group must be 48 or 64 (D=%d, G=%d)", D, G);
-    SC_CHECK(Kp == 128, "sc_posconv_seg_bf16: kernel must be 128 taps (Kp=%d)", Kp);
-    SC_CHECK(((uintptr_t)xg % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)out % 8) == 0 &&
-                 (!residual || ((uintptr_t)residual % 8) == 0) && (!bias || ((uintptr_t)bias % 16) == 0),
-             "sc_posconv_seg_bf16: alignment");
-    hipStream_t s = (hipStream_t)stream;
-    const uint16_t *xp = (const uint16_t*)xg, *wp = (const uint16_t*)w, *rp = (const uint16_t*)residual;
-    uint16_t* op = (uint16_t*)out;
-    const int R = seg->max_pitch;
-    return DG == 48 ? launch_posconv<48, 4>(xp, wp, bias, rp, op, seg->B, R, D, G, Kp, R + Kp, s, seg->row0, seg->rows)
-                    : launch_posconv<64, 8>(xp, wp, bias, rp, op, seg->B, R, D, G, Kp, R + Kp, s, seg->row0, seg->rows);
+    return DG == 48 ? launch_posconv<48, 4>(xp, wp, bias, rp, op, B, R, D, G, Kp, Rp, s, row0, seg_rows)
+                    : launch_posconv<64, 8>(xp, wp, bias, rp, op, B, R, D, G, Kp, Rp, s, row0, seg_rows);
 }

@@ -711,25 +711,59 @@ int wsum_bwd_launch(const uint16_t* h, const void* gv, int NL, float* dw_partial
     return 0;
 }
 
+// instantiated here, in this order, so that the uniform kernels keep their place in the code object in front of the ragged ones
+template int wsum_fwd_launch(const uint16_t*, const float*, int, uint16_t*, const UniformRows&, int, int, bool, int, hipStream_t);
+template int wsum_bwd_launch(const uint16_t*, const void*, int, float*, int, const UniformRows&, int, int, int, hipStream_t);
+
 }  // namespace
 
-extern "C" int sc_wsum_fwd(const sc_bf16* h, const float* w, int32_t NL, sc_bf16* out, int32_t B, int32_t R, int32_t D,
-                           int32_t row_off, int32_t normalize, void* stream) {
-    SC_CHECK(h && w && out, "sc_wsum_fwd: null pointer");
-    SC_CHECK(NL >= 1 && NL <= 32 && D % 8 == 0 && row_off >= 0 && row_off < R, "sc_wsum_fwd: bad NL/D/row_off");
+// seg == NULL: uniform rows.  seg: h in the ragged layout, out / g a uniform [B, R, D] buffer (B must equal seg->B).
+extern "C" int sc_wsum_fwd(const sc_bf16* h, const float* w, int32_t NL, sc_bf16* out, const sc_segments* seg, int32_t B, int32_t R,
+                           int32_t D, int32_t row_off, int32_t normalize, void* stream) {
+    SC_CHECK(h && w && out && (!seg || seg->row0), "sc_wsum_fwd: null pointer");
+    SC_CHECK(NL >= 1 && NL <= 32 && D % 8 == 0 && row_off >= 0 && row_off < R && (!seg || (seg->B > 0 && seg->rows > 0)), "sc_wsum_fwd: bad NL/D/row_off");
+    SC_CHECK(!seg || B == seg->B, "sc_wsum_fwd: B=%d against seg->B=%d", B, seg->B);
     if (normalize) SC_CHECK(D <= 1024, "sc_wsum_fwd: normalised variant needs D <= 1024 (got %d)", D);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t plane = seg ? (int64_t)seg->rows * D : 0;
+    if (seg && !normalize && (NL == 13 || NL == 25) && (int64_t)R * (D / 8) < (1ll << 30) && B <= 65535 && !sc_option(5)) {      // option 5: A/B switch (tools/)
+        const dim3 g2((unsigned)(((int64_t)R * (D / 8) + 255) / 256), (unsigned)B);
+        if (NL == 13) hipLaunchKernelGGL(wsum_fwd_seg_fixed_kernel<13>, g2, dim3(256), 0, s, h, w, out, seg->row0, R, D, row_off, plane);
+        else hipLaunchKernelGGL(wsum_fwd_seg_fixed_kernel<25>, g2, dim3(256), 0, s, h, w, out, seg->row0, R, D, row_off, plane);
+        SC_LAUNCH_CHECK();
+        return 0;
+    }
     const int64_t rows = (int64_t)B * R, total = rows * (D / 8);
     const int grid = normalize ? (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096) : (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    return wsum_fwd_launch(h, w, NL, out, UniformRows{B, R}, D, row_off, normalize, grid, (hipStream_t)stream);
+    return seg ? wsum_fwd_launch(h, w, NL, out, SegRows{seg->row0, B, R, plane}, D, row_off, normalize, grid, s)
+               : wsum_fwd_launch(h, w, NL, out, UniformRows{B, R}, D, row_off, normalize, grid, s);
 }
 
-extern "C" int sc_wsum_bwd(const sc_bf16* h, const void* gv, int32_t NL, float* dw_partial, int32_t nblk, int32_t B,
+extern "C" int sc_wsum_bwd(const sc_bf16* h, const void* gv, int32_t NL, float* dw_partial, int32_t nblk, const sc_segments* seg, int32_t B,
                            int32_t R, int32_t D, int32_t row_off, int32_t flags, void* stream) {
-    SC_CHECK(h && gv && dw_partial, "sc_wsum_bwd: null pointer");
-    SC_CHECK(NL >= 1 && NL <= 32 && D % 8 == 0 && nblk >= 1 && row_off >= 0 && row_off < R, "sc_wsum_bwd: bad args");
+    SC_CHECK(h && gv && dw_partial && (!seg || seg->row0), "sc_wsum_bwd: null pointer");
     SC_CHECK(((uintptr_t)gv % 16) == 0, "sc_wsum_bwd: g must be 16-byte aligned");
-    if (flags & 1) SC_CHECK(D <= 1024, "sc_wsum_bwd: normalised variant needs D <= 1024 (got %d)", D);
-    return wsum_bwd_launch(h, gv, NL, dw_partial, nblk, UniformRows{B, R}, D, row_off, flags, (hipStream_t)stream);
+    const bool normalize = flags & 1, g16 = flags & 2;         // bit 1: g is bf16
+    SC_CHECK(NL >= 1 && NL <= 32 && D % 8 == 0 && nblk >= 1 && row_off >= 0 && row_off < R && (!seg || (seg->B > 0 && seg->rows > 0)), "sc_wsum_bwd: bad args");
+    SC_CHECK(!seg || B == seg->B, "sc_wsum_bwd: B=%d against seg->B=%d", B, seg->B);
+    if (normalize) SC_CHECK(D <= 1024, "sc_wsum_bwd: normalised variant needs D <= 1024 (got %d)", D);
+    hipStream_t s = (hipStream_t)stream;
+    if (!seg) return wsum_bwd_launch(h, gv, NL, dw_partial, nblk, UniformRows{B, R}, D, row_off, flags, s);
+    const int64_t plane = (int64_t)seg->rows * D;
+    if (!normalize && (NL == 13 || NL == 25) && (int64_t)B * R * (D / 8) < (1ll << 31) && !sc_option(5)) {      // option 5: A/B switch (tools/)
+        const float* g = (const float*)gv;
+        const uint16_t* gh = (const uint16_t*)gv;
+        if (NL == 13) {
+            if (g16) hipLaunchKernelGGL((wsum_bwd_seg_fixed_kernel<13, uint16_t>), dim3(nblk), dim3(256), 0, s, h, gh, dw_partial, seg->row0, B, R, D, row_off, plane);
+            else hipLaunchKernelGGL((wsum_bwd_seg_fixed_kernel<13, float>), dim3(nblk), dim3(256), 0, s, h, g, dw_partial, seg->row0, B, R, D, row_off, plane);
+        } else {
+            if (g16) hipLaunchKernelGGL((wsum_bwd_seg_fixed_kernel<25, uint16_t>), dim3(nblk), dim3(256), 0, s, h, gh, dw_partial, seg->row0, B, R, D, row_off, plane);
+            else hipLaunchKernelGGL((wsum_bwd_seg_fixed_kernel<25, float>), dim3(nblk), dim3(256), 0, s, h, g, dw_partial, seg->row0, B, R, D, row_off, plane);
+        }
+        SC_LAUNCH_CHECK();
+        return 0;
+    }
+    return wsum_bwd_launch(h, gv, NL, dw_partial, nblk, SegRows{seg->row0, B, R, plane}, D, row_off, flags, s);
 }
 
 extern "C" int sc_wsum_lazy_fwd(const sc_bf16* h, const float* w, int32_t NL, sc_bf16* out, int32_t B, int32_t R, int32_t D,
@@ -758,72 +792,24 @@ extern "C" int sc_wsum_lazy_bwd(const sc_bf16* h, const float* g, int32_t NL, fl
     return 0;
 }
 
-extern "C" int sc_posconv_prep(const sc_bf16* x, const int32_t* valid_len, sc_bf16* xz, sc_bf16* xg, int32_t B,
+// seg == NULL: uniform rows (posconv_prep_kernel).  seg: ragged rows (posconv_prep_seg_kernel, which finds a row's utterance in
+// seg->chunk; B / R are not read)
+extern "C" int sc_posconv_prep(const sc_bf16* x, const int32_t* valid_len, sc_bf16* xz, sc_bf16* xg, const sc_segments* seg, int32_t B,
                                int32_t R, int32_t D, int32_t G, int32_t halo, void* stream) {
-    SC_CHECK(x && valid_len && xz && xg, "sc_posconv_prep: null pointer");
-    SC_CHECK(G > 0 && D % G == 0 && (D / G) % 8 == 0, "sc_posconv_prep: D/G=%d must be a multiple of 8", D / G);
-    const int64_t total = (int64_t)B * R * (D / 8);
-    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(posconv_prep_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, valid_len, xz, xg, B, R, D, G, halo);
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sc_wsum_fwd_seg(const sc_bf16* h, const float* w, int32_t NL, sc_bf16* out, const sc_segments* seg, int32_t Rout, int32_t D,
-                               int32_t row_off, int32_t normalize, void* stream) {
-    SC_CHECK(h && w && out && seg && seg->row0, "sc_wsum_fwd_seg: null pointer");
-    SC_CHECK(NL >= 1 && NL <= 32 && D % 8 == 0 && row_off >= 0 && Rout > row_off && seg->B > 0 && seg->rows > 0, "sc_wsum_fwd_seg: bad NL/D/row_off");
-    if (normalize) SC_CHECK(D <= 1024, "sc_wsum_fwd_seg: normalised variant needs D <= 1024 (got %d)", D);
-    const int B = seg->B;
-    const int64_t plane = (int64_t)seg->rows * D;
-    hipStream_t s = (hipStream_t)stream;
-    if (!normalize && (NL == 13 || NL == 25) && (int64_t)Rout * (D / 8) < (1ll << 30) && B <= 65535 && !sc_option(5)) {      // option 5: A/B switch (tools/)
-        const dim3 g2((unsigned)(((int64_t)Rout * (D / 8) + 255) / 256), (unsigned)B);
-        if (NL == 13) hipLaunchKernelGGL(wsum_fwd_seg_fixed_kernel<13>, g2, dim3(256), 0, s, h, w, out, seg->row0, Rout, D, row_off, plane);
-        else hipLaunchKernelGGL(wsum_fwd_seg_fixed_kernel<25>, g2, dim3(256), 0, s, h, w, out, seg->row0, Rout, D, row_off, plane);
-        SC_LAUNCH_CHECK();
-        return 0;
+    SC_CHECK(x && valid_len && xz && xg && (!seg || seg->chunk), "sc_posconv_prep: null pointer");
+    if (seg) {
+        SC_CHECK(G > 0 && D % G == 0 && (D / G) % 8 == 0 && seg->rows > 0 && seg->rows % SC_SEG_ROWS == 0 && seg->B > 0 && halo > 0,
+                 "sc_posconv_prep: D/G=%d must be a multiple of 8, rows a multiple of 8", D / G);
+        SC_CHECK(((uintptr_t)seg->chunk % 16) == 0, "sc_posconv_prep: chunk table must be 16-byte aligned");
+    } else {
+        SC_CHECK(G > 0 && D % G == 0 && (D / G) % 8 == 0, "sc_posconv_prep: D/G=%d must be a multiple of 8", D / G);
     }
-    const int64_t rows = (int64_t)B * Rout, total = rows * (D / 8);
-    const int grid = normalize ? (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096) : (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    return wsum_fwd_launch(h, w, NL, out, SegRows{seg->row0, B, Rout, plane}, D, row_off, normalize, grid, s);
-}
-
-extern "C" int sc_wsum_bwd_seg(const sc_bf16* h, const void* gv, int32_t NL, float* dw_partial, int32_t nblk, const sc_segments* seg,
-                               int32_t Rout, int32_t D, int32_t row_off, int32_t flags, void* stream) {
-    SC_CHECK(h && gv && dw_partial && seg && seg->row0, "sc_wsum_bwd_seg: null pointer");
-    SC_CHECK(((uintptr_t)gv % 16) == 0, "sc_wsum_bwd_seg: g must be 16-byte aligned");
-    const bool normalize = flags & 1, g16 = flags & 2;         // bit 1: g is bf16
-    SC_CHECK(NL >= 1 && NL <= 32 && D % 8 == 0 && nblk >= 1 && row_off >= 0 && Rout > row_off && seg->B > 0 && seg->rows > 0, "sc_wsum_bwd_seg: bad args");
-    if (normalize) SC_CHECK(D <= 1024, "sc_wsum_bwd_seg: normalised variant needs D <= 1024 (got %d)", D);
-    const int B = seg->B;
-    const int64_t plane = (int64_t)seg->rows * D;
-    hipStream_t s = (hipStream_t)stream;
-    if (!normalize && (NL == 13 || NL == 25) && (int64_t)B * Rout * (D / 8) < (1ll << 31) && !sc_option(5)) {      // option 5: A/B switch (tools/)
-        const float* g = (const float*)gv;
-        const uint16_t* gh = (const uint16_t*)gv;
-        if (NL == 13) {
-            if (g16) hipLaunchKernelGGL((wsum_bwd_seg_fixed_kernel<13, uint16_t>), dim3(nblk), dim3(256), 0, s, h, gh, dw_partial, seg->row0, B, Rout, D, row_off, plane);
-            else hipLaunchKernelGGL((wsum_bwd_seg_fixed_kernel<13, float>), dim3(nblk), dim3(256), 0, s, h, g, dw_partial, seg->row0, B, Rout, D, row_off, plane);
-        } else {
-            if (g16) hipLaunchKernelGGL((wsum_bwd_seg_fixed_kernel<25, uint16_t>), dim3(nblk), dim3(256), 0, s, h, gh, dw_partial, seg->row0, B, Rout, D, row_off, plane);
-            else hipLaunchKernelGGL((wsum_bwd_seg_fixed_kernel<25, float>), dim3(nblk), dim3(256), 0, s, h, g, dw_partial, seg->row0, B, Rout, D, row_off, plane);
-        }
-        SC_LAUNCH_CHECK();
-        return 0;
-    }
-    return wsum_bwd_launch(h, gv, NL, dw_partial, nblk, SegRows{seg->row0, B, Rout, plane}, D, row_off, flags, s);
-}
-
-extern "C" int sc_posconv_prep_seg(const sc_bf16* x, const int32_t* valid_len, sc_bf16* xz, sc_bf16* xg, const sc_segments* seg, int32_t D,
-                                   int32_t G, int32_t halo, void* stream) {
-    SC_CHECK(x && valid_len && xz && xg && seg && seg->chunk, "sc_posconv_prep_seg: null pointer");
-    SC_CHECK(G > 0 && D % G == 0 && (D / G) % 8 == 0 && seg->rows > 0 && seg->rows % SC_SEG_ROWS == 0 && seg->B > 0 && halo > 0,
-             "sc_posconv_prep_seg: D/G=%d must be a multiple of 8, rows a multiple of 8", D / G);
-    SC_CHECK(((uintptr_t)seg->chunk % 16) == 0, "sc_posconv_prep_seg: chunk table must be 16-byte aligned");
-    const int64_t total = (int64_t)seg->rows * (D / 8);
+    const int64_t total = (seg ? (int64_t)seg->rows : (int64_t)B * R) * (D / 8);
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(posconv_prep_seg_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, valid_len, xz, xg, seg->chunk, seg->rows, seg->B, D, G, halo);
+    if (seg)
+        hipLaunchKernelGGL(posconv_prep_seg_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, valid_len, xz, xg, seg->chunk, seg->rows, seg->B, D, G, halo);
+    else
+        hipLaunchKernelGGL(posconv_prep_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, valid_len, xz, xg, B, R, D, G, halo);
     SC_LAUNCH_CHECK();
     return 0;
 }

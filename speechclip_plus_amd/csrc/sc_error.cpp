@@ -39,7 +39,7 @@ extern "C" uint32_t sc_hash32(uint32_t x) {
 }
 
 extern "C" const char* sc_last_error(void) { return g_err; }
-extern "C" int sc_abi_version(void) { return 6; }
+extern "C" int sc_abi_version(void) { return 7; }
 // 1 = the diagnostics build (timing-only / stamped kernels + the LayerNorm-folded GEMMs), 0 = the product library
 extern "C" int sc_is_diag_build(void) {
 #ifdef SC_DIAG_BUILD

@@ -19,6 +19,11 @@ def _p(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _seg(seg: Optional["RowSegments"]):
+    """the ``seg`` argument of an entry point that takes either row layout: NULL = uniform rows"""
+    return seg.ref() if seg is not None else None
+
+
 def aligned16(t: torch.Tensor) -> torch.Tensor:
     """``t`` itself when its storage offset is 16-byte aligned, else a fresh copy (trainable parameters are views into the
     optimiser's flat buffer at 4-byte granularity; kernels that load 16 bytes per lane need aligned bases)."""
@@ -317,35 +322,23 @@ def attn_fwd(qk: torch.Tensor, vt: torch.Tensor, valid_len: torch.Tensor, out: t
              gate: Optional[torch.Tensor] = None, table: Optional[torch.Tensor] = None) -> None:
     """``seg``: ragged rows (B / R are then ignored; vt = per utterance [H, 64, pitch] back to back, as gemm_raw(seg=...) writes it).
     ``gate`` [H, rows] / ``table`` [H, 2 Tmax - 1] fp32 (both or neither): WavLM's gated relative-position bias
-    gate[h, i] * table[h, Tmax - 1 + j - i] on the scaled scores (sc_attn_fwd_relbias_bf16; ``wavlm_gate`` writes the gate)."""
+    gate[h, i] * table[h, Tmax - 1 + j - i] on the scaled scores (``wavlm_gate`` writes the gate).  One entry point: sc_attn_fwd_bf16."""
     assert qk.dtype == torch.bfloat16 and vt.dtype == torch.bfloat16 and out.dtype == torch.bfloat16
     assert valid_len.dtype == torch.int32
     assert (gate is None) == (table is None), "attn_fwd: gate and table come together"
     if _timer is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
+    tmax = 0
     if gate is not None:
         rows = seg.rows if seg is not None else B * R
         assert gate.dtype == torch.float32 and gate.is_contiguous() and gate.shape == (H, rows), (gate.shape, H, rows)
         assert table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2 and table.shape[0] == H and table.shape[1] % 2 == 1
         tmax = (table.shape[1] + 1) // 2
-        if seg is not None:
-            check(lib().sc_attn_fwd_seg_relbias_bf16(_p(qk), qk.stride(0), _p(vt), _p(valid_len), _p(out), out.stride(0), seg.ref(),
-                                                     _p(seg.work) if use_work else _p(None), seg.n_work if use_work else 0, H, D, float(scale),
-                                                     _p(gate), _p(table), tmax, _p(lse2), int(causal), float(drop_p),
-                                                     int(drop_seed) & 0xffffffff, _stream()), "sc_attn_fwd_seg_relbias_bf16")
-        else:
-            check(lib().sc_attn_fwd_relbias_bf16(_p(qk), qk.stride(0), _p(vt), _p(valid_len), _p(out), out.stride(0), B, R, H, D, float(scale),
-                                                 _p(gate), _p(table), tmax, _p(lse2), int(causal), float(drop_p),
-                                                 int(drop_seed) & 0xffffffff, _stream()), "sc_attn_fwd_relbias_bf16")
-    elif seg is not None:
-        check(lib().sc_attn_fwd_seg_bf16(_p(qk), qk.stride(0), _p(vt), _p(valid_len), _p(out), out.stride(0), seg.ref(),
-                                         _p(seg.work) if use_work else _p(None), seg.n_work if use_work else 0, H, D, float(scale), _p(lse2),
-                                         int(causal), float(drop_p), int(drop_seed) & 0xffffffff, _stream()), "sc_attn_fwd_seg_bf16")
-    else:
-        check(lib().sc_attn_fwd_bf16(_p(qk), qk.stride(0), _p(vt), _p(valid_len), _p(out), out.stride(0), B, R, H, D,
-                                     float(scale), _p(lse2), int(causal), float(drop_p), int(drop_seed) & 0xffffffff, _stream()),
-              "sc_attn_fwd_bf16")
+    work, nwork = (seg.work, seg.n_work) if seg is not None and use_work else (None, 0)
+    check(lib().sc_attn_fwd_bf16(_p(qk), qk.stride(0), _p(vt), _p(valid_len), _p(out), out.stride(0), _seg(seg), _p(work), nwork, B, R, H, D,
+                                 float(scale), _p(gate), _p(table), tmax, _p(lse2), int(causal), float(drop_p), int(drop_seed) & 0xffffffff,
+                                 _stream()), "sc_attn_fwd_bf16")
     if _timer is not None:
         ev1.record()
         _timer.add("attn_fwd_relbias" if gate is not None else "attn_fwd", ev0, ev1, float(alg_flops))
@@ -1222,43 +1215,40 @@ def conv0_layernorm_gelu_bwd(wav_pad: torch.Tensor, w0: torch.Tensor, bias: Opti
 
 def posconv_prep(x: torch.Tensor, valid_len: torch.Tensor, xz: torch.Tensor, xg: torch.Tensor, B: int, R: int, D: int,
                  G: int, halo: int) -> None:
-    check(lib().sc_posconv_prep(_p(x), _p(valid_len), _p(xz), _p(xg), B, R, D, G, halo, _stream()), "sc_posconv_prep")
+    check(lib().sc_posconv_prep(_p(x), _p(valid_len), _p(xz), _p(xg), None, B, R, D, G, halo, _stream()), "sc_posconv_prep")
 
 
 def posconv_prep_seg(x: torch.Tensor, valid_len: torch.Tensor, xz: torch.Tensor, xg: torch.Tensor, seg: "RowSegments", D: int, G: int,
                      halo: int) -> None:
     """ragged rows: xg = flat [G, rows + 2 halo B, D / G] slab buffer (numel at least that), utterance b at slab row row0[b] + 2 halo b"""
     assert xg.numel() >= (seg.rows + 2 * halo * seg.B) * D
-    check(lib().sc_posconv_prep_seg(_p(x), _p(valid_len), _p(xz), _p(xg), seg.ref(), D, G, halo, _stream()), "sc_posconv_prep_seg")
+    check(lib().sc_posconv_prep(_p(x), _p(valid_len), _p(xz), _p(xg), seg.ref(), 0, 0, D, G, halo, _stream()), "sc_posconv_prep")
 
 
-def posconv_seg(xg: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], residual: Optional[torch.Tensor], out: torch.Tensor,
-                seg: "RowSegments", D: int, G: int, Kp: int, alg_rows: Optional[int] = None) -> None:
+def _posconv(xg, w, bias, residual, out, seg, B, R, D, G, Kp, Rp, alg_rows) -> None:
+    """sc_posconv_bf16 in its timer bracket; ``alg_rows``: the rows the launch is credited with"""
     assert xg.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and out.dtype == torch.bfloat16
     if _timer is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    check(lib().sc_posconv_seg_bf16(_p(xg), _p(w), _p(bias), _p(residual), _p(out), seg.ref(), D, G, Kp, _stream()), "sc_posconv_seg_bf16")
+    check(lib().sc_posconv_bf16(_p(xg), _p(w), _p(bias), _p(residual), _p(out), _seg(seg), B, R, D, G, Kp, Rp, _stream()), "sc_posconv_bf16")
     if _timer is not None:
         ev1.record()
-        _timer.add("posconv", ev0, ev1, 2.0 * (seg.rows if alg_rows is None else alg_rows) * D * Kp * (D // G))
+        _timer.add("posconv", ev0, ev1, 2.0 * alg_rows * D * Kp * (D // G))
+
+
+def posconv_seg(xg: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], residual: Optional[torch.Tensor], out: torch.Tensor,
+                seg: "RowSegments", D: int, G: int, Kp: int, alg_rows: Optional[int] = None) -> None:
+    """``posconv`` on ragged rows: the slab layout of ``posconv_prep_seg``, out / residual rows row0[b] + t"""
+    _posconv(xg, w, bias, residual, out, seg, 0, 0, D, G, Kp, 0, seg.rows if alg_rows is None else alg_rows)
 
 
 def posconv(xg: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], residual: Optional[torch.Tensor], out: torch.Tensor,
             B: int, R: int, D: int, G: int, Kp: int, alg_rows: Optional[int] = None) -> None:
     """HuBERT positional convolution + bias + GELU + residual on the slab layout of ``posconv_prep`` (sc_posconv_bf16):
     xg [G, B, Rp, D/G] bf16, w [G, D/G, Kp*D/G] bf16 tap-major, out / residual [B*R, D] bf16."""
-    assert xg.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and out.dtype == torch.bfloat16
     assert xg.is_contiguous() and w.is_contiguous() and out.is_contiguous() and xg.shape[0] == G and xg.shape[1] == B
-    Rp = xg.shape[2]
-    if _timer is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(lib().sc_posconv_bf16(_p(xg), _p(w), _p(bias), _p(residual), _p(out), B, R, D, G, Kp, Rp, _stream()), "sc_posconv_bf16")
-    if _timer is not None:
-        ev1.record()
-        rows = R if alg_rows is None else alg_rows
-        _timer.add("posconv", ev0, ev1, 2.0 * B * rows * D * Kp * (D // G))
+    _posconv(xg, w, bias, residual, out, None, B, R, D, G, Kp, xg.shape[2], B * (R if alg_rows is None else alg_rows))
 
 
 class LazyStates:
@@ -1275,16 +1265,13 @@ def wsum_fwd(h: torch.Tensor, w_softmax: torch.Tensor, out: torch.Tensor, B: int
     NL = h.shape[0]
     if seg is not None:
         assert lazy is None and h.shape[1] == seg.rows and B == seg.B
-        assert h.dtype == torch.bfloat16 and w_softmax.dtype == torch.float32 and out.dtype == torch.bfloat16
-        check(lib().sc_wsum_fwd_seg(_p(h), _p(w_softmax), NL, _p(out), seg.ref(), R, D, row_off, int(normalize), _stream()), "sc_wsum_fwd_seg")
-        return
     if lazy is not None:
         assert not normalize
         check(lib().sc_wsum_lazy_fwd(_p(h), _p(w_softmax), NL, _p(out), B, R, D, row_off, _p(lazy.stats), _p(lazy.gamma), _p(lazy.beta),
                                      lazy.first_lazy, lazy.ns, lazy.eps, _stream()), "sc_wsum_lazy_fwd")
         return
     assert h.dtype == torch.bfloat16 and w_softmax.dtype == torch.float32 and out.dtype == torch.bfloat16
-    check(lib().sc_wsum_fwd(_p(h), _p(w_softmax), NL, _p(out), B, R, D, row_off, int(normalize), _stream()), "sc_wsum_fwd")
+    check(lib().sc_wsum_fwd(_p(h), _p(w_softmax), NL, _p(out), _seg(seg), B, R, D, row_off, int(normalize), _stream()), "sc_wsum_fwd")
 
 
 def wsum_bwd(h: torch.Tensor, g: torch.Tensor, B: int, R: int, D: int, row_off: int, nblk: int = 1024,
@@ -1299,7 +1286,7 @@ def wsum_bwd(h: torch.Tensor, g: torch.Tensor, B: int, R: int, D: int, row_off: 
         check(lib().sc_wsum_lazy_bwd(_p(h), _p(g), NL, _p(part), nblk, B, R, D, row_off, _p(lazy.stats), _p(lazy.gamma), _p(lazy.beta),
                                      lazy.first_lazy, lazy.ns, lazy.eps, _stream()), "sc_wsum_lazy_bwd")
         return part.sum(0)
-    check(lib().sc_wsum_bwd(_p(h), _p(g), NL, _p(part), nblk, B, R, D, row_off, int(normalize), _stream()), "sc_wsum_bwd")
+    check(lib().sc_wsum_bwd(_p(h), _p(g), NL, _p(part), nblk, None, B, R, D, row_off, int(normalize), _stream()), "sc_wsum_bwd")
     return part.sum(0)
 
 
@@ -1645,15 +1632,14 @@ def wsum_bwd_logits(h: torch.Tensor, g: torch.Tensor, w_soft: torch.Tensor, B: i
     part = torch.empty(nblk, NL, device=h.device, dtype=torch.float32)
     if seg is not None:
         assert lazy is None and h.shape[1] == seg.rows and B == seg.B
-        check(lib().sc_wsum_bwd_seg(_p(h), _p(g), NL, _p(part), nblk, seg.ref(), R, D, row_off, flags, _stream()), "sc_wsum_bwd_seg")
-    elif lazy is not None:
+    if lazy is not None:
         assert not normalize
         if g.dtype != torch.float32:
             g = g.float()
         check(lib().sc_wsum_lazy_bwd(_p(h), _p(g), NL, _p(part), nblk, B, R, D, row_off, _p(lazy.stats), _p(lazy.gamma), _p(lazy.beta),
                                      lazy.first_lazy, lazy.ns, lazy.eps, _stream()), "sc_wsum_lazy_bwd")
     else:
-        check(lib().sc_wsum_bwd(_p(h), _p(g), NL, _p(part), nblk, B, R, D, row_off, flags, _stream()), "sc_wsum_bwd")
+        check(lib().sc_wsum_bwd(_p(h), _p(g), NL, _p(part), nblk, _seg(seg), B, R, D, row_off, flags, _stream()), "sc_wsum_bwd")
     out = torch.empty(NL, device=h.device, dtype=torch.float32)
     check(lib().sc_rt_softmax_bwd_reduce(_p(part), nblk, NL, _p(w_soft), _p(out), _stream()), "sc_rt_softmax_bwd_reduce")
     return out

@@ -322,7 +322,7 @@ class _Plan:
         self.halo = halo
         if seg_mode:
             self.wav_pad = z(self.spr * M + 64, dtype=torch.float32)           # ONE flat waveform, utterance b at sample 320 row0[b]
-            self.xg = z(G * (M + 2 * halo * B) * (D // G))                     # flat slab buffer (sc_posconv_prep_seg)
+            self.xg = z(G * (M + 2 * halo * B) * (D // G))                     # flat slab buffer (sc_posconv_prep with seg)
             self.vt = z(D * (M + S))
             self._seg_cache = (None, None)
         else:

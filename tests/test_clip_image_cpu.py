@@ -149,4 +149,4 @@ def test_layer_args_ffn_act_replaces_reserved():
     assert H.ffn_act.offset == H.pre_ln.offset + 4 and H.ffn_act.size == 4
     assert H.ffn_act.offset == 3 * 8 + 7 * 4 and H.qkv_w.offset == H.ffn_act.offset + 4
     assert _lib.lib().sc_sizeof(1) == ctypes.sizeof(H)
-    assert _lib.lib().sc_abi_version() == 6
+    assert _lib.lib().sc_abi_version() == 7

@@ -287,7 +287,7 @@ def test_weighted_sum_golden(dev, golden):
 
 
 def test_weighted_sum_over_segments_fixed_layer_count_kernel(dev):
-    """Round 5: sc_wsum_fwd_seg takes a one-chunk-per-thread kernel with the layer count as a compile-time constant for NL = 13 / 25 (base /
+    """Round 5: sc_wsum_fwd with seg takes a one-chunk-per-thread kernel with the layer count as a compile-time constant for NL = 13 / 25 (base /
     large).  It must compute what the generic kernel computes (sc_set_option(5, 1) selects the generic one): the same fp32 multiply-adds
     in the same order - the compiler's contraction choices may differ, so at most one bf16 ulp on a few elements per million - and both
     within half an ulp + fp32 round-off of the exact sum; every row of the uniform output written, zeros outside the utterances."""

@@ -1074,7 +1074,7 @@ def _encoder_mask_hook(seed_of, B, T, D, H, R, p=0.1, seg=False):
     """oracle ``drop`` hook that rebuilds the kernels' stateless hash masks on the host (site numbering of
     speech_encoder._encode_kernels: 0 input, 1 encoder, 3 i + 2 attention, 3 i + 3 out_proj, 3 i + 4 fc2 of layer i).
     ``seg``: the frozen encoder's segment layout with every utterance at pitch R (an un-ragged forward): the attention kernel then
-    numbers a probability ((h rows + row0[b] + q) max_pitch + k), sc_attn_fwd_seg_bf16."""
+    numbers a probability ((h rows + row0[b] + q) max_pitch + k), sc_attn_fwd_bf16 with seg."""
     from test_gpu_kernels import _keep_mask, _keep_mask8
     site_of = {"input": lambda i: 0, "encoder": lambda i: 1, "attn": lambda i: 3 * i + 2, "dropout1": lambda i: 3 * i + 3,
                "dropout3": lambda i: 3 * i + 4}

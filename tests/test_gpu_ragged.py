@@ -173,7 +173,7 @@ def test_ragged_train_step_equals_the_padded_train_step(setup):
 
 
 def test_segment_attention_and_vt_store_against_torch():
-    """sc_gemm_bf16 with a segment table (V^T per utterance [H, 64, pitch]) + sc_attn_fwd_seg_bf16, pitches 8 .. 160 (last q-blocks of
+    """sc_gemm_bf16 with a segment table (V^T per utterance [H, 64, pitch]) + sc_attn_fwd_bf16 with seg, pitches 8 .. 160 (last q-blocks of
     8 / 24 / 32 / 64 / 104 / 128 rows, a K tile that crosses into the next utterance), with and without the host's work list, against fp32 torch."""
     from speechclip_plus_amd import ops
     torch.manual_seed(0)
@@ -215,8 +215,40 @@ def test_segment_attention_and_vt_store_against_torch():
         assert rel_l2(outs[0][rows], ref) < 1.5e-2, (b, rel_l2(outs[0][rows], ref))
 
 
+@pytest.mark.parametrize("causal", [False, True])
+def test_plain_attention_is_the_same_in_both_row_layouts(causal):
+    """sc_attn_fwd_bf16 without the bias: one call with seg (with and without the host's work list) against one call per utterance with
+    seg = NULL, B = 1, R = the utterance's pitch on views of the same qk / vt buffers (an utterance's V^T at element D * row0[b]) -
+    every row of every utterance bit for bit.  The shapes of test_segment_attention_and_vt_store_against_torch: last q-blocks of 8 / 24 /
+    32 / 64 / 104 / 128 rows, a K tile that crosses into the next utterance.  drop_p = 0: the dropout element index is defined per layout."""
+    from speechclip_plus_amd import ops
+    torch.manual_seed(2)
+    H, D = 2, 128
+    pitch = [24, 160, 64, 104, 128, 8]
+    valid = [7, 150, 64, 65, 100, 8]
+    seg = ops.RowSegments(pitch, valid, "cuda")
+    M, r0 = seg.rows, seg.row0_host
+    qk = torch.randn(M + 64, 2 * D, device="cuda").to(torch.bfloat16)              # 64 rows / 64 V^T elements of slack behind the last utterance
+    vt = torch.randn(D * (M + 64), device="cuda").to(torch.bfloat16)
+    vl = torch.tensor(valid, dtype=torch.int32, device="cuda")
+    ragged = []
+    for use_work in (True, False):
+        out = torch.zeros(M + 64, D, device="cuda", dtype=torch.bfloat16)
+        ops.attn_fwd(qk, vt, vl, out, 0, 0, H, D, 0.125, causal=causal, seg=seg, use_work=use_work)
+        ragged.append(out)
+    uniform = torch.zeros(M + 64, D, device="cuda", dtype=torch.bfloat16)
+    for b, p in enumerate(pitch):
+        ops.attn_fwd(qk[r0[b]:], vt[D * r0[b]:], vl[b: b + 1], uniform[r0[b]:], 1, p, H, D, 0.125, causal=causal)
+    for b, p in enumerate(pitch):
+        rows = slice(r0[b], r0[b] + p)
+        assert float(uniform[rows].float().abs().max()) > 0.0, b
+        for out in ragged:
+            assert torch.equal(out[rows], uniform[rows]), (causal, b)
+    assert float(uniform[M:].abs().max()) == 0.0 and float(ragged[0][M:].abs().max()) == 0.0
+
+
 def test_segment_posconv_and_weighted_sum_match_the_uniform_kernels():
-    """sc_posconv_prep_seg + sc_posconv_seg_bf16 and sc_wsum_fwd_seg / sc_wsum_bwd_seg against the uniform-pitch kernels run per
+    """sc_posconv_prep + sc_posconv_bf16 and sc_wsum_fwd / sc_wsum_bwd with seg against the same entries on uniform rows, run per
     utterance on the same data: bit-identical rows; the slab halos are re-zeroed when the layout moves."""
     from speechclip_plus_amd import ops
     torch.manual_seed(1)

@@ -23,7 +23,7 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/speechclip_hip.h but not exported"
     assert set(_lib.SIGNATURES) | {"sc_last_error", "sc_hash32", "sc_infonce_workspace_floats", "sc_workspace_bytes", "sc_sizeof"} == declared
-    assert lib.sc_abi_version() == 6
+    assert lib.sc_abi_version() == 7
     # the ctypes mirrors of the argument structs have the C structs' sizes (checked again at every load: _lib.lib())
     for what, cls in enumerate((_lib.GemmArgs, _lib.HubertLayerArgs, _lib.RtGemmArgs, _lib.RtLnArgs, _lib.RtLnBwdArgs)):
         assert lib.sc_sizeof(what) == ctypes.sizeof(cls), cls.__name__
@@ -79,6 +79,80 @@ def test_frontend_refusals_are_host_side():
              ("uniform ldw_out < L", "ldw_out < L", [(wav_prep, "sc_wav_prep")], lambda: dict(ldw_out=L - 1)),
              ("C = 256, GroupNorm form", "C=256", [(gn, "sc_conv0_gn_gelu")], lambda: dict(C=256)),
              ("C = 1024, LayerNorm form", "got 1024", [(ln, "sc_conv0_ln_gelu")], lambda: dict(C=1024))]
+    for what, reason, entries, kwargs in cases:
+        for fn, name in entries:
+            rc = fn(**kwargs())
+            err = lib.sc_last_error().decode()
+            assert rc != 0 and err.startswith(name + ":") and reason in err and "launch" not in err, (what, name, rc, err)
+    assert raw.raw == b"\xa5" * 4096
+
+
+def test_encoder_refusals_are_host_side():
+    """The merged encoder entries (sc_attn_fwd_bf16, sc_posconv_bf16, sc_posconv_prep, sc_wsum_fwd, sc_wsum_bwd: row layout, work list
+    and WavLM's bias as arguments) check their arguments on the host before any launch: with host pointers and no GPU, every
+    combination the entries refuse returns non-zero with sc_last_error() naming the merged symbol and the reason, and the output
+    buffer keeps its sentinel.  (Only refused calls are made: the pointers are host memory no kernel may see.)
+    causal = 32 / 64 (segment-causal packing) belongs to the uniform layout only: the ragged call refuses it, the uniform call does NOT
+    - made here with a bad ldqk as well, it is refused for the leading dimension, the check behind the causal one."""
+    from speechclip_plus_amd import _lib
+    lib = _lib.lib()
+    raw = ctypes.create_string_buffer(b"\xa5" * 4096, 4096)
+    p = (ctypes.addressof(raw) + 15) // 16 * 16              # a 16-byte aligned, non-null host address
+
+    def seg(B=2, row0=p, chunk=p, max_pitch=8):
+        s = _lib.Segments()
+        s.row0, s.chunk, s.B, s.rows, s.max_pitch = row0, chunk, B, 16, max_pitch
+        return ctypes.byref(s)
+
+    B, R, H, D = 2, 128, 2, 128
+
+    def attn(sg=None, work=None, nwork=0, ldqk=2 * D, H=H, gate=None, table=None, tmax=0, causal=0):
+        return lib.sc_attn_fwd_bf16(p, ldqk, p, p, p, D, sg, work, nwork, B, R, H, D, 0.125, gate, table, tmax, None, causal, 0.0, 0, None)
+
+    def posconv(sg=None, D=768, G=16, Kp=128, Rp=R + 128):
+        return lib.sc_posconv_bf16(p, p, p, p, p, sg, B, R, D, G, Kp, Rp, None)
+
+    def prep(sg=None):
+        return lib.sc_posconv_prep(p, p, p, p, sg, B, R, 768, 16, 64, None)
+
+    def wsum_fwd(sg=None, D=D, row_off=1, normalize=0):
+        return lib.sc_wsum_fwd(p, p, 13, p, sg, B, R, D, row_off, normalize, None)
+
+    def wsum_bwd(sg=None, D=D, row_off=1, normalize=0, g=p):
+        return lib.sc_wsum_bwd(p, g, 13, p, 4, sg, B, R, D, row_off, normalize, None)
+
+    A, PC, PP, WF, WB = (attn, "sc_attn_fwd_bf16"), (posconv, "sc_posconv_bf16"), (prep, "sc_posconv_prep"), (wsum_fwd, "sc_wsum_fwd"), (wsum_bwd, "sc_wsum_bwd")
+    cases = [("seg with row0 == NULL", "null pointer", [A, PC, WF, WB], lambda: dict(sg=seg(row0=None))),
+             ("seg with chunk == NULL", "null pointer", [PP], lambda: dict(sg=seg(chunk=None))),
+             ("work without seg", "a work list needs the segment layout", [A], lambda: dict(work=p, nwork=1)),
+             ("nwork without seg", "a work list needs the segment layout", [A], lambda: dict(nwork=1)),
+             ("gate without table", "null gate / table", [A], lambda: dict(gate=p, tmax=R)),
+             ("table without gate", "null gate / table", [A], lambda: dict(table=p, tmax=R)),
+             ("tmax < pitch, uniform", "the row pitch is 128", [A], lambda: dict(gate=p, table=p, tmax=R - 8)),
+             ("tmax < pitch, ragged", "the row pitch is 160", [A], lambda: dict(sg=seg(max_pitch=160), gate=p, table=p, tmax=152)),
+             ("biased with causal = 1", "built without a causal mask", [A], lambda: dict(gate=p, table=p, tmax=R, causal=1)),
+             ("ragged with causal = 32", "causal=32", [A], lambda: dict(sg=seg(), causal=32)),
+             ("uniform with causal = 32 passes the causal check", "bad leading dims", [A], lambda: dict(causal=32, ldqk=2 * D + 4)),
+             ("uniform with causal = 16", "causal=16 (0, 1, or a segment of 32 / 64 rows)", [A], lambda: dict(causal=16)),
+             ("D != 64 H", "head_dim must be 64", [A], lambda: dict(H=3)),
+             ("ldqk % 8 != 0", "bad leading dims", [A], lambda: dict(ldqk=2 * D + 4)),
+             ("ldqk % 8 != 0, ragged", "bad leading dims", [A], lambda: dict(sg=seg(), ldqk=2 * D + 4)),
+             ("misaligned work", "the work list must be 16-byte aligned", [A], lambda: dict(sg=seg(), work=p + 4, nwork=1)),
+             ("ragged B = 65536", "B=65536", [A], lambda: dict(sg=seg(B=65536))),
+             ("D / G = 32", "channels per group must be 48 or 64", [PC], lambda: dict(D=512)),
+             ("D / G = 32, ragged", "channels per group must be 48 or 64", [PC], lambda: dict(sg=seg(), D=512)),
+             ("Kp = 64", "kernel must be 128 taps", [PC], lambda: dict(Kp=64, Rp=R + 64)),
+             ("Kp = 64, ragged", "kernel must be 128 taps", [PC], lambda: dict(sg=seg(), Kp=64)),
+             ("uniform Rp < R + 127", "Rp >= R + 127", [PC], lambda: dict(Rp=R + 126)),
+             ("seg with a misaligned chunk", "chunk table must be 16-byte aligned", [PP], lambda: dict(sg=seg(chunk=p + 4))),
+             ("row_off >= R", "bad NL/D/row_off", [WF], lambda: dict(row_off=R)),
+             ("row_off >= R, ragged", "bad NL/D/row_off", [WF], lambda: dict(sg=seg(), row_off=R)),
+             ("row_off >= R", "bad args", [WB], lambda: dict(row_off=R)),
+             ("row_off >= R, ragged", "bad args", [WB], lambda: dict(sg=seg(), row_off=R)),
+             ("normalize with D = 2048", "needs D <= 1024 (got 2048)", [WF, WB], lambda: dict(D=2048, normalize=1)),
+             ("normalize with D = 2048, ragged", "needs D <= 1024 (got 2048)", [WF, WB], lambda: dict(sg=seg(), D=2048, normalize=1)),
+             ("misaligned g", "g must be 16-byte aligned", [WB], lambda: dict(g=p + 4)),
+             ("B != seg->B", "B=2 against seg->B=3", [WF, WB], lambda: dict(sg=seg(B=3)))]
     for what, reason, entries, kwargs in cases:
         for fn, name in entries:
             rc = fn(**kwargs())

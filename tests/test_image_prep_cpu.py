@@ -109,7 +109,7 @@ def test_new_symbols_declared_bound_and_exported():
         assert len(_lib.SIGNATURES[name]) == nargs and getattr(lib, name) is not None
     assert "clip_official.py:153-166" in header and "base_dataset.py:93-106" in header
     assert "image_prep.hip" in build.SOURCES
-    assert lib.sc_abi_version() == 6
+    assert lib.sc_abi_version() == 7
     # host-side refusals, no launch: null pointers, neither output, odd P
     assert lib.sc_image_resample_h_u8(None, 1, None, None, None, 1, 1, 1, 224, None) != 0
     assert b"null pointer" in lib.sc_last_error()

@@ -19,7 +19,7 @@ def test_symbols_declared_bound_and_exported():
     lib = _lib.lib()
     for name in ("sc_search_slabs", "sc_search_topk_bf16"):
         assert name in declared and name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.sc_abi_version() == 6
+    assert lib.sc_abi_version() == 7
     assert "retrieval.py:45-46" in header and "kwClip.py:447-482" in header
     assert sc.search is retrieval.search and sc.GalleryIndex is retrieval.GalleryIndex
     assert {"search", "GalleryIndex"} <= set(sc.__all__)

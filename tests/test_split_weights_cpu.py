@@ -110,7 +110,7 @@ def test_layer_driver_rejects_w_split_with_fused_ln():
 
 def test_struct_sizes_and_field_slots_unchanged():
     L = _lib.lib()
-    assert L.sc_abi_version() == 6
+    assert L.sc_abi_version() == 7
     assert ctypes.sizeof(_lib.GemmArgs) == 312 and L.sc_sizeof(0) == 312      # the parent's sizes
     assert ctypes.sizeof(_lib.HubertLayerArgs) == L.sc_sizeof(1)
     g = [n for n, _ in _lib.GemmArgs._fields_]

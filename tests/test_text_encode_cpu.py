@@ -39,7 +39,7 @@ def test_sc_text_assemble_is_exported_declared_and_bound():
     decl = re.search(r"int sc_text_assemble\(([^;]*)\);", header)
     assert decl is not None and len(decl.group(1).split(",")) == 16          # as many parameters as the ctypes signature
     assert "clip_official.py:213-220" in header
-    assert _lib.lib().sc_abi_version() == 6                                  # 6 since the front-end entry points merged; this entry was additive
+    assert _lib.lib().sc_abi_version() == 7                                  # 7 since the encoder entry points merged; this entry was additive
 
 
 def test_no_cpu_path():

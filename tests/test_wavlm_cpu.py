@@ -63,13 +63,17 @@ def test_both_key_maps_load_the_same_weights():
 
 def test_abi_additions():
     lib = _lib.lib()
-    assert lib.sc_abi_version() == 6
-    for name in ("sc_attn_fwd_relbias_bf16", "sc_attn_fwd_seg_relbias_bf16", "sc_wavlm_gate_bf16"):
-        assert name in _lib.SIGNATURES and getattr(lib, name) is not None
-    import os
+    assert lib.sc_abi_version() == 7
+    # the library can run biased attention: the gate kernel, and the one attention entry takes the bias as arguments
+    assert "sc_wavlm_gate_bf16" in _lib.SIGNATURES and lib.sc_wavlm_gate_bf16 is not None
+    import os, re
     header = open(os.path.join(os.path.dirname(_lib.__file__), "..", "include", "speechclip_hip.h")).read()
-    for name in ("sc_attn_fwd_relbias_bf16", "sc_attn_fwd_seg_relbias_bf16", "sc_wavlm_gate_bf16"):
-        assert f"int {name}(" in header
+    assert "int sc_wavlm_gate_bf16(" in header
+    decl = re.search(r"int sc_attn_fwd_bf16\(([^;]*)\);", header)
+    assert decl is not None
+    for arg in ("const float* gate", "const float* table", "int32_t tmax"):
+        assert arg in decl.group(1), arg
+    assert len(decl.group(1).split(",")) == len(_lib.SIGNATURES["sc_attn_fwd_bf16"])
 
 
 def test_archs():

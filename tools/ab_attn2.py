@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """same-process A/B of sc_attn_fwd_bf16 builds: argv[1:] = libraries (default: tools/_ab/lib_base.so vs the tree's), each timed with
-scale 0.125 and - where the build knows the pre-scaled form - scale 0 (timing only there: the random Q is not pre-scaled)."""
+scale 0.125 and - where the build knows the pre-scaled form - scale 0 (timing only there: the random Q is not pre-scaled).  Every library must be
+a build of ABI version 7 (sc_attn_fwd_bf16 takes seg / work / nwork and gate / table / tmax)."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -24,7 +25,7 @@ for p in (0.0, 0.1):
                 if scale == 0.0 and i == 0:
                     continue
                 o = outs.setdefault((n, p, scale), torch.zeros(B * R + 64, D, device=dev, dtype=torch.bfloat16))
-                call = lambda: L.sc_attn_fwd_bf16(qk.data_ptr(), 2 * D, vt.data_ptr(), valid.data_ptr(), o.data_ptr(), D, B, R, H, D, ctypes.c_float(scale), None, 0, ctypes.c_float(p), 99, st)
+                call = lambda: L.sc_attn_fwd_bf16(qk.data_ptr(), 2 * D, vt.data_ptr(), valid.data_ptr(), o.data_ptr(), D, None, None, 0, B, R, H, D, ctypes.c_float(scale), None, None, 0, None, 0, ctypes.c_float(p), 99, st)
                 rc = call()
                 assert rc == 0, rc
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""same-process A/B of two builds of sc_attn_fwd_bf16: the product library vs the library given as argv[1] (alternating rounds)"""
+"""same-process A/B of two builds of sc_attn_fwd_bf16: the product library vs the library given as argv[1] (alternating rounds; both of ABI version 7:
+seg / work / nwork and gate / table / tmax in the argument list)"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -17,7 +18,7 @@ for p in (0.0, 0.1):
     res = {n: [] for n, _ in libs}
     for rnd in range(6):
         for i, (n, L) in enumerate(libs):
-            call = lambda: L.sc_attn_fwd_bf16(qk.data_ptr(), 2 * D, vt.data_ptr(), valid.data_ptr(), outs[i].data_ptr(), D, B, R, H, D, 0.125, None, 0, p, 99, st)
+            call = lambda: L.sc_attn_fwd_bf16(qk.data_ptr(), 2 * D, vt.data_ptr(), valid.data_ptr(), outs[i].data_ptr(), D, None, None, 0, B, R, H, D, 0.125, None, None, 0, None, 0, p, 99, st)
             call()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()

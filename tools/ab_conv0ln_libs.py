@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """same-process A/B of library builds on the layer_norm-mode conv layer 0 (HuBERT-large): B = 64 x 10 s, bitwise comparison + time.
-Every library is called through this tree's ops / _lib.SIGNATURES, so all of them must be builds of one ABI version (sc_abi_version() == 6:
-the front-end entry points take seg / wav_off / out_f32); a library from before that change cannot be loaded here."""
+Every library is called through this tree's ops / _lib.SIGNATURES, so all of them must be builds of one ABI version (sc_abi_version() == 7:
+the front-end and the encoder entry points take seg / wav_off / out_f32 and seg / gate / table); a library from before those changes cannot
+be loaded here."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
