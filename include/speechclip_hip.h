@@ -581,6 +581,26 @@ int sc_search_slabs(int32_t nQ, int32_t N, int32_t k);
 int sc_search_topk_bf16(const sc_bf16* q_split, const sc_bf16* g_split, int32_t nQ, int32_t N, int32_t K6, int32_t k, int32_t S,
                         float* part_vals, int32_t* part_idx, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Retrieval ranks: per query the number of candidates ahead of its best correct candidate, in both directions, computed in the
+ * epilogue of the score GEMM (csrc/rank.hip).  Additive in round 14; sc_abi_version() stays 7.
+ *   replaces: the sort and rank look-up of avssl/module/retrieval.py:45-121 on the scores of avssl/model/kwClip.py:447-482 - here the
+ *             [nA, nB] score matrix is never written and recall at every k, median and mean rank come from two integer vectors.
+ *   sc_rank_counts_bf16  a_split [roundup(nA, 128), K6] / b_split [roundup(nB, 128), K6]: sc_search_topk_bf16's operands (side 0 / side 1
+ *                        of sc_split3_bf16, K6 = 6 Ep, Ep % 64 == 0, padding rows zero) and its scores, to the bit.  a_ids [nA] /
+ *                        b_ids [nB] int64: the pair (i, j) is correct iff a_ids[i] == b_ids[j].  Two launches of one kernel on
+ *                        ``stream``: (1) best_a[i] = the largest key over the correct, non-NaN scores of row i, best_b[j] the same of
+ *                        column j (atomicMax; key = sc_topk_rows_f32's order as a uint32: float order, -0 == +0; 0 = no such
+ *                        candidate); (2) ahead_a[i] = #{j : s_ij > best_i} + #{j not correct : s_ij == best_i or s_ij is NaN} and
+ *                        ahead_b[j] its mirror image over rows (int32 atomicAdd).  Rows >= nA / columns >= nB never enter.  All four
+ *                        outputs are the caller's and must be ZERO on entry; nothing is allocated.  Integer atomics only: the
+ *                        result is bitwise reproducible and does not depend on S.  S: slabs of the nB axis (sc_search_slabs(nA, nB, 1)
+ *                        is a good value), S >= 1 (slabs of ceil(tiles / S) column tiles; one past the last tile is empty and adds
+ *                        nothing); K6 % 384 == 0; nA == 0 or nB == 0: no-op, returns 0.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_rank_counts_bf16(const sc_bf16* a_split, const sc_bf16* b_split, const int64_t* a_ids, const int64_t* b_ids, int32_t nA, int32_t nB,
+                        int32_t K6, int32_t S, uint32_t* best_a, uint32_t* best_b, int32_t* ahead_a, int32_t* ahead_b, void* stream);
+
 /* Keyword BatchNorm: nn.BatchNorm1d over the keyword positions (avssl/module/speechclip_c_modules/kw_bn.py:167-228).
  *   x [N, E] fp32 (N = batch x keyword slots), per-channel statistics.  training: batch statistics (biased variance for the
  *   normalisation, unbiased for the running estimate; run_mean / run_var updated in place with `momentum`), save_mean / save_rstd

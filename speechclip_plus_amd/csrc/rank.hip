@@ -1,0 +1,317 @@
+// Retrieval ranks (gfx950): for every row of A and every row of B, how many candidates of the other side rank ahead of its best
+// correct candidate - the one integer per query that recall@k, median rank and mean rank are made of - produced in the epilogue of the
+// split-bf16 score GEMM.  The [nA, nB] score matrix never exists in memory.
+//   replaces: the sort-and-look-up of avssl/module/retrieval.py:45-121 (and the half dozen [nA, nB] temporaries a masked-maximum form
+//             of it needs per direction) on the scores of avssl/model/kwClip.py:447-482.
+//
+// Scores: csrc/search.hip's, to the bit.  A is the side-0 three-way split sc_split3_bf16 writes, B the side-1 split, rows padded to 128,
+// K6 = 6 Ep columns; a score is the fp32 sum of the six K-blocks on v_mfma_f32_16x16x32_bf16, K-tiles in increasing order.  The K loop is
+// search.hip's (gemm_bf16.hip's 128 x 128 tile) written again: 256 threads = 2 x 2 waves, LDS-DMA staging into two buffers, 16-byte chunk
+// index XOR ((row >> 1) & 7) applied on the global source address, one barrier per K-tile.
+//
+// The pair (i, j) is CORRECT iff a_ids[i] == b_ids[j].  One 128 x 128 score tile serves both directions: its rows for A -> B, its columns
+// for B -> A.  Two launches of one kernel body (template parameter PHASE), both over the same K loop, so the score compared in the second
+// is bit for bit the score that produced ``best`` in the first:
+//   PHASE 0, best:   per row the largest key (tk_key of csrc/topk.hip: float order, -0 == +0, every NaN on top) over correct, non-NaN
+//                    columns; per column the same over correct, non-NaN rows.  Combined across tiles with atomicMax on a uint32 key
+//                    per row / per column; key 0 = no correct non-NaN candidate.  A tile whose 128 + 128 ids hold no matching pair
+//                    (every thread compares its column's id with half of the rows' ids in LDS, one workgroup-wide OR) contributes
+//                    nothing and is skipped BEFORE its K loop: with few captions per image nearly all tiles are, and this launch
+//                    takes 0.18 ms next to the second's 1.81 ms at 25 000 x 5 000 x 768 (docs/rounds/r14_ranks.md).
+//   PHASE 1, count:  ahead_a[i] = #{j : s_ij > best_i} + #{j not correct : s_ij == best_i or s_ij is NaN}, and the mirror image per
+//                    column, compared on keys.  On keys that is: a correct candidate counts iff best < key < NaN, a wrong one iff
+//                    key >= best.
+//
+// Epilogue: the accumulators go to the LDS tile (over the staging ring) as KEYS.  Row direction: a wave owns 32 rows, a lane reads
+// columns lane and lane + 64 of a row (conflict free); a row's count is two ballots and two scalar pop-counts, kept by lane (row & 31)
+// in a register across the column tiles of the slab and added to ahead_a once, after the last tile.  Column direction: thread = column
+// tid & 127 over rows 64 (tid >> 7) .. + 63 (consecutive lanes on consecutive banks; the rows' ids and best keys are LDS broadcasts);
+// the two halves meet in LDS and threads 0 .. 127 issue one int32 atomic per column per tile - one lane per consecutive column, 256
+// contiguous bytes per wave instruction.  Rows >= nA and columns >= nB are excluded by their index.
+//
+// Only integer atomicMax / atomicAdd from vector lanes: the result is bitwise reproducible and independent of S.  Every buffer is the
+// caller's, the four outputs zeroed by the caller; nothing is allocated here.
+#include "sc_common.h"
+
+#include <algorithm>
+
+namespace {
+
+constexpr int BM = 128, BN = 128, BK = 64;
+constexpr int ROWB = BK * 2;                        // bytes per LDS tile row
+constexpr int A_BYTES = BM * ROWB, B_BYTES = BN * ROWB;
+constexpr int RING_BYTES = 2 * (A_BYTES + B_BYTES);
+static_assert(RING_BYTES == BM * BN * 4, "the 32-bit key tile lies exactly over the two-stage ring");
+constexpr int TM = 64, TN = 64, FM = 4, FN = 4;     // per-wave tile, 16 x 16 fragments
+constexpr int SIDE_BYTES = BM * 8 + BM * 4 + 2 * BN * 4;   // ids and best keys of the 128 rows, the two halves' column partials
+constexpr int LDS_BYTES = RING_BYTES + SIDE_BYTES;
+
+constexpr uint32_t TK_NAN = 0xffffffffu;     // above +inf (0xff800000); 0 is below every real key (-inf maps to 0x007fffff)
+
+// fp32 -> uint32 with the order of csrc/topk.hip's contract: a < b as floats <=> key(a) < key(b); -0 and +0 share a key; every NaN is
+// TK_NAN
+__device__ __forceinline__ uint32_t tk_key(float v) {
+    const uint32_t u = __float_as_uint(v);
+    uint32_t k = u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
+    if ((u & 0x7fffffffu) > 0x7f800000u) k = TK_NAN;
+    if (k == 0x7fffffffu) k = 0x80000000u;
+    return k;
+}
+
+__device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
+
+// does a candidate with key ``key`` rank ahead of a best correct candidate with key ``best``?
+__device__ __forceinline__ bool ahead_of(uint32_t key, uint32_t best, bool correct) {
+    return correct ? (key > best && key != TK_NAN) : key >= best;
+}
+
+struct RankArgs {
+    const uint16_t* a;       // [roundup(nA, 128), K6] side-0 split
+    const uint16_t* b;       // [roundup(nB, 128), K6] side-1 split
+    const int64_t* a_ids;    // [nA]
+    const int64_t* b_ids;    // [nB]
+    int nA, nB, K6, S, tiles;
+    uint32_t* best_a;        // [nA] keys
+    uint32_t* best_b;        // [nB]
+    int32_t* ahead_a;        // [nA]
+    int32_t* ahead_b;        // [nB]
+};
+
+template <int PHASE>
+__global__ __launch_bounds__(256) void rank_kernel(const RankArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+
+    // ---- block -> (row tile, slab): search.hip's XCD remap (bijective; blocks b, b + 8, ... share an L2), then row tiles fastest
+    const int nM = (p.nA + BM - 1) / BM;
+    const int nT = (p.nB + BN - 1) / BN;
+    int L;
+    {
+        const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
+        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    }
+    const int slab = L / nM, m_tile = L - slab * nM;
+    const int m0 = m_tile * BM;
+    const int t_begin = slab * p.tiles, t_end = min(nT, t_begin + p.tiles);
+
+    char* const As = smem;
+    char* const Bs = smem + 2 * A_BYTES;
+    uint32_t* const Ks = (uint32_t*)smem;                               // [BM][BN] keys of the tile's scores
+    int64_t* const aid_s = (int64_t*)(smem + RING_BYTES);               // [BM] ids of the tile's rows
+    uint32_t* const abest_s = (uint32_t*)(smem + RING_BYTES + BM * 8);  // [BM] their best keys (PHASE 1)
+    uint32_t* const colpart = abest_s + BM;                             // [2][BN] the two row halves' column results
+
+    const int rows_valid = min(BM, p.nA - m0);                         // >= 1: rows of this tile that exist
+    if (tid < BM) {
+        const bool v = tid < rows_valid;
+        aid_s[tid] = v ? p.a_ids[m0 + tid] : 0;
+        if (PHASE == 1) abest_s[tid] = v ? p.best_a[m0 + tid] : 0u;
+    }
+    __syncthreads();
+
+    // column direction: this thread's column of the tile and its half of the rows
+    const int c = tid & (BN - 1);
+    const int cr0 = (tid >> 7) * 64, cr1 = min(cr0 + 64, rows_valid);
+    // row direction: this wave's rows; lane rr keeps the result of row wave * 32 + rr across the tiles of the slab
+    const int rows_here = min(32, p.nA - m0 - wave * 32);              // wave-uniform; <= 0: nothing to scan
+    uint32_t row_acc = 0;
+
+    // ---- DMA source pointers of the row tile (per lane; the swizzle lives in the source address) ------------------------
+    constexpr int A_INST = BM / 32, B_INST = BN / 32;
+    const uint16_t* a_src[A_INST];
+#pragma unroll
+    for (int i = 0; i < A_INST; ++i) {
+        const int row = (i * 4 + wave) * 8 + (lane >> 3);
+        const int ch = (lane & 7) ^ ((row >> 1) & 7);
+        a_src[i] = p.a + (int64_t)(m0 + row) * p.K6 + ch * 8;         // rows are padded to 128: in bounds
+    }
+    int a_off[FM][2], b_off[FN][2];
+#pragma unroll
+    for (int mi = 0; mi < FM; ++mi) {
+        const int row = wm * TM + mi * 16 + (lane & 15);
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) a_off[mi][kk] = row * ROWB + (((kk * 4 + (lane >> 4)) ^ ((row >> 1) & 7)) << 4);
+    }
+#pragma unroll
+    for (int ni = 0; ni < FN; ++ni) {
+        const int row = wn * TN + ni * 16 + (lane & 15);
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) b_off[ni][kk] = row * ROWB + (((kk * 4 + (lane >> 4)) ^ ((row >> 1) & 7)) << 4);
+    }
+    const int nk = p.K6 / BK;
+
+    for (int t = t_begin; t < t_end; ++t) {
+        const int n0 = t * BN;
+        // ids (and best keys) of this thread's columns: straight from global memory, in flight under the K loop
+        const bool okc = n0 + c < p.nB;
+        const bool ok0 = n0 + lane < p.nB, ok1 = n0 + 64 + lane < p.nB;
+        const int64_t bid_c = okc ? p.b_ids[n0 + c] : 0;
+        const int64_t bid0 = ok0 ? p.b_ids[n0 + lane] : 0, bid1 = ok1 ? p.b_ids[n0 + 64 + lane] : 0;
+        uint32_t bestc = 0;
+        if (PHASE == 1 && okc) bestc = p.best_b[n0 + c];
+        if (PHASE == 0) {
+            // no matching pair of ids in the tile: nothing to take a maximum over
+            int hit = 0;
+            if (okc)
+                for (int r = cr0; r < cr1; ++r) hit |= (int)(aid_s[r] == bid_c);
+            if (!__syncthreads_or(hit)) continue;
+        }
+
+        const uint16_t* b_src[B_INST];
+#pragma unroll
+        for (int i = 0; i < B_INST; ++i) {
+            const int row = (i * 4 + wave) * 8 + (lane >> 3);
+            const int ch = (lane & 7) ^ ((row >> 1) & 7);
+            b_src[i] = p.b + (int64_t)(n0 + row) * p.K6 + ch * 8;     // rows are padded to 128: in bounds
+        }
+        auto stage = [&](int buf, int kt) {
+#pragma unroll
+            for (int i = 0; i < A_INST; ++i) glds16(a_src[i] + kt * BK, As + buf * A_BYTES + (i * 4 + wave) * 1024);
+#pragma unroll
+            for (int i = 0; i < B_INST; ++i) glds16(b_src[i] + kt * BK, Bs + buf * B_BYTES + (i * 4 + wave) * 1024);
+        };
+        f32x4 acc[FM][FN];
+#pragma unroll
+        for (int mi = 0; mi < FM; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < FN; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+        stage(0, 0);
+        __syncthreads();   // hipcc drains the DMA (vmcnt(0)) in front of the barrier
+        for (int kt = 0; kt < nk; ++kt) {
+            const int buf = kt & 1;
+            if (kt + 1 < nk) stage(buf ^ 1, kt + 1);
+            const char* as = As + buf * A_BYTES;
+            const char* bs = Bs + buf * B_BYTES;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                bf16x8 af[FM], bfr[FN];
+#pragma unroll
+                for (int mi = 0; mi < FM; ++mi) af[mi] = *(const bf16x8*)(as + a_off[mi][kk]);
+#pragma unroll
+                for (int ni = 0; ni < FN; ++ni) bfr[ni] = *(const bf16x8*)(bs + b_off[ni][kk]);
+#pragma unroll
+                for (int mi = 0; mi < FM; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < FN; ++ni)
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mi], bfr[ni], acc[mi][ni], 0, 0, 0);
+            }
+            __syncthreads();
+        }
+
+        // ---- keys of the scores -> LDS tile (every wave is past the ring: the K loop ends in a barrier) -------------------
+#pragma unroll
+        for (int ni = 0; ni < FN; ++ni) {
+            const int nl = wn * TN + ni * 16 + (lane & 15);
+#pragma unroll
+            for (int mi = 0; mi < FM; ++mi) {
+                const int ml = wm * TM + mi * 16 + 4 * (lane >> 4);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Ks[(ml + r) * BN + nl] = tk_key(acc[mi][ni][r]);
+            }
+        }
+        __syncthreads();
+
+        // ---- row direction: wave w scans rows 32 w .. 32 w + 31, a lane the columns lane and lane + 64 ---------------------
+        for (int rr = 0; rr < rows_here; ++rr) {
+            const int r = wave * 32 + rr;
+            const uint32_t key0 = Ks[r * BN + lane], key1 = Ks[r * BN + 64 + lane];
+            const int64_t aid = aid_s[r];
+            const bool c0 = ok0 && aid == bid0, c1 = ok1 && aid == bid1;
+            if (PHASE == 0) {
+                const uint32_t m = wave_max_u32(max(c0 && key0 != TK_NAN ? key0 : 0u, c1 && key1 != TK_NAN ? key1 : 0u));
+                if (lane == rr) row_acc = max(row_acc, m);
+            } else {
+                const uint32_t best = abest_s[r];
+                const uint64_t m0b = __ballot(ok0 && ahead_of(key0, best, c0)), m1b = __ballot(ok1 && ahead_of(key1, best, c1));
+                const uint32_t n = (uint32_t)(__popcll(m0b) + __popcll(m1b));
+                if (lane == rr) row_acc += n;
+            }
+        }
+        // ---- column direction: thread = column c over its half of the rows that exist -------------------------------------------
+        {
+            uint32_t v = 0;
+            for (int r = cr0; r < cr1; ++r) {
+                const uint32_t key = Ks[r * BN + c];
+                const bool cor = aid_s[r] == bid_c;
+                if (PHASE == 0) v = max(v, cor && key != TK_NAN ? key : 0u);
+                else v += ahead_of(key, bestc, cor) ? 1u : 0u;
+            }
+            colpart[(tid >> 7) * BN + c] = v;
+        }
+        __syncthreads();   // the halves meet; and every read of the key tile is done: the next tile's DMA may overwrite it
+        if (tid < BN && okc) {
+            const uint32_t v0 = colpart[c], v1 = colpart[BN + c];
+            if (PHASE == 0) {
+                const uint32_t m = max(v0, v1);
+                if (m) atomicMax(p.best_b + n0 + c, m);
+            } else {
+                atomicAdd(p.ahead_b + n0 + c, (int32_t)(v0 + v1));
+            }
+        }
+        // colpart is written again only behind the next tile's K-loop barriers
+    }
+
+    // ---- this slab's share of every row, once -----------------------------------------------------------------------------------
+    if (lane < rows_here && row_acc) {
+        const int row = m0 + wave * 32 + lane;
+        if (PHASE == 0) atomicMax(p.best_a + row, row_acc);
+        else atomicAdd(p.ahead_a + row, (int32_t)row_acc);
+    }
+}
+
+template <int PHASE>
+int launch(const RankArgs& a, int64_t nwg, hipStream_t stream) {
+    static sc_lds_attr_once attr;
+    if (hipError_t e = sc_set_max_lds_once(attr, rank_kernel<PHASE>, LDS_BYTES); e != hipSuccess) {
+        sc_set_error("hipFuncSetAttribute(rank): %s", hipGetErrorString(e));
+        return -3;
+    }
+    hipLaunchKernelGGL(rank_kernel<PHASE>, dim3((unsigned)nwg), dim3(256), LDS_BYTES, stream, a);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int sc_rank_counts_bf16(const sc_bf16* a_split, const sc_bf16* b_split, const int64_t* a_ids, const int64_t* b_ids, int32_t nA,
+                                   int32_t nB, int32_t K6, int32_t S, uint32_t* best_a, uint32_t* best_b, int32_t* ahead_a, int32_t* ahead_b,
+                                   void* stream) {
+    SC_CHECK(nA >= 0 && nB >= 0, "sc_rank_counts_bf16: nA >= 0, nB >= 0 (nA %d, nB %d)", nA, nB);
+    SC_CHECK(K6 > 0 && K6 % 384 == 0, "sc_rank_counts_bf16: K6=%d must be 6 Ep with Ep a multiple of 64", K6);
+    SC_CHECK(S >= 1, "sc_rank_counts_bf16: S >= 1 (S %d)", S);
+    if (nA == 0 || nB == 0) return 0;                                 // no pair: the zeroed outputs are the result
+    const int64_t nM = ((int64_t)nA + BM - 1) / BM, nT = ((int64_t)nB + BN - 1) / BN;
+    const int64_t tiles = (nT + S - 1) / S;                           // a slab past the last tile is empty: its workgroups add nothing
+    SC_CHECK(a_split, "sc_rank_counts_bf16: null a_split");
+    SC_CHECK(b_split, "sc_rank_counts_bf16: null b_split");
+    SC_CHECK(a_ids, "sc_rank_counts_bf16: null a_ids");
+    SC_CHECK(b_ids, "sc_rank_counts_bf16: null b_ids");
+    SC_CHECK(best_a, "sc_rank_counts_bf16: null best_a");
+    SC_CHECK(best_b, "sc_rank_counts_bf16: null best_b");
+    SC_CHECK(ahead_a, "sc_rank_counts_bf16: null ahead_a");
+    SC_CHECK(ahead_b, "sc_rank_counts_bf16: null ahead_b");
+    SC_CHECK(((uintptr_t)a_split % 16) == 0 && ((uintptr_t)b_split % 16) == 0, "sc_rank_counts_bf16: operands must be 16-byte aligned");
+    SC_CHECK(((uintptr_t)a_ids % 8) == 0 && ((uintptr_t)b_ids % 8) == 0, "sc_rank_counts_bf16: ids must be 8-byte aligned");
+    SC_CHECK(nM * S < ((int64_t)1 << 31), "sc_rank_counts_bf16: %lld workgroups", (long long)(nM * S));
+    RankArgs a;
+    a.a = (const uint16_t*)a_split;
+    a.b = (const uint16_t*)b_split;
+    a.a_ids = a_ids; a.b_ids = b_ids;
+    a.nA = nA; a.nB = nB; a.K6 = K6; a.S = S; a.tiles = (int)tiles;
+    a.best_a = best_a; a.best_b = best_b; a.ahead_a = ahead_a; a.ahead_b = ahead_b;
+    if (int rc = launch<0>(a, nM * S, (hipStream_t)stream); rc != 0) return rc;
+    return launch<1>(a, nM * S, (hipStream_t)stream);
+}

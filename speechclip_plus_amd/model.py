@@ -546,9 +546,14 @@ class KWClip_GeneralTransformer(nn.Module):
         first = torch.full((uniq.shape[0],), n, dtype=torch.long, device=ids.device).scatter_reduce(0, inv, pos, "amin", include_self=False)
         order = torch.argsort(first)
         img_ids, img_feats = uniq[order], imgs[last[order]]
-        score_per_audio = audio @ img_feats.t()
-        result = mutualRetrieval(score_per_A=score_per_audio, score_per_B=score_per_audio.t(), AB_answers=ids, BA_answers=img_ids,
-                                 recall_at=self.recall_at)
+        if self.config.retrieval.get("fused_ranks", False):
+            # opt-in: both directions' ranks out of the score GEMM's epilogue (csrc/rank.hip), no [nA, nB] matrix
+            from .retrieval import mutual_recall
+            result = mutual_recall(audio, img_feats, ids, img_ids, self.recall_at)
+        else:
+            score_per_audio = audio @ img_feats.t()
+            result = mutualRetrieval(score_per_A=score_per_audio, score_per_B=score_per_audio.t(), AB_answers=ids, BA_answers=img_ids,
+                                     recall_at=self.recall_at)
         if self._detokenize_enabled() and outputs and outputs[0].get("keywords", None) is not None:
             every = int(self.config.log_setting.get("log_detokenize_results_every_n_epoch", 1) or 1)
             if int(getattr(self, "current_epoch", 0)) % every == 0:

@@ -926,6 +926,41 @@ def search_topk(q_split: torch.Tensor, g_split: torch.Tensor, nQ: int, N: int, k
     return vals, idx
 
 
+def _rank_key_value(key: torch.Tensor) -> torch.Tensor:
+    """the uint32 keys of csrc/rank.hip (held as int32 bits) -> the fp32 values they stand for; key 0 (no candidate) -> -inf"""
+    bits = torch.where(key < 0, key & 0x7fffffff, ~key)                # key >= 2^31: a value >= 0 with its sign bit set; below: the complement
+    return torch.where(key == 0, torch.full_like(bits, -8388608), bits).view(torch.float32)   # 0xff800000 = -inf
+
+
+def rank_counts(a_split: torch.Tensor, b_split: torch.Tensor, a_ids: torch.Tensor, b_ids: torch.Tensor, nA: int, nB: int,
+                slabs: Optional[int] = None):
+    """For the nA rows of A against the nB rows of B, candidate j being correct for query i iff a_ids[i] == b_ids[j]
+    (sc_rank_counts_bf16, csrc/rank.hip): -> (best_a [nA] fp32, ahead_a [nA] int32, best_b [nB] fp32, ahead_b [nB] int32).  ``best`` is
+    the largest score over a query's correct, non-NaN candidates (-inf: none) and ``ahead`` counts the candidates scoring above it
+    plus the wrong ones that tie with it or are NaN - A's rows as queries over B's rows in ``_a``, the other way round in ``_b``.
+    ``a_split`` = split3_bf16(A, 0) [>= roundup(nA, 128), 6 Ep], ``b_split`` = split3_bf16(B, 1) [>= roundup(nB, 128), 6 Ep]; the scores are
+    those of ``search_topk`` / ``cosine_scores_split`` and no [nA, nB] matrix is written.  ``slabs``: how many slabs B's rows are cut
+    into (None: sc_search_slabs(nA, nB, 1)); the result does not depend on it, nor on the run."""
+    if not (a_split.is_cuda and b_split.is_cuda and a_ids.is_cuda and b_ids.is_cuda):
+        raise RuntimeError("rank_counts runs on the HIP kernels: no CPU path")
+    assert a_split.dtype == torch.bfloat16 and b_split.dtype == torch.bfloat16 and a_split.dim() == 2 and b_split.dim() == 2
+    assert a_split.is_contiguous() and b_split.is_contiguous()
+    K6 = a_split.shape[1]
+    assert b_split.shape[1] == K6, (a_split.shape, b_split.shape)
+    nA, nB = int(nA), int(nB)
+    assert a_split.shape[0] >= -(-nA // 128) * 128 and b_split.shape[0] >= -(-nB // 128) * 128, (a_split.shape, nA, b_split.shape, nB)
+    assert a_ids.dtype == torch.int64 and b_ids.dtype == torch.int64 and a_ids.is_contiguous() and b_ids.is_contiguous()
+    assert tuple(a_ids.shape) == (nA,) and tuple(b_ids.shape) == (nB,), (a_ids.shape, nA, b_ids.shape, nB)
+    dev = a_split.device
+    S = search_slabs(nA, nB, 1) if slabs is None else int(slabs)
+    out = torch.zeros(2 * (nA + nB), device=dev, dtype=torch.int32)    # the kernel's four outputs, zeroed in one fill
+    key_a, key_b, ahead_a, ahead_b = out[:nA], out[nA: nA + nB], out[nA + nB: 2 * nA + nB], out[2 * nA + nB:]
+    if nA and nB:
+        check(lib().sc_rank_counts_bf16(_p(a_split), _p(b_split), _p(a_ids), _p(b_ids), nA, nB, K6, S, _p(key_a), _p(key_b), _p(ahead_a),
+                                        _p(ahead_b), _stream()), "sc_rank_counts_bf16")
+    return _rank_key_value(key_a), ahead_a, _rank_key_value(key_b), ahead_b
+
+
 def topk_rescore_cos(kw: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, vals: torch.Tensor, eps: float = 1e-8) -> torch.Tensor:
     """vals[r, j] <- cos(kw[r], table[idx[r, j]]) accumulated in fp64 (sc_topk_rescore_cos_f32): kw [rows, E], table [V, E] fp32, idx /
     vals [rows, k] int32 / fp32 contiguous (idx as ops.topk_rows wrote it; -1 -> -inf)."""

@@ -14,7 +14,7 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 
 import torch
 
-__all__ = ["mutualRetrieval", "GalleryIndex", "search"]
+__all__ = ["mutualRetrieval", "GalleryIndex", "search", "mutual_ranks", "recall_from_ranks", "mutual_recall"]
 
 
 def _recall(score: torch.Tensor, query_ids: torch.Tensor, cand_ids: torch.Tensor, ks: Sequence[int], cand_title: str) -> Dict[str, float]:
@@ -170,3 +170,88 @@ def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex], k:
                 ops.cosine_scores_split(q[r0:r1], rnorm, index.split, index.split.shape[0], out=scores[:rp], split_out=split[:rp])
                 ops.topk_rows(scores[: r1 - r0], index.N, k, vals=vals[r0:r1], idx=idx[r0:r1])
     return vals, idx.long()
+
+
+# ------------------------------------------------------------------------------------------------ ranks without the score matrix
+# What ``_recall`` needs of a query is one integer: how many candidates are ahead of its best correct candidate.  csrc/rank.hip
+# produces that integer for every row AND every column in the epilogue of the score GEMM ``search`` runs, so recall at any k, median
+# and mean rank in both directions come from two integer vectors and no [nA, nB] array exists (avssl/module/retrieval.py:45-121 on
+# the scores of avssl/model/kwClip.py:447-482).
+def mutual_ranks(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex], a_ids: torch.Tensor, b_ids: torch.Tensor, cosine: bool = False,
+                 slabs: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """A [nA, E], B [nB, E] (or a GalleryIndex of it), a_ids [nA], b_ids [nB] integer ids; row j of B is a correct candidate for row i
+    of A (and the other way round) iff a_ids[i] == b_ids[j].  -> {"ahead_AB" [nA] int64, "ahead_BA" [nB] int64, "best_AB" [nA] fp32,
+    "best_BA" [nB] fp32} on the device: ``best`` is the score of a query's best correct candidate (-inf: it has none, or only NaN
+    ones) and ``ahead`` the number of candidates ranked ahead of it by ``_recall``'s rule: a higher score, or a wrong candidate with
+    the same score (ties count against the query) or a NaN score.  A query without a correct candidate, or whose best correct score is
+    not finite, gets ``ahead`` = the number of candidates: it never hits.  rank = ahead + 1.
+
+    Scores are ``search``'s: the three-way bf16 splits of both rows multiplied on the bf16 matrix pipe, six K-blocks summed in fp32,
+    within (6 Ep + 8) 2^-24 sum_i |a_i| |b_i| of the exact inner product (Ep = E rounded up to 64); an infinity in a row becomes NaN
+    in the split.  ``cosine=True`` scales the rows of A and B by 1 / max(|x|, 1e-8) first (a GalleryIndex carries its own choice).
+    A is split once, in chunks of rows like a GalleryIndex (12 Ep bytes per row, no second fp32 copy).  ``slabs``: slabs of B's rows
+    in the kernel (tests); the result is bitwise independent of it and of the run."""
+    from . import ops
+    if not isinstance(A, torch.Tensor) or A.dim() != 2:
+        raise ValueError("mutual_ranks: A must be a [nA, E] tensor")
+    b_cuda = B.split.is_cuda if isinstance(B, GalleryIndex) else (isinstance(B, torch.Tensor) and B.is_cuda)
+    if not A.is_cuda or not b_cuda:
+        raise RuntimeError("mutual_ranks runs on the HIP kernels: device tensors only")
+    index = B if isinstance(B, GalleryIndex) else GalleryIndex(B, cosine=cosine)
+    nA, E = A.shape
+    nB = index.N
+    assert E == index.E, (A.shape, index.E)
+    if a_ids.dim() != 1 or b_ids.dim() != 1 or a_ids.numel() != nA or b_ids.numel() != nB:
+        raise AssertionError(f"ids {tuple(a_ids.shape)} / {tuple(b_ids.shape)} do not match {nA} x {nB} rows")
+    dev = A.device
+    a_ids = a_ids.to(device=dev, dtype=torch.int64).contiguous()
+    b_ids = b_ids.to(device=dev, dtype=torch.int64).contiguous()
+    a_split = torch.empty(-(-nA // 128) * 128, 6 * index.Ep, device=dev, dtype=torch.bfloat16)
+    for r0 in range(0, nA, _INDEX_CHUNK_ROWS):
+        r1 = min(nA, r0 + _INDEX_CHUNK_ROWS)
+        _split_rows(_rows_f32(A[r0:r1]), 0, cosine, a_split[r0:])
+    best_a, ahead_a, best_b, ahead_b = ops.rank_counts(a_split, index.split, a_ids, b_ids, nA, nB, slabs=slabs)
+    # key 0 (no correct, non-NaN candidate) came back as -inf; +inf: an overflowed score
+    ahead_a = torch.where(torch.isfinite(best_a), ahead_a.long(), torch.full((), nB, dtype=torch.int64, device=dev))
+    ahead_b = torch.where(torch.isfinite(best_b), ahead_b.long(), torch.full((), nA, dtype=torch.int64, device=dev))
+    return {"ahead_AB": ahead_a, "ahead_BA": ahead_b, "best_AB": best_a, "best_BA": best_b}
+
+
+def recall_from_ranks(ahead: torch.Tensor, n_candidates: int, ks: Sequence[int], cand_title: str = "") -> Dict[str, float]:
+    """ahead [Q] (candidates ahead of each query's best correct one; ``n_candidates`` for a query that never hits) -> recall@k in per
+    cent for every k of ``ks`` as ``_recall`` reports it (a hit iff ahead < k, any k), and with rank = ahead + 1 ``median_rank`` (the
+    mean of the two middle ranks when Q is even) and ``mean_rank``."""
+    out = {}
+    for k in ks:
+        if k > n_candidates:
+            print(f"recall@{k} asks for more than the {n_candidates} {cand_title + ' ' if cand_title else ''}candidates there are; counted over all of them")
+        out[f"recall@{k}"] = 100.0 * (ahead < k).float().mean().item()
+    Q = ahead.numel()
+    if Q == 0:
+        out["median_rank"] = out["mean_rank"] = float("nan")
+        return out
+    rank = torch.sort(ahead.reshape(-1).double() + 1.0).values
+    out["median_rank"] = 0.5 * (rank[(Q - 1) // 2] + rank[Q // 2]).item()
+    out["mean_rank"] = rank.mean().item()
+    return out
+
+
+def mutual_recall(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex], AB_answers: torch.Tensor, BA_answers: torch.Tensor,
+                  recall_at: list, modality_A_title: str = "audio", modality_B_title: str = "image", cosine: bool = False,
+                  slabs: Optional[int] = None, rank_stats: bool = False) -> Tuple[dict, dict, dict]:
+    """``mutualRetrieval``'s three dictionaries (A -> B, B -> A, their mean) from the embeddings instead of the score matrices:
+    ``mutual_recall(A, B, ...)`` reports what ``mutualRetrieval(A @ B.t(), (A @ B.t()).t(), ...)`` reports, on ``mutual_ranks``' scores
+    and without the [nA, nB] matrix.  ``AB_answers`` [nA] / ``BA_answers`` [nB]: the ids of A's and B's rows.  ``rank_stats=True``
+    adds ``median_rank`` and ``mean_rank`` (rank = ahead + 1) to every dictionary.  The scores differ from a torch matmul's in the last
+    bits (see ``mutual_ranks``): two candidates whose exact scores are closer than twice that bound may rank in either order."""
+    if AB_answers.dim() != 1 or BA_answers.dim() != 1:
+        raise AssertionError("answers must be 1-d id vectors")
+    ranks = mutual_ranks(A, B, AB_answers, BA_answers, cosine=cosine, slabs=slabs)
+    nA, nB = AB_answers.numel(), BA_answers.numel()
+    results_AB = recall_from_ranks(ranks["ahead_AB"], nB, recall_at, modality_B_title)
+    results_BA = recall_from_ranks(ranks["ahead_BA"], nA, recall_at, modality_A_title)
+    if not rank_stats:
+        for res in (results_AB, results_BA):
+            del res["median_rank"], res["mean_rank"]
+    results_mean = {key: 0.5 * (results_AB[key] + results_BA[key]) for key in results_AB}
+    return results_AB, results_BA, results_mean
