@@ -601,6 +601,45 @@ int sc_search_topk_bf16(const sc_bf16* q_split, const sc_bf16* g_split, int32_t 
 int sc_rank_counts_bf16(const sc_bf16* a_split, const sc_bf16* b_split, const int64_t* a_ids, const int64_t* b_ids, int32_t nA, int32_t nB,
                         int32_t K6, int32_t S, uint32_t* best_a, uint32_t* best_b, int32_t* ahead_a, int32_t* ahead_b, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Compact gallery search: one bf16 copy of the gallery (2 Ep bytes per row), a coarse fused top-D scan, an exact re-rank of the D
+ * candidates from the fp32 rows and a per-query certificate (csrc/search_compact.hip).  Additive in round 15; sc_abi_version() stays 7.
+ *   replaces: the ranking of avssl/module/retrieval.py:45-46 on the scores of avssl/model/kwClip.py:447-482, as sc_search_topk_bf16 does,
+ *             with a sixth of its gallery bytes and matrix work.
+ *   sc_rows_bf16           x [R, E] fp32 with row pitch ldx, row_scale [R] or NULL (1) -> out [Rp, Ep] bf16 with
+ *                          out[r, i] = bf16_rne(fl32(x[r, i] * row_scale[r])), zero outside [R, E]; Rp % 128 == 0, Ep % 64 == 0.
+ *                          norms [3, R] fp32: per row the 2-norm of the scaled row x', of its rounded image x~ and of the residual
+ *                          x' - x~ (exact in fp32), each accumulated in fp64 and rounded once.  One pass, memory bound.  R == 0 with
+ *                          Rp == 0: no-op.
+ *   sc_search_coarse_bf16  sc_search_topk_bf16's contract on plain bf16 operands q_bf16 [roundup(nQ, 128), Ep] / g_bf16
+ *                          [roundup(N, 128), Ep] (what sc_rows_bf16 writes; padding rows zero).  scores = sum over Ep of bf16 x bf16
+ *                          products on v_mfma_f32_16x16x32_bf16, fp32 accumulation, K-tiles in increasing order.  Writes, per query
+ *                          and slab, the slab's D best as part_vals / part_idx [nQ, S, D], best first, in sc_topk_rows_f32's order:
+ *                          larger first, lower gallery row first among equals, -0 == +0, NaN on top, -inf / -1 behind the last
+ *                          column.  Columns >= N never enter.  1 <= D <= 32; Ep % 64 == 0 (512 works; sc_search_topk_bf16 wants
+ *                          K6 % 384 == 0); S as sc_search_slabs(nQ, N, D) rules; merge S > 1 slabs with sc_topk_rows_f32 + a gather.
+ *                          nQ == 0: no-op; N == 0: -inf / -1.  No atomics; the result is bit-identical for every S.
+ *   sc_search_rerank_f32   q [nQ, E] fp32 (pitch ldq, q_scale [nQ] or NULL), rows [N, E] fp32 (pitch ldr, g_scale [N] or NULL),
+ *                          cand_idx / cand_vals [nQ, D] (the merged coarse lists, best first; an index outside [0, N) is a filler and
+ *                          is no candidate), eps [nQ] fp32, k <= D <= 32.  Per query: the exact score of every candidate,
+ *                          fp32_round(sum_i (double) q'_i * (double) g'_i) with q'_i = fl32(q_i * q_scale), g'_i = fl32(g_i * g_scale)
+ *                          and the sum in fp64; the candidates sorted by exact value descending, gallery row ascending, in
+ *                          sc_topk_rows_f32's key order (NaN on top, -0 == +0); vals [nQ, k] fp32, idx [nQ, k] int32 (-inf / -1 behind
+ *                          the last candidate) and certified [nQ] uint8.  The certificate, evaluated in fp64: 0 if any candidate's
+ *                          coarse or exact value, or eps, is not finite; else 1 if N <= D (every row is a candidate); else 1 iff
+ *                          e_k - |e_k| 2^-23 > t + eps, e_k the k-th best exact value and t the coarse value of the D-th (last)
+ *                          candidate.  A row outside the candidates has a coarse score <= t and an exact score within eps of it, so it
+ *                          is strictly below e_k: it cannot enter the list, not even by a tie.  Deterministic, no atomics, nothing
+ *                          allocated.  nQ == 0: no-op.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_rows_bf16(const float* x, int64_t ldx, const float* row_scale, int32_t R, int32_t E, sc_bf16* out, int32_t Rp, int32_t Ep,
+                 float* norms, void* stream);
+int sc_search_coarse_bf16(const sc_bf16* q_bf16, const sc_bf16* g_bf16, int32_t nQ, int32_t N, int32_t Ep, int32_t D, int32_t S,
+                          float* part_vals, int32_t* part_idx, void* stream);
+int sc_search_rerank_f32(const float* q, int64_t ldq, const float* q_scale, const float* rows, int64_t ldr, const float* g_scale,
+                         const int32_t* cand_idx, const float* cand_vals, const float* eps, int32_t nQ, int32_t N, int32_t E, int32_t D,
+                         int32_t k, float* vals, int32_t* idx, uint8_t* certified, void* stream);
+
 /* Keyword BatchNorm: nn.BatchNorm1d over the keyword positions (avssl/module/speechclip_c_modules/kw_bn.py:167-228).
  *   x [N, E] fp32 (N = batch x keyword slots), per-channel statistics.  training: batch statistics (biased variance for the
  *   normalisation, unbiased for the running estimate; run_mean / run_var updated in place with `momentum`), save_mean / save_rstd

@@ -172,6 +172,10 @@ SIGNATURES = {
     "sc_topk_rescore_cos_f32": [c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "sc_search_slabs": [c_int, c_int, c_int],
     "sc_search_topk_bf16": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "sc_rows_bf16": [c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p],
+    "sc_search_coarse_bf16": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "sc_search_rerank_f32": [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                             c_void_p, c_void_p, c_void_p, c_void_p],
     "sc_rank_counts_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sc_bn_rows_fwd": [c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_i64,
                        c_void_p, c_void_p, c_void_p],

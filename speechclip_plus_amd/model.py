@@ -767,10 +767,14 @@ class KWClip_GeneralTransformer(nn.Module):
         ranking avssl/module/retrieval.py:45-46 computes from the scores of kwClip.py:447-482 and drops).  ``queries``: a [nQ, E]
         tensor of speech embeddings, or a list of waveforms - those go through ``encode_speech``, and ``src`` ("cascaded" /
         "parallel"; None: ``config.retrieval.audio_feat_src``) picks the branch output.  ``gallery``: image or caption embeddings
-        [N, E] (what ``forward_image`` / ``forward_text`` return) or a retrieval.GalleryIndex built with ``cosine=True``.  Query
+        [N, E] (what ``forward_image`` / ``forward_text`` return) or a retrieval.GalleryIndex / CompactGalleryIndex built with
+        ``cosine=True``.  Query
         and gallery rows are brought to unit length as ``forward`` does, so the scores are cosines.  ``k``: None = max(recall_at)."""
-        from .retrieval import GalleryIndex, search
-        g_cuda = gallery.split.is_cuda if isinstance(gallery, GalleryIndex) else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
+        from .retrieval import CompactGalleryIndex, GalleryIndex, search
+        if isinstance(gallery, CompactGalleryIndex):
+            g_cuda = gallery.coarse.is_cuda
+        else:
+            g_cuda = gallery.split.is_cuda if isinstance(gallery, GalleryIndex) else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
         if not g_cuda or (isinstance(queries, torch.Tensor) and not queries.is_cuda):
             raise RuntimeError("retrieve runs on the HIP kernels: device tensors only")
         if isinstance(queries, (list, tuple)):
@@ -787,7 +791,7 @@ class KWClip_GeneralTransformer(nn.Module):
             raise ValueError("retrieve: queries must be a [nQ, E] tensor of embeddings or a list of waveforms")
         k = int(max(self.recall_at)) if k is None else int(k)
         queries = unit_rows(queries.detach().float())
-        if not isinstance(gallery, GalleryIndex):
+        if not isinstance(gallery, (GalleryIndex, CompactGalleryIndex)):
             gallery = unit_rows(gallery.detach().float())
         return search(queries, gallery, k)
 

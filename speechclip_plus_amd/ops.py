@@ -926,6 +926,101 @@ def search_topk(q_split: torch.Tensor, g_split: torch.Tensor, nQ: int, N: int, k
     return vals, idx
 
 
+def rows_bf16(x: torch.Tensor, row_scale: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """x [R, E] fp32 (* row_scale [R]) -> (out [Rp, Ep] bf16, norms [3, R] fp32), Rp / Ep = R / E rounded up to 128 / 64
+    (sc_rows_bf16, csrc/search_compact.hip): the rows rounded to bf16 (nearest even), zero outside [R, E], and per row the 2-norms of
+    the scaled row, of its bf16 image and of their difference, each accumulated in fp64.  ``out``: a caller-owned [Rp, Ep] bf16 buffer."""
+    if not x.is_cuda:
+        raise RuntimeError("rows_bf16 runs on the HIP kernels: no CPU path")
+    assert x.dtype == torch.float32 and x.dim() == 2 and (x.stride(1) == 1 or x.shape[1] == 1)
+    R, E = x.shape
+    Rp, Ep = -(-R // 128) * 128, -(-E // 64) * 64
+    if out is None:
+        out = torch.empty(Rp, Ep, device=x.device, dtype=torch.bfloat16)
+    assert out.dtype == torch.bfloat16 and tuple(out.shape) == (Rp, Ep) and out.is_contiguous()
+    norms = torch.empty(3, R, device=x.device, dtype=torch.float32)
+    if row_scale is not None:
+        assert row_scale.dtype == torch.float32 and tuple(row_scale.shape) == (R,) and row_scale.is_contiguous()
+    if R:
+        check(lib().sc_rows_bf16(_p(x), x.stride(0) if R > 1 else E, _p(row_scale), R, E, _p(out), Rp, Ep, _p(norms), _stream()), "sc_rows_bf16")
+    return out, norms
+
+
+def search_coarse(q_bf16: torch.Tensor, g_bf16: torch.Tensor, nQ: int, N: int, D: int, slabs: Optional[int] = None,
+                  vals: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None):
+    """The D best of N gallery rows for each of nQ queries by their bf16 x bf16 scores (sc_search_coarse_bf16, csrc/search_compact.hip):
+    ``q_bf16`` = rows_bf16(queries) [>= roundup(nQ, 128), Ep], ``g_bf16`` = rows_bf16(gallery) [>= roundup(N, 128), Ep] ->
+    (vals [nQ, D] fp32, idx [nQ, D] int32), best first in ``topk_rows``' order (ties to the lower gallery row, NaN first, -inf / -1
+    behind the N-th entry).  ``slabs``: None = sc_search_slabs(nQ, N, D); the result does not depend on it.  More than one slab: the
+    per-slab lists [nQ, S, D] are merged by ``topk_rows`` and one gather, as ``search_topk`` merges them."""
+    if not (q_bf16.is_cuda and g_bf16.is_cuda):
+        raise RuntimeError("search_coarse runs on the HIP kernels: no CPU path")
+    assert q_bf16.dtype == torch.bfloat16 and g_bf16.dtype == torch.bfloat16 and q_bf16.dim() == 2 and g_bf16.dim() == 2
+    assert q_bf16.is_contiguous() and g_bf16.is_contiguous()
+    Ep = q_bf16.shape[1]
+    assert g_bf16.shape[1] == Ep, (q_bf16.shape, g_bf16.shape)
+    nQ, N, D = int(nQ), int(N), int(D)
+    assert q_bf16.shape[0] >= -(-nQ // 128) * 128 and g_bf16.shape[0] >= -(-N // 128) * 128, (q_bf16.shape, nQ, g_bf16.shape, N)
+    dev = q_bf16.device
+    if vals is None:
+        vals = torch.empty(nQ, D, device=dev, dtype=torch.float32)
+    if idx is None:
+        idx = torch.empty(nQ, D, device=dev, dtype=torch.int32)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
+    assert tuple(vals.shape) == (nQ, D) and tuple(idx.shape) == (nQ, D)
+    S = search_slabs(nQ, N, D) if slabs is None else int(slabs)
+    if S == 1 or nQ == 0:
+        pv, pi = vals, idx
+    else:
+        pv = torch.empty(nQ, S * D, device=dev, dtype=torch.float32)
+        pi = torch.empty(nQ, S * D, device=dev, dtype=torch.int32)
+    null = ctypes.c_void_p(0)
+    check(lib().sc_search_coarse_bf16(_p(q_bf16) if nQ else null, _p(g_bf16) if N else null, nQ, N, Ep, D, S, _p(pv) if nQ else null,
+                                      _p(pi) if nQ else null, _stream()), "sc_search_coarse_bf16")
+    if pv is not vals:
+        _, pos = topk_rows(pv, S * D, D, vals=vals)
+        torch.gather(pi, 1, pos.long(), out=idx)
+    return vals, idx
+
+
+def search_rerank(q: torch.Tensor, q_scale: Optional[torch.Tensor], rows: torch.Tensor, g_scale: Optional[torch.Tensor],
+                  cand_idx: torch.Tensor, cand_vals: torch.Tensor, eps: torch.Tensor, k: int, vals: Optional[torch.Tensor] = None,
+                  idx: Optional[torch.Tensor] = None, certified: Optional[torch.Tensor] = None):
+    """Exact re-rank of coarse candidates (sc_search_rerank_f32, csrc/search_compact.hip): ``q`` [nQ, E] / ``rows`` [N, E] fp32 (unit
+    column stride, any pitch), ``q_scale`` [nQ] / ``g_scale`` [N] or None, ``cand_idx`` / ``cand_vals`` [nQ, D] int32 / fp32 (best
+    first, -1 = no candidate), ``eps`` [nQ] fp32 -> (vals [nQ, k] fp32, idx [nQ, k] int32, certified [nQ] uint8): the k best
+    candidates by their inner product accumulated in fp64 (rows scaled in fp32 first), and 1 where no row outside the candidates can
+    belong to the list: every value finite and (N <= D or e_k - |e_k| 2^-23 > cand_vals[:, D - 1] + eps)."""
+    if not (q.is_cuda and rows.is_cuda and cand_idx.is_cuda):
+        raise RuntimeError("search_rerank runs on the HIP kernels: no CPU path")
+    assert q.dtype == torch.float32 and rows.dtype == torch.float32 and q.dim() == 2 and rows.dim() == 2
+    assert (q.stride(1) == 1 or q.shape[1] == 1) and (rows.stride(1) == 1 or rows.shape[1] == 1)
+    nQ, E = q.shape
+    N = rows.shape[0]
+    assert rows.shape[1] == E, (q.shape, rows.shape)
+    D, k = int(cand_idx.shape[1]), int(k)
+    assert cand_idx.dtype == torch.int32 and cand_vals.dtype == torch.float32 and cand_idx.is_contiguous() and cand_vals.is_contiguous()
+    assert tuple(cand_idx.shape) == (nQ, D) and tuple(cand_vals.shape) == (nQ, D) and 1 <= k <= D <= 32, (cand_idx.shape, cand_vals.shape, k)
+    assert eps.dtype == torch.float32 and tuple(eps.shape) == (nQ,) and eps.is_contiguous()
+    for s, n in ((q_scale, nQ), (g_scale, N)):
+        assert s is None or (s.dtype == torch.float32 and tuple(s.shape) == (n,) and s.is_contiguous())
+    dev = q.device
+    if vals is None:
+        vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
+    if idx is None:
+        idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
+    if certified is None:
+        certified = torch.empty(nQ, device=dev, dtype=torch.uint8)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and certified.dtype == torch.uint8
+    assert vals.is_contiguous() and idx.is_contiguous() and certified.is_contiguous()
+    assert tuple(vals.shape) == (nQ, k) and tuple(idx.shape) == (nQ, k) and tuple(certified.shape) == (nQ,)
+    if nQ:
+        check(lib().sc_search_rerank_f32(_p(q), q.stride(0) if nQ > 1 else E, _p(q_scale), _p(rows) if N else ctypes.c_void_p(0),
+                                         rows.stride(0) if N > 1 else E, _p(g_scale), _p(cand_idx), _p(cand_vals), _p(eps), nQ, N, E, D, k,
+                                         _p(vals), _p(idx), _p(certified), _stream()), "sc_search_rerank_f32")
+    return vals, idx, certified
+
+
 def _rank_key_value(key: torch.Tensor) -> torch.Tensor:
     """the uint32 keys of csrc/rank.hip (held as int32 bits) -> the fp32 values they stand for; key 0 (no candidate) -> -inf"""
     bits = torch.where(key < 0, key & 0x7fffffff, ~key)                # key >= 2^31: a value >= 0 with its sign bit set; below: the complement

@@ -14,7 +14,8 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 
 import torch
 
-__all__ = ["mutualRetrieval", "GalleryIndex", "search", "mutual_ranks", "recall_from_ranks", "mutual_recall"]
+__all__ = ["mutualRetrieval", "GalleryIndex", "search", "mutual_ranks", "recall_from_ranks", "mutual_recall", "CompactGalleryIndex",
+           "search_compact", "compact_eps"]
 
 
 def _recall(score: torch.Tensor, query_ids: torch.Tensor, cand_ids: torch.Tensor, ks: Sequence[int], cand_title: str) -> Dict[str, float]:
@@ -114,7 +115,7 @@ class GalleryIndex:
         return self.N
 
 
-def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex], k: int, cosine: bool = False,
+def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex, "CompactGalleryIndex"], k: int, cosine: bool = False,
            slabs: Optional[int] = None, route: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """queries [nQ, E], gallery [N, E] (or a GalleryIndex of it) -> (vals [nQ, k] fp32, idx [nQ, k] int64): for every query the k
     gallery rows with the largest inner product, best first, on the device.  ``cosine=True`` scales query and gallery rows by
@@ -130,8 +131,13 @@ def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex], k:
     the selection runs in the score GEMM's epilogue, the [nQ, N] score matrix is never written, queries go in chunks of 16384
     rows) or "composition" (the same score GEMM into one 128 MiB scratch per chunk of queries + ops.topk_rows; faster on small
     galleries); both give the same lists.  ``slabs``: slabs of the gallery axis of the fused kernel (tests; implies "fused"; the
-    result does not depend on it)."""
+    result does not depend on it).  A CompactGalleryIndex as ``gallery``: ``search_compact(queries, gallery, k)[:2]`` - the same lists
+    from the bf16 copy, with re-rank scores as ``vals`` (see there)."""
     from . import ops
+    if isinstance(gallery, CompactGalleryIndex):      # the compact route (below): exact lists through the certificate and its fallback
+        if route is not None:
+            raise ValueError("search: route applies to a GalleryIndex or a tensor, not to a CompactGalleryIndex")
+        return search_compact(queries, gallery, k, cosine=cosine, slabs=slabs)[:2]
     if not isinstance(queries, torch.Tensor) or queries.dim() != 2:
         raise ValueError("search: queries must be a [nQ, E] tensor")
     g_cuda = gallery.split.is_cuda if isinstance(gallery, GalleryIndex) else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
@@ -170,6 +176,153 @@ def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex], k:
                 ops.cosine_scores_split(q[r0:r1], rnorm, index.split, index.split.shape[0], out=scores[:rp], split_out=split[:rp])
                 ops.topk_rows(scores[: r1 - r0], index.N, k, vals=vals[r0:r1], idx=idx[r0:r1])
     return vals, idx.long()
+
+
+# ------------------------------------------------------------------------------------------------ compact gallery search
+# A GalleryIndex costs 12 Ep bytes per gallery row and six K-blocks per score.  The compact index keeps ONE bf16 copy (2 Ep bytes per
+# row) for a coarse top-D scan (csrc/search_compact.hip), re-ranks the D candidates exactly from the fp32 rows and certifies, per
+# query, that no row outside the candidates can belong to the answer; a query without the certificate goes through ``search``.
+_FALLBACK_CHUNK_ROWS = 131072      # gallery rows per temporary GalleryIndex of the exact fallback
+
+
+def compact_eps(q_norms: torch.Tensor, gmax: float, gtmax: float, dmax: float, Ep: int) -> torch.Tensor:
+    """The bound on |exact - coarse| of a query against ANY gallery row, in fp64: ``q_norms`` [3, nQ] = (|q'|, |q~|, |q' - q~|) as
+    ``ops.rows_bf16`` reports them (q' the scaled fp32 row, q~ its bf16 image), ``gmax`` / ``gtmax`` / ``dmax`` the largest |g'|, |g~|
+    and |g' - g~| over the gallery, ``Ep`` the padded row length.  With exact - coarse_true = sum (q' - q~) g' + sum q~ (g' - g~),
+    Cauchy-Schwarz on both sums and the fp32 accumulation of Ep products in the project's usual form:
+
+        eps = (|q' - q~| gmax + |q~| dmax + (Ep + 8) 2^-24 |q~| gtmax) (1 + 2^-20)
+
+    (the last factor covers the fp32 roundings of the norms and of eps itself).  -> [nQ] fp64 on ``q_norms``' device."""
+    n = q_norms.double()
+    return (n[2] * float(gmax) + n[1] * float(dmax) + (Ep + 8) * 2.0 ** -24 * n[1] * float(gtmax)) * (1.0 + 2.0 ** -20)
+
+
+class CompactGalleryIndex:
+    """A gallery [N, E] prepared for ``search_compact``: ``coarse`` = its rows rounded to bf16 ([roundup(N, 128), Ep] bf16, Ep = E
+    rounded up to 64: 2 Ep bytes per gallery row, a sixth of a GalleryIndex), built in chunks of rows; ``rows`` = the fp32 gallery the
+    exact re-rank reads - kept BY REFERENCE when it is already fp32 on the device with unit column stride (the caller must not modify
+    it afterwards), one fp32 copy otherwise; ``rnorm`` [N] = 1 / max(|g|, 1e-8) for ``cosine=True`` (the scores against unit or
+    ``cosine=True`` queries are then cosines), else None; ``gmax`` / ``gtmax`` / ``dmax`` = the largest norm of a scaled row, of its
+    bf16 image and of their difference (``compact_eps``); ``nbytes`` = what the index itself allocated."""
+
+    def __init__(self, gallery: torch.Tensor, cosine: bool = False):
+        from . import ops
+        if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2:
+            raise ValueError("CompactGalleryIndex: gallery must be a [N, E] tensor")
+        if not gallery.is_cuda:
+            raise RuntimeError("CompactGalleryIndex runs on the HIP kernels: device tensors only")
+        self.N, self.E = int(gallery.shape[0]), int(gallery.shape[1])
+        assert self.E >= 1, gallery.shape
+        self.cosine = bool(cosine)
+        self.Ep = -(-self.E // 64) * 64
+        self.rows = _rows_f32(gallery)
+        held = self.rows.data_ptr() == gallery.data_ptr() and gallery.dtype == torch.float32
+        self.coarse = torch.empty(-(-self.N // 128) * 128, self.Ep, device=gallery.device, dtype=torch.bfloat16)
+        self.rnorm = torch.empty(self.N, device=gallery.device, dtype=torch.float32) if self.cosine else None
+        top = torch.zeros(3, device=gallery.device, dtype=torch.float32)
+        for r0 in range(0, self.N, _INDEX_CHUNK_ROWS):
+            r1 = min(self.N, r0 + _INDEX_CHUNK_ROWS)
+            x = self.rows[r0:r1]
+            scale = None
+            if self.cosine:
+                self.rnorm[r0:r1] = ops.vq_prep(x)[1]
+                scale = self.rnorm[r0:r1]
+            _, norms = ops.rows_bf16(x, scale, out=self.coarse[r0: r0 + -(-(r1 - r0) // 128) * 128])
+            top = torch.maximum(top, norms.amax(dim=1))               # amax / maximum carry a NaN on
+        self.gmax, self.gtmax, self.dmax = (float(v) for v in top.tolist())
+        self.nbytes = self.coarse.numel() * 2 + (self.rnorm.numel() * 4 if self.cosine else 0) + (0 if held else self.rows.numel() * 4)
+
+    @property
+    def device(self) -> torch.device:
+        return self.coarse.device
+
+    def __len__(self) -> int:
+        return self.N
+
+
+def _exact_fallback(q: torch.Tensor, index: CompactGalleryIndex, k: int, cosine: bool):
+    """q [nU, E] fp32 -> (vals [nU, k] fp32, idx [nU, k] int32) by ``search`` against the fp32 rows, the gallery in chunks of
+    ``_FALLBACK_CHUNK_ROWS`` rows (a temporary GalleryIndex each), the per-chunk lists merged in index order and the k survivors
+    re-scored by ``ops.search_rerank``"""
+    from . import ops
+    nU, dev = q.shape[0], q.device
+    pv, pi = [], []
+    for c0 in range(0, max(index.N, 1), _FALLBACK_CHUNK_ROWS):
+        c1 = min(index.N, c0 + _FALLBACK_CHUNK_ROWS)
+        v, i = search(q, GalleryIndex(index.rows[c0:c1], cosine=index.cosine), k, cosine=cosine)
+        pv.append(v)
+        pi.append(torch.where(i >= 0, i + c0, i))
+    if len(pv) == 1:
+        cv, ci = pv[0], pi[0].int()
+    else:      # chunk order is index order and only the last chunk can end in fillers: position order keeps the tie rule
+        allv, alli = torch.cat(pv, dim=1), torch.cat(pi, dim=1)
+        cv, pos = ops.topk_rows(allv, allv.shape[1], k)
+        ci = torch.gather(alli, 1, pos.long()).int()
+    q_scale = ops.vq_prep(q)[1] if cosine else None
+    vals, idx, _ = ops.search_rerank(q, q_scale, index.rows, index.rnorm, ci.contiguous(), cv.contiguous(),
+                                     torch.zeros(nU, device=dev, dtype=torch.float32), k)
+    return vals, idx
+
+
+def search_compact(queries: torch.Tensor, gallery: Union[torch.Tensor, CompactGalleryIndex], k: int, cosine: bool = False, depth: int = 32,
+                   fallback: str = "exact", slabs: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """queries [nQ, E], gallery [N, E] (or a CompactGalleryIndex of it) -> (vals [nQ, k] fp32, idx [nQ, k] int64, certified [nQ] bool):
+    ``search``'s lists from a bf16 copy of the gallery.  1 <= k <= depth <= 32.  Per query: the ``depth`` best rows by the bf16 x bf16
+    score (one K-block instead of six), re-ranked by their inner products accumulated in fp64 from the fp32 rows, and the certificate
+    ``certified``: the k-th exact value lies above the last candidate's coarse value by more than ``compact_eps``, so no row outside
+    the candidates can belong to the list, not even by a tie.  Order and tails are ``search``'s (larger first, lower gallery row among
+    equals, NaN on top, -inf / -1 behind the N-th entry).  ``vals`` are the re-rank scores - the fp64 sum rounded once, closer to the
+    exact inner product than ``search``'s fp32 scores - so where ``search`` orders two rows by rounding noise the lists may differ.
+    ``cosine=True`` scales query and gallery rows by 1 / max(|x|, 1e-8) (an index carries its own choice; the flag then applies to the
+    queries).  Queries go in chunks of 16384 rows through one reused bf16 buffer.
+
+    ``fallback="exact"`` (default): the mask is read on the host - the one synchronisation of the call - and every uncertified query
+    is searched again by ``search`` against the fp32 rows, in gallery chunks of 131072 rows, and re-scored the same way; their
+    ``certified`` stays False.  This costs a PASS OVER THE WHOLE GALLERY (a three-way split of every chunk included) whenever any row
+    is uncertified.  ``fallback="none"``: no synchronisation; an uncertified row holds the best k of its candidates.  ``slabs``:
+    at most so many slabs of the coarse kernel's gallery axis (tests; empty slabs are dropped, the result does not depend on it)."""
+    from . import ops
+    if not isinstance(queries, torch.Tensor) or queries.dim() != 2:
+        raise ValueError("search_compact: queries must be a [nQ, E] tensor")
+    g_cuda = gallery.coarse.is_cuda if isinstance(gallery, CompactGalleryIndex) else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
+    if not queries.is_cuda or not g_cuda:
+        raise RuntimeError("search_compact runs on the HIP kernels: device tensors only")
+    if fallback not in ("exact", "none"):
+        raise ValueError(f"search_compact: fallback = {fallback!r} (\"exact\" or \"none\")")
+    index = gallery if isinstance(gallery, CompactGalleryIndex) else CompactGalleryIndex(gallery, cosine=cosine)
+    nQ, E = queries.shape
+    assert E == index.E, (queries.shape, index.E)
+    k, D = int(k), int(depth)
+    assert 1 <= k <= D <= 32, f"k = {k}, depth = {D}: 1 <= k <= depth <= 32"
+    dev = queries.device
+    vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
+    cert = torch.empty(nQ, device=dev, dtype=torch.uint8)
+    if nQ == 0:
+        return vals, idx.long(), cert.bool()
+    q = _rows_f32(queries)
+    if slabs is not None:      # at most ``slabs`` slabs of whole column tiles, none of them empty (sc_search_slabs' rule)
+        nT = max(-(-index.N // 128), 1)
+        slabs = -(-nT // -(-nT // max(min(int(slabs), nT), 1)))
+    chunk = min(_INDEX_CHUNK_ROWS, -(-nQ // 128) * 128)
+    qbuf = torch.empty(chunk, index.Ep, device=dev, dtype=torch.bfloat16)                # the one query buffer of the call
+    for r0 in range(0, nQ, chunk):
+        r1 = min(nQ, r0 + chunk)
+        qc = q[r0:r1]
+        q_scale = ops.vq_prep(qc)[1] if cosine else None
+        q16, norms = ops.rows_bf16(qc, q_scale, out=qbuf[: -(-(r1 - r0) // 128) * 128])
+        eps = compact_eps(norms, index.gmax, index.gtmax, index.dmax, index.Ep).float()
+        cv, ci = ops.search_coarse(q16, index.coarse, r1 - r0, index.N, D, slabs=slabs)
+        ops.search_rerank(qc, q_scale, index.rows, index.rnorm, ci, cv, eps, k, vals=vals[r0:r1], idx=idx[r0:r1], certified=cert[r0:r1])
+    cert = cert.bool()
+    if fallback == "exact":
+        todo = torch.nonzero(~cert).squeeze(1)                        # the host reads the mask here
+        if todo.numel():
+            fv, fi = _exact_fallback(q[todo].contiguous(), index, k, cosine)
+            vals[todo] = fv
+            idx[todo] = fi
+    return vals, idx.long(), cert
 
 
 # ------------------------------------------------------------------------------------------------ ranks without the score matrix
