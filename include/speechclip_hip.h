@@ -640,6 +640,40 @@ int sc_search_rerank_f32(const float* q, int64_t ldq, const float* q_scale, cons
                          const int32_t* cand_idx, const float* cand_vals, const float* eps, int32_t nQ, int32_t N, int32_t E, int32_t D,
                          int32_t k, float* vals, int32_t* idx, uint8_t* certified, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Filtered gallery search: sc_search_topk_bf16 / sc_topk_rows_f32 over the admissible gallery rows only (csrc/search_filter.hip).
+ * Additive in round 16; sc_abi_version() stays 7.
+ *   replaces: score.masked_fill(mask, -inf) + torch.topk over the whole [nQ, N] matrix of the scores of avssl/model/kwClip.py:447-482
+ *             (ranked by avssl/module/retrieval.py:45-46): excluding a query's own item and its sibling captions, mining the k
+ *             highest-scoring wrong items of an anchor, dropping removed rows of a built index.
+ *   THE RULE (one definition for every layer).  Gallery row j is ADMISSIBLE for query i iff
+ *       j < N,  and  live == NULL or live[j] != 0,  and  the ids are NULL or g_ids[j] != q_ids[i].
+ *   q_ids [nQ] / g_ids [N] are int64, both or neither, all 64 bits compared, negative values legal; live [N] is uint8.  Neither
+ *   g_ids nor live is padded: nothing at or past N is read.  The result is sc_topk_rows_f32's order over the admissible rows only:
+ *   larger score first, lower gallery row first among equal scores (-0 == +0), NaN above every number, -inf / -1 behind the last
+ *   admissible row.  An inadmissible row never appears, whatever its score (NaN included); an admissible row has the fp32 bits the
+ *   unfiltered entry gives it; an admissible row whose score is a real -inf ranks ahead of every filler, in every slab arrangement.
+ *   sc_search_topk_filtered_bf16  sc_search_topk_bf16's operands, arithmetic and slabs (S >= 1 slabs of ceil(tiles / S) column
+ *                                 tiles; a slab past the last tile is empty).  With a filter any slab may hold fewer than k
+ *                                 admissible rows, so the per-slab lists are written as 64-bit words, part [nQ, S, k] uint64, best
+ *                                 first: word = key << 32 | ~row (key = sc_topk_rows_f32's order as a uint32: float order,
+ *                                 -0 == +0, every NaN 0xffffffff, -inf 0x007fffff), 0 = no entry.  Always merge with
+ *                                 sc_search_merge_u64 (S = 1 included: it decodes).  1 <= k <= 32; K6 % 384 == 0; nQ == 0: no-op;
+ *                                 N == 0: empty lists.
+ *   sc_search_merge_u64           part [nQ, S, k] -> vals [nQ, k] fp32 / idx [nQ, k] int32: per query the k largest words, decoded
+ *                                 (a zero comes back as +0, every NaN as the default NaN, no entry as -inf / -1).  Words of
+ *                                 distinct rows are distinct, so the order is total and does not depend on S.
+ *   sc_topk_rows_filtered_f32     sc_topk_rows_f32's contract (scores [rows, ld], V valid columns, 16-byte loads when the base is
+ *                                 16-byte aligned and ld % 4 == 0, vals are the matrix's own bits) with q_ids [rows] / g_ids [V] /
+ *                                 live [V].  Inadmissible columns are skipped; the score matrix is not modified.  1 <= k <= 32.
+ *   All three: argument checks in front of any launch, no atomics, nothing allocated, bit-identical results for every S and run.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_search_topk_filtered_bf16(const sc_bf16* q_split, const sc_bf16* g_split, int32_t nQ, int32_t N, int32_t K6, int32_t k, int32_t S,
+                                 const int64_t* q_ids, const int64_t* g_ids, const uint8_t* live, uint64_t* part, void* stream);
+int sc_search_merge_u64(const uint64_t* part, int32_t nQ, int32_t S, int32_t k, float* vals, int32_t* idx, void* stream);
+int sc_topk_rows_filtered_f32(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, const int64_t* q_ids,
+                              const int64_t* g_ids, const uint8_t* live, float* vals, int32_t* idx, void* stream);
+
 /* Keyword BatchNorm: nn.BatchNorm1d over the keyword positions (avssl/module/speechclip_c_modules/kw_bn.py:167-228).
  *   x [N, E] fp32 (N = batch x keyword slots), per-channel statistics.  training: batch statistics (biased variance for the
  *   normalisation, unbiased for the running estimate; run_mean / run_var updated in place with `momentum`), save_mean / save_rstd

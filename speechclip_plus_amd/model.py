@@ -762,14 +762,18 @@ class KWClip_GeneralTransformer(nn.Module):
         return {"cascaded_audio_feat": output["cascaded_audio_feat"], "parallel_audio_feat": output["parallel_audio_feat"],
                 "vq_results": output["vq_results"], "keywords": output["keywords"]}
 
-    def retrieve(self, queries, gallery, k: Optional[int] = None, src: Optional[str] = None):
+    def retrieve(self, queries, gallery, k: Optional[int] = None, src: Optional[str] = None, query_ids: Optional[torch.Tensor] = None,
+                 gallery_ids: Optional[torch.Tensor] = None):
         """Which gallery items a query retrieves: (vals [nQ, k] fp32, idx [nQ, k] int64), best first (retrieval.search; the
         ranking avssl/module/retrieval.py:45-46 computes from the scores of kwClip.py:447-482 and drops).  ``queries``: a [nQ, E]
         tensor of speech embeddings, or a list of waveforms - those go through ``encode_speech``, and ``src`` ("cascaded" /
         "parallel"; None: ``config.retrieval.audio_feat_src``) picks the branch output.  ``gallery``: image or caption embeddings
         [N, E] (what ``forward_image`` / ``forward_text`` return) or a retrieval.GalleryIndex / CompactGalleryIndex built with
         ``cosine=True``.  Query
-        and gallery rows are brought to unit length as ``forward`` does, so the scores are cosines.  ``k``: None = max(recall_at)."""
+        and gallery rows are brought to unit length as ``forward`` does, so the scores are cosines.  ``k``: None = max(recall_at).
+        ``query_ids`` [nQ] / ``gallery_ids`` [N] (int64 device tensors): a gallery row whose id equals the query's is left out of that
+        query's list (retrieval.search's filter - a spoken caption must not retrieve itself or its siblings).  A tensor gallery takes
+        ``gallery_ids``; a GalleryIndex brings its own ``ids`` and its ``live`` mask.  Without ids the call is the unfiltered one."""
         from .retrieval import CompactGalleryIndex, GalleryIndex, search
         if isinstance(gallery, CompactGalleryIndex):
             g_cuda = gallery.coarse.is_cuda
@@ -793,7 +797,9 @@ class KWClip_GeneralTransformer(nn.Module):
         queries = unit_rows(queries.detach().float())
         if not isinstance(gallery, (GalleryIndex, CompactGalleryIndex)):
             gallery = unit_rows(gallery.detach().float())
-        return search(queries, gallery, k)
+        if query_ids is None and gallery_ids is None:
+            return search(queries, gallery, k)
+        return search(queries, gallery, k, query_ids=query_ids, gallery_ids=gallery_ids)
 
     def extract_keywords(self, wav) -> dict:
         """kwClip.py:1093-1103, the inference entry of the keyword recipes: ``wav`` one 1-D waveform (or a list of them) ->

@@ -926,6 +926,118 @@ def search_topk(q_split: torch.Tensor, g_split: torch.Tensor, nQ: int, N: int, k
     return vals, idx
 
 
+def check_filter_tensor(name: str, what: str, t, n: int, dtypes=(torch.int64,)) -> None:
+    """``t`` as a filter operand ``what`` of ``name``: a contiguous tensor [n] of one of ``dtypes`` (where it lives: ``filter_operands``)"""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: {what} must be a tensor")
+    if t.dtype not in dtypes:
+        raise ValueError(f"{name}: {what} must be {' or '.join(str(d) for d in dtypes)}, not {t.dtype}")
+    if t.dim() != 1 or t.numel() != n:
+        raise ValueError(f"{name}: {what} has shape {tuple(t.shape)}, expected ({n},)")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be contiguous")
+
+
+def filter_operands(name: str, nQ: int, N: int, q_ids, g_ids, live, dev, names=("q_ids", "g_ids", "live")):
+    """The filter operands of the filtered entries, checked before any launch: ``q_ids`` [nQ] / ``g_ids`` [N] int64 (both or neither),
+    ``live`` [N] bool or uint8, all contiguous and on the device ``dev`` (None: any one device is taken).  Format errors are reported
+    before device errors.  -> (q_ids, g_ids, live as uint8), each a tensor or None.  ``names``: what the caller calls them."""
+    if (q_ids is None) != (g_ids is None):
+        raise ValueError(f"{name}: ids on one side only - give {names[0]} and {names[1]}, or neither")
+    given = [(what, t, n, dtypes) for what, t, n, dtypes in ((names[0], q_ids, nQ, (torch.int64,)), (names[1], g_ids, N, (torch.int64,)),
+                                                             (names[2], live, N, (torch.bool, torch.uint8))) if t is not None]
+    for what, t, n, dtypes in given:
+        check_filter_tensor(name, what, t, n, dtypes)
+    for what, t, _, _ in given:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} runs on the HIP kernels: device tensors only ({what})")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"{name}: {what} is on {t.device}, the operands on {dev}")
+    if live is not None and live.dtype == torch.bool:
+        live = live.view(torch.uint8)                     # the same bytes: True is 1
+    return q_ids, g_ids, live
+
+
+def topk_rows_filtered(scores: torch.Tensor, V: int, k: int, q_ids: Optional[torch.Tensor] = None, g_ids: Optional[torch.Tensor] = None,
+                       live: Optional[torch.Tensor] = None, vals: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None):
+    """``topk_rows`` over the admissible columns only (sc_topk_rows_filtered_f32, csrc/search_filter.hip): column j is admissible for
+    row i iff j < V, ``live`` is None or live[j] != 0, and the ids are None or g_ids[j] != q_ids[i] (``q_ids`` [rows] / ``g_ids`` [V]
+    int64, both or neither; ``live`` [V] bool or uint8).  -> (vals [rows, k] fp32, idx [rows, k] int32), ``topk_rows``' order over the
+    admissible columns, -inf / -1 behind the last of them; an admissible -inf keeps its column.  ``scores`` is not modified."""
+    if not scores.is_cuda:
+        raise RuntimeError("topk_rows_filtered runs on the HIP kernels: no CPU path")
+    assert scores.dtype == torch.float32 and scores.dim() == 2 and (scores.stride(1) == 1 or scores.shape[1] == 1)
+    rows, V, k = scores.shape[0], int(V), int(k)
+    assert scores.shape[1] >= V, (scores.shape, V)
+    q_ids, g_ids, live = filter_operands("topk_rows_filtered", rows, V, q_ids, g_ids, live, scores.device)
+    ld = scores.stride(0) if rows > 1 else max(V, 1)
+    if vals is None:
+        vals = torch.empty(rows, k, device=scores.device, dtype=torch.float32)
+    if idx is None:
+        idx = torch.empty(rows, k, device=scores.device, dtype=torch.int32)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
+    assert tuple(vals.shape) == (rows, k) and tuple(idx.shape) == (rows, k)
+    null = ctypes.c_void_p(0)
+    check(lib().sc_topk_rows_filtered_f32(_p(scores) if rows else null, ld, rows, V, k, _p(q_ids), _p(g_ids), _p(live),
+                                          _p(vals) if rows else null, _p(idx) if rows else null, _stream()), "sc_topk_rows_filtered_f32")
+    return vals, idx
+
+
+def search_merge(part: torch.Tensor, k: int, vals: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None):
+    """part [nQ, S, k] int64 - the per-slab list words ``search_topk_filtered``'s kernel writes (key << 32 | ~row, best first, 0 = no
+    entry) -> (vals [nQ, k] fp32, idx [nQ, k] int32): per query the k largest words, decoded; -inf / -1 where a query has fewer than
+    k entries (sc_search_merge_u64).  A real -inf is an entry and ranks ahead of every filler, whichever slab holds it."""
+    if not part.is_cuda:
+        raise RuntimeError("search_merge runs on the HIP kernels: no CPU path")
+    assert part.dtype == torch.int64 and part.dim() == 3 and part.is_contiguous() and part.shape[2] == int(k), (part.dtype, part.shape, k)
+    nQ, S, k = part.shape[0], part.shape[1], int(k)
+    if vals is None:
+        vals = torch.empty(nQ, k, device=part.device, dtype=torch.float32)
+    if idx is None:
+        idx = torch.empty(nQ, k, device=part.device, dtype=torch.int32)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
+    assert tuple(vals.shape) == (nQ, k) and tuple(idx.shape) == (nQ, k)
+    null = ctypes.c_void_p(0)
+    check(lib().sc_search_merge_u64(_p(part) if nQ else null, nQ, S, k, _p(vals) if nQ else null, _p(idx) if nQ else null, _stream()),
+          "sc_search_merge_u64")
+    return vals, idx
+
+
+def search_topk_filtered(q_split: torch.Tensor, g_split: torch.Tensor, nQ: int, N: int, k: int, q_ids: Optional[torch.Tensor] = None,
+                         g_ids: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None, slabs: Optional[int] = None,
+                         vals: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None):
+    """``search_topk`` over the admissible gallery rows only (sc_search_topk_filtered_bf16 + sc_search_merge_u64,
+    csrc/search_filter.hip): gallery row j is admissible for query i iff j < N, ``live`` is None or live[j] != 0, and the ids are None
+    or g_ids[j] != q_ids[i] (``q_ids`` [nQ] / ``g_ids`` [N] int64, both or neither, all 64 bits compared; ``live`` [N] bool or uint8).
+    Operands, scores and order are ``search_topk``'s; an inadmissible row never appears, -inf / -1 stand behind the last admissible
+    row, and an admissible row scoring a real -inf ranks ahead of them.  ``slabs``: None = sc_search_slabs; any S >= 1 is legal here
+    (a slab may hold no admissible row at all) and the result does not depend on it.  The per-slab lists [nQ, S, k] are 64-bit
+    words, merged and decoded by ``search_merge``.  ``vals`` / ``idx``: caller-owned contiguous outputs."""
+    if not (q_split.is_cuda and g_split.is_cuda):
+        raise RuntimeError("search_topk_filtered runs on the HIP kernels: no CPU path")
+    assert q_split.dtype == torch.bfloat16 and g_split.dtype == torch.bfloat16 and q_split.dim() == 2 and g_split.dim() == 2
+    assert q_split.is_contiguous() and g_split.is_contiguous()
+    K6 = q_split.shape[1]
+    assert g_split.shape[1] == K6, (q_split.shape, g_split.shape)
+    nQ, N, k = int(nQ), int(N), int(k)
+    assert q_split.shape[0] >= -(-nQ // 128) * 128 and g_split.shape[0] >= -(-N // 128) * 128, (q_split.shape, nQ, g_split.shape, N)
+    dev = q_split.device
+    q_ids, g_ids, live = filter_operands("search_topk_filtered", nQ, N, q_ids, g_ids, live, dev)
+    if vals is None:
+        vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
+    if idx is None:
+        idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
+    assert tuple(vals.shape) == (nQ, k) and tuple(idx.shape) == (nQ, k)
+    S = search_slabs(nQ, N, k) if slabs is None else int(slabs)
+    part = torch.empty(nQ, max(S, 1), k, device=dev, dtype=torch.int64)
+    null = ctypes.c_void_p(0)
+    check(lib().sc_search_topk_filtered_bf16(_p(q_split) if nQ else null, _p(g_split) if N else null, nQ, N, K6, k, S,
+                                             _p(q_ids) if nQ and N else null, _p(g_ids) if nQ and N else null, _p(live) if N else null,
+                                             _p(part) if nQ else null, _stream()), "sc_search_topk_filtered_bf16")
+    return search_merge(part, k, vals=vals, idx=idx)
+
+
 def rows_bf16(x: torch.Tensor, row_scale: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
     """x [R, E] fp32 (* row_scale [R]) -> (out [Rp, Ep] bf16, norms [3, R] fp32), Rp / Ep = R / E rounded up to 128 / 64
     (sc_rows_bf16, csrc/search_compact.hip): the rows rounded to bf16 (nearest even), zero outside [R, E], and per row the 2-norms of

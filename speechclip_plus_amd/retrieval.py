@@ -15,7 +15,7 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 import torch
 
 __all__ = ["mutualRetrieval", "GalleryIndex", "search", "mutual_ranks", "recall_from_ranks", "mutual_recall", "CompactGalleryIndex",
-           "search_compact", "compact_eps"]
+           "search_compact", "compact_eps", "hard_negatives"]
 
 
 def _recall(score: torch.Tensor, query_ids: torch.Tensor, cand_ids: torch.Tensor, ks: Sequence[int], cand_title: str) -> Dict[str, float]:
@@ -91,15 +91,24 @@ class GalleryIndex:
     """A gallery [N, E] prepared for ``search``: the side-1 three-way bf16 split of its rows ([roundup(N, 128), 6 Ep] bf16, Ep = E
     rounded up to 64: 12 Ep bytes per gallery row), built in chunks of rows so that no second fp32 copy of a large gallery is made.
     ``cosine=True``: every row is scaled by 1 / max(|g|, 1e-8) on the way in, so the scores against unit (or ``cosine=True``)
-    queries are cosines.  Build once, search with any number of query batches."""
+    queries are cosines.  Build once, search with any number of query batches.
 
-    def __init__(self, gallery: torch.Tensor, cosine: bool = False):
+    ``ids``: int64 [N] ids of the rows (kept as ``index.ids``, a device tensor, or None): ``search(..., query_ids=...)`` then leaves
+    out every row whose id equals the query's.  ``index.live``: None (every row takes part) or a bool [N] device tensor;
+    ``remove(rows)`` / ``restore(rows=None)`` change it in place - the split is never touched, so taking rows out of a built index
+    (a NaN row, a withdrawn item) costs one small copy, and ``search`` skips them.  ``n_live`` counts the rows that take part."""
+
+    def __init__(self, gallery: torch.Tensor, cosine: bool = False, ids: Optional[torch.Tensor] = None):
         if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2:
             raise ValueError("GalleryIndex: gallery must be a [N, E] tensor")
         if not gallery.is_cuda:
             raise RuntimeError("GalleryIndex runs on the HIP kernels: device tensors only")
         self.N, self.E = int(gallery.shape[0]), int(gallery.shape[1])
         assert self.E >= 1, gallery.shape
+        if ids is not None:
+            from . import ops
+            ops.filter_operands("GalleryIndex", self.N, self.N, ids, ids, None, gallery.device, names=("ids", "ids", "live"))
+        self.ids, self.live = ids, None
         self.cosine = bool(cosine)
         self.Ep = -(-self.E // 64) * 64
         self.split = torch.empty(-(-self.N // 128) * 128, 6 * self.Ep, device=gallery.device, dtype=torch.bfloat16)
@@ -114,9 +123,53 @@ class GalleryIndex:
     def __len__(self) -> int:
         return self.N
 
+    def _rows_arg(self, rows) -> torch.Tensor:
+        """row numbers (a tensor or a sequence of ints) -> int64 on the index's device, every one inside [0, N)"""
+        rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= self.N):
+            raise IndexError(f"GalleryIndex: rows outside [0, {self.N})")
+        return rows.to(self.device)
+
+    def remove(self, rows) -> "GalleryIndex":
+        """Take gallery rows ``rows`` out of every later ``search`` (``live[rows] = False``, in place; the split is not touched)."""
+        rows = self._rows_arg(rows)
+        if self.live is None:
+            self.live = torch.ones(self.N, device=self.device, dtype=torch.bool)
+        self.live[rows] = False
+        return self
+
+    def restore(self, rows=None) -> "GalleryIndex":
+        """Put ``rows`` back (None: every row; ``live`` becomes None again, so ``search`` runs exactly as before any ``remove``)."""
+        if rows is None:
+            self.live = None
+        elif self.live is not None:
+            self.live[self._rows_arg(rows)] = True
+        else:
+            self._rows_arg(rows)                                      # nothing is removed; the rows are still checked
+        return self
+
+    @property
+    def n_live(self) -> int:
+        return self.N if self.live is None else int(self.live.sum())
+
+
+def _search_filter(queries: torch.Tensor, gallery, query_ids, gallery_ids, live):
+    """The filter of a ``search`` call, checked before anything is launched (ops.filter_operands): ``gallery_ids`` / ``live`` default
+    to a GalleryIndex's own.  -> (query_ids, gallery_ids, live), all None when the call has no filter."""
+    from . import ops
+    own = isinstance(gallery, GalleryIndex)
+    if gallery_ids is None and query_ids is not None and own:
+        gallery_ids = gallery.ids
+    if live is None and own:
+        live = gallery.live
+    nQ, N = queries.shape[0], (gallery.N if own else gallery.shape[0])
+    return ops.filter_operands("search", nQ, N, query_ids, gallery_ids, live, gallery.device if gallery.device.type == "cuda" else None,
+                               names=("query_ids", "gallery_ids", "live"))
+
 
 def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex, "CompactGalleryIndex"], k: int, cosine: bool = False,
-           slabs: Optional[int] = None, route: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+           slabs: Optional[int] = None, route: Optional[str] = None, *, query_ids: Optional[torch.Tensor] = None,
+           gallery_ids: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """queries [nQ, E], gallery [N, E] (or a GalleryIndex of it) -> (vals [nQ, k] fp32, idx [nQ, k] int64): for every query the k
     gallery rows with the largest inner product, best first, on the device.  ``cosine=True`` scales query and gallery rows by
     1 / max(|x|, 1e-8) first (a GalleryIndex carries its own choice; the flag then applies to the queries).  1 <= k <= 32.
@@ -132,14 +185,30 @@ def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex, "Co
     rows) or "composition" (the same score GEMM into one 128 MiB scratch per chunk of queries + ops.topk_rows; faster on small
     galleries); both give the same lists.  ``slabs``: slabs of the gallery axis of the fused kernel (tests; implies "fused"; the
     result does not depend on it).  A CompactGalleryIndex as ``gallery``: ``search_compact(queries, gallery, k)[:2]`` - the same lists
-    from the bf16 copy, with re-rank scores as ``vals`` (see there)."""
+    from the bf16 copy, with re-rank scores as ``vals`` (see there).
+
+    Filter (csrc/search_filter.hip): gallery row j is ADMISSIBLE for query i iff j < N, ``live`` is absent or live[j] != 0, and ids
+    are absent or gallery_ids[j] != query_ids[i].  ``query_ids`` [nQ] / ``gallery_ids`` [N]: int64, contiguous, on the device, all
+    64 bits compared, negative values legal, both or neither; ``live`` [N]: bool (or uint8).  ``gallery_ids`` / ``live`` default to
+    the GalleryIndex's own ``ids`` / ``live``.  The result is the order above over the admissible rows only: an inadmissible row never
+    appears whatever its score (NaN included), -inf / -1 stand behind the last admissible row, an admissible row has the same fp32
+    bits as without the filter, and one whose score is a real -inf ranks ahead of the fillers.  Both routes run with a filter and
+    ``default_route`` picks as before.  Without ids and without a live mask the call runs exactly the unfiltered code.  A
+    CompactGalleryIndex with any filter is a ValueError: its certificate is stated over all N rows."""
     from . import ops
     if isinstance(gallery, CompactGalleryIndex):      # the compact route (below): exact lists through the certificate and its fallback
+        if query_ids is not None or gallery_ids is not None or live is not None:
+            raise ValueError("search: a CompactGalleryIndex takes no filter - its certificate (no row outside the candidates can belong "
+                             "to the list) would have to be restated over the admissible rows; use a GalleryIndex")
         if route is not None:
             raise ValueError("search: route applies to a GalleryIndex or a tensor, not to a CompactGalleryIndex")
         return search_compact(queries, gallery, k, cosine=cosine, slabs=slabs)[:2]
     if not isinstance(queries, torch.Tensor) or queries.dim() != 2:
         raise ValueError("search: queries must be a [nQ, E] tensor")
+    if query_ids is not None or gallery_ids is not None or live is not None or (isinstance(gallery, GalleryIndex) and gallery.live is not None):
+        if not isinstance(gallery, (torch.Tensor, GalleryIndex)) or (isinstance(gallery, torch.Tensor) and gallery.dim() != 2):
+            raise ValueError("search: gallery must be a [N, E] tensor or a GalleryIndex")
+        query_ids, gallery_ids, live = _search_filter(queries, gallery, query_ids, gallery_ids, live)
     g_cuda = gallery.split.is_cuda if isinstance(gallery, GalleryIndex) else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
     if not queries.is_cuda or not g_cuda:
         raise RuntimeError("search runs on the HIP kernels: device tensors only")
@@ -149,6 +218,8 @@ def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex, "Co
     k = int(k)
     assert 1 <= k <= 32, f"k = {k}: the selection keeps at most 32 gallery rows per query"
     dev = queries.device
+    if query_ids is not None or live is not None:
+        return _search_filtered(queries, index, k, cosine, slabs, route, query_ids, gallery_ids, live)
     vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
     idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
     if route is None:
@@ -176,6 +247,58 @@ def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex, "Co
                 ops.cosine_scores_split(q[r0:r1], rnorm, index.split, index.split.shape[0], out=scores[:rp], split_out=split[:rp])
                 ops.topk_rows(scores[: r1 - r0], index.N, k, vals=vals[r0:r1], idx=idx[r0:r1])
     return vals, idx.long()
+
+
+def _search_filtered(queries: torch.Tensor, index: GalleryIndex, k: int, cosine: bool, slabs: Optional[int], route: Optional[str],
+                     query_ids: Optional[torch.Tensor], gallery_ids: Optional[torch.Tensor], live: Optional[torch.Tensor]):
+    """``search`` with a filter: the same chunking, buffers and score kernels, the selection by csrc/search_filter.hip (a loop of its
+    own, so that the unfiltered one above stays exactly as it was)"""
+    from . import ops
+    nQ, dev = queries.shape[0], queries.device
+    vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
+    if route is None:
+        route = "fused" if slabs is not None else default_route(nQ, index.N)
+    if route not in ("fused", "composition"):
+        raise ValueError(f"search: route = {route!r} (\"fused\" or \"composition\")")
+    if nQ > 0:
+        q = _rows_f32(queries)
+        if route == "composition" and index.N > 0:
+            from .keyword_neighbors import default_chunk_rows
+            chunk = min(default_chunk_rows(index.N), -(-nQ // 128) * 128)
+            scores = torch.empty(chunk, index.split.shape[0], device=dev, dtype=torch.float32)   # the one score scratch of the call
+        else:
+            chunk = min(_INDEX_CHUNK_ROWS, -(-nQ // 128) * 128)
+            scores = None
+        split = torch.empty(chunk, 6 * index.Ep, device=dev, dtype=torch.bfloat16)       # the one query-split buffer of the call
+        for r0 in range(0, nQ, chunk):
+            r1 = min(nQ, r0 + chunk)
+            qi = None if query_ids is None else query_ids[r0:r1]
+            if scores is None:
+                _split_rows(q[r0:r1], 0, cosine, split)
+                ops.search_topk_filtered(split, index.split, r1 - r0, index.N, k, q_ids=qi, g_ids=gallery_ids, live=live, slabs=slabs,
+                                         vals=vals[r0:r1], idx=idx[r0:r1])
+            else:
+                rp = -(-(r1 - r0) // 128) * 128
+                rnorm = ops.vq_prep(q[r0:r1])[1] if cosine else None
+                ops.cosine_scores_split(q[r0:r1], rnorm, index.split, index.split.shape[0], out=scores[:rp], split_out=split[:rp])
+                ops.topk_rows_filtered(scores[: r1 - r0], index.N, k, q_ids=qi, g_ids=gallery_ids, live=live, vals=vals[r0:r1],
+                                       idx=idx[r0:r1])
+    return vals, idx.long()
+
+
+def hard_negatives(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex], a_ids: torch.Tensor, b_ids: Optional[torch.Tensor], k: int,
+                   cosine: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Hard-negative mining: for every anchor A[i] the k highest-scoring rows of B that are WRONG for it - rows j with
+    b_ids[j] != a_ids[i] - as (vals [nA, k] fp32, idx [nA, k] int64), hardest first.  ``a_ids`` [nA] / ``b_ids`` [nB]: int64 device
+    tensors (the ids ``mutual_ranks`` takes to decide what is correct); ``b_ids`` None: the ids of the GalleryIndex ``B``.  This is
+    ``search(A, B, k, cosine, query_ids=a_ids, gallery_ids=b_ids)``: scores, order, ties and tails are ``search``'s, an anchor with
+    fewer than k wrong rows ends in -inf / -1, and a removed row of an index (``live``) is never mined."""
+    if a_ids is None:
+        raise ValueError("hard_negatives: a_ids is required (without ids every row is a negative: that is search)")
+    if b_ids is None and not (isinstance(B, GalleryIndex) and B.ids is not None):
+        raise ValueError("hard_negatives: b_ids is required unless B is a GalleryIndex built with ids=")
+    return search(A, B, k, cosine=cosine, query_ids=a_ids, gallery_ids=b_ids)
 
 
 # ------------------------------------------------------------------------------------------------ compact gallery search
