@@ -195,11 +195,34 @@ uint32_t sc_hash32(uint32_t x);   /* host twin of the kernels' dropout hash (low
  * Bias (gate, table: both or neither; both NULL = the plain kernel, tmax is not read):
  *     softmax(scale q k^T + gate[h][i] table[h][j - i] + kpm(-inf)) v
  *   gate  [H][rows] fp32, rows = B R (uniform) or seg->rows: one value per (head, query row) in the row layout of the call
- *         (sc_wavlm_gate_bf16); pad rows may hold anything finite
+ *         (sc_wavlm_gate_bf16); pad rows may hold any bits ("Reads" below)
  *   table [H][2 tmax - 1] fp32, natural-log units: entry tmax - 1 + (j - i) = the bias of key j seen from query i; tmax >= the
  *         (largest) row pitch, which is limited to 8064 rows (the workgroup's slice of the table sits in LDS)
  *   causal must be 0 (error otherwise).
+ * Reads (what the kernel loads but the mathematics excludes; line numbers are csrc/attention.hip's; tested by
+ * tests/test_gpu_poison.py, docs/parity.md "What a kernel reads and must ignore").  With n = max(1, min(valid_len[b], pitch)) (:112-113):
+ *   rows read as K: whole 64-key tiles (:29, :186-195), i.e. rows 0 .. 64 ceil(n / 64) - 1 of the utterance (:131, :138, :140-141; with
+ *       causal a q-block stops at its own last row, :158-159).  Since the pitch is a multiple of 8 that is up to 56 rows past the
+ *       pitch: they land in the next utterance or, behind the last one, behind the rows of qk.  They must be READABLE; they may hold
+ *       any bits, NaN and Inf included: the scores of keys >= n are overwritten with -inf before anything uses them (:227-233).
+ *   elements read as V^T: the same key range of every d row of [H, 64, pitch] (:130, :132, :139, :142-143), running on into the next d
+ *       row, the next head, the next utterance or, for the last rows of the last utterance, up to 56 elements behind vt.  They must
+ *       be READABLE and FINITE: a masked key's probability is exactly 0 (:260), but its V^T column is still multiplied by it in the
+ *       P.V matrix product (:297-308), and 0 x NaN = 0 x Inf = NaN.  A non-finite value there turns the valid outputs of that
+ *       (utterance, head) into NaN - and through the next layer's V^T those of the utterance in front of it.
+ *   rows read as Q: a wave loads 32 query rows (:110-111, :115-121), so up to row 32 ceil(pitch / 32) - 1 of the utterance, at most 24
+ *       rows past the pitch.  READABLE, any bits: a lane's query is one column of every product, and the lanes past the pitch
+ *       store nothing (:336).
+ *   SC_ATTN_SLACK (64) rows behind the last row of qk and SC_ATTN_SLACK elements behind the last element of vt cover all three;
+ *       the caller provides them (zeroed once: nothing writes them).  R % 64 == 0 in the uniform layout needs none.
+ *   ignored by value: the q and k of pad rows t >= valid_len[b] (any bits), gate on pad rows (read by the pad row's own lane only, the
+ *       index clamped to the last row, :166-167), table offsets outside the head's table (clamped, :168-172), and valid_len itself
+ *       outside [1, pitch] (clamped, :112-113).
+ *   guarantee: out and lse2 of the query rows t < valid_len[b] do not depend on any of the above by value (bit for bit); rows
+ *       t >= valid_len[b] inside the pitch are written (scratch: finite when their q is of ordinary magnitude); nothing is written
+ *       past the pitch (:336).
  * ---------------------------------------------------------------------------------------------- */
+#define SC_ATTN_SLACK 64
 int sc_attn_fwd_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* vt, const int32_t* valid_len, sc_bf16* out, int64_t ldo,
                      const sc_segments* seg, const int32_t* work, int32_t nwork, int32_t B, int32_t R, int32_t H, int32_t D, float scale,
                      const float* gate, const float* table, int32_t tmax, float* lse2, int32_t causal, float drop_p, uint32_t drop_seed,
@@ -878,8 +901,22 @@ int sc_rt_elem(const float* y, int64_t y_slice, int32_t ns, const float* bias, c
  * avssl/module/speech_encoder_plus.py:49-53) on the caller's stream - QKV GEMM (V^T epilogue) -> attention -> out_proj (+bias,
  * dropout, +residual) -> LayerNorm -> FC1 (+bias, GELU) -> FC2 (+bias, dropout, +residual) -> LayerNorm; pre_ln = 1: the
  * HuBERT-large order (LayerNorms in front of the two halves).  x / out: [B*R, D] bf16 in the padded row layout, head_dim 64.
- * Scratch (caller-owned, sc_workspace_bytes(SC_WS_HUBERT_LAYER, B*R, D, F) bytes in total): qk [B*R, 2D], vt [B, H, 64, R],
- * ctx / pre / x1 [B*R, D], ffn [B*R, F], all bf16.  p_attn / p_res = 0 in inference; seeds as in sc_gemm_args / sc_attn_fwd_bf16.
+ * Scratch (caller-owned, six pointers): qk [B*R, 2D], vt [B, H, 64, R], ctx / pre / x1 [B*R, D], ffn [B*R, F], all bf16.  p_attn /
+ * p_res = 0 in inference; seeds as in sc_gemm_args / sc_attn_fwd_bf16.
+ * What lies behind qk and vt (sc_attn_fwd_bf16, "Reads"; the driver hands both to it unchanged, csrc/hubert_layer.cpp:70): SC_ATTN_SLACK
+ *   rows of 2D elements behind qk must be readable (any bits); SC_ATTN_SLACK elements behind vt must be readable and FINITE when the
+ *   attention launch runs, so they must not be part of ctx / pre / x1 / ffn / out (which this call writes, and which may hold
+ *   anything before) - zero them once; no kernel writes them.
+ *   sc_workspace_bytes(SC_WS_HUBERT_LAYER, rows = B*R, D, F) is the size of one allocation that carries both:
+ *       qk [rows + SC_ATTN_SLACK, 2D] | vt [rows * D + SC_ATTN_SLACK] | ctx [rows, D] | pre [rows, D] | x1 [rows, D] | ffn [rows, F]
+ *   = 2 (rows (6D + F) + SC_ATTN_SLACK (2D + 1)) bytes.  (Before this was written down the size was the six buffers back to back: the
+ *   elements behind vt were then the first of ctx, uninitialised in a fresh allocation.)
+ * Content on entry: apart from the finite elements behind vt, every scratch buffer and `out` may hold any bits (NaN included): each is
+ *   written over all rows before it is read (QKV GEMM: qk, vt; attention: every row of ctx inside a pitch; GEMMs / LayerNorms: all rows).
+ * Pad rows of x (t >= valid_len[b] inside a pitch) are scratch, not ignored: they pass through the LayerNorms and all four GEMMs, their
+ *   k is masked and their V^T columns are multiplied by 0.  They must therefore be FINITE and of ordinary magnitude (zeros, or the
+ *   previous layer's output on them): a NaN, an Inf or a value whose V projection overflows bf16 there breaks the valid rows of the
+ *   utterance.  With that, out / ffn / qk on the rows t < valid_len[b] do not depend on the pad rows' values (bit for bit).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     const sc_bf16* x; sc_bf16* out;
@@ -912,7 +949,7 @@ typedef struct {
 } sc_hubert_layer_args;
 int sc_hubert_layer_fwd(const sc_hubert_layer_args* args, void* stream);
 #define SC_WS_INFONCE 0       /* a = Bg */
-#define SC_WS_HUBERT_LAYER 1  /* a = B*R rows, b = D, c = F */
+#define SC_WS_HUBERT_LAYER 1  /* a = B*R rows, b = D, c = F: the six scratch buffers with SC_ATTN_SLACK behind qk and vt (layout above) */
 int64_t sc_workspace_bytes(int32_t what, int64_t a, int64_t b, int64_t c);
 
 /* ------------------------------------------------------------------------------------------------

@@ -19,8 +19,6 @@ Raw images (a list of uint8 [H, W, 3] images of any size, or a packed ragged bat
 resize + centre crop + normalise (ClipModel.prep_image, clip_official.py:153-166) runs on the device (image_prep.py,
 csrc/image_prep.hip) and writes the patch GEMM's operand directly; ``prep_image`` returns the fp32 pixels themselves.
 """
-from types import SimpleNamespace
-
 import torch
 from torch import nn
 
@@ -83,6 +81,7 @@ class ClipImageEncoder(nn.Module):
         self._seed(seed)
         self.requires_grad_(False)
         self._seg_cache = {}
+        self._ws_cache = (None, None)            # ((B, device), the blocks' scratch): one batch size at a time, as the encoder's plans
         if device is not None:
             self.to(device)
 
@@ -225,7 +224,6 @@ class ClipImageEncoder(nn.Module):
     def _encode_patches(self, A: torch.Tensor, B: int, dev):
         """the tower from the patch GEMM's operand A [seg.rows, Kp] bf16 on"""
         from . import ops
-        from ._lib import lib
         W, F = self.width, 4 * self.width
         w = self._weights(dev)
         seg, valid_len = self.segments(B, dev)
@@ -234,13 +232,12 @@ class ClipImageEncoder(nn.Module):
         ops.gemm_raw(A, self.Kp, w["conv1"], self.Kp, G, W, rows, W, self.Kp, out_f32=True)
         X = ops.vit_embed_ln(G, w["cls"], w["pos"], w["ln_pre_g"], w["ln_pre_b"], seg)
         Y = torch.empty_like(X)
-        ws = torch.empty(int(lib().sc_workspace_bytes(1, rows, W, F)) // 2, device=dev, dtype=torch.bfloat16)
-        sizes = {"qk": 2 * W, "vt": W, "ctx": W, "pre": W, "x1": W, "ffn": F}
-        pl, off = {}, 0
-        for name, n in sizes.items():
-            pl[name] = ws[off: off + rows * n].view(rows, n)
-            off += rows * n
-        pl = SimpleNamespace(**pl)
+        # the blocks' scratch, kept for the next batch of the same size: behind qk and vt it carries the zeroed slack that the
+        # attention tiles read past the last image (tokens 50 / 257 at pitch 56 / 264: key tiles of 64 end 8 / 56 keys behind a row)
+        key = (B, str(dev))
+        if self._ws_cache[0] != key:
+            self._ws_cache = (key, ops.hubert_layer_workspace(rows, W, F, dev))
+        pl = self._ws_cache[1]
         for i in range(self.arch["layers"]):
             ops.hubert_layer_fwd(X, Y, valid_len, w, i, pl, B, self.pitch, self.tokens, W, F, self.heads, pre_ln=True, seg=seg, ffn_act=2)
             X, Y = Y, X

@@ -366,9 +366,9 @@ extern "C" int sc_attn_fwd_bf16(const sc_bf16* qk, int64_t ldqk, const sc_bf16* 
         SC_CHECK(seg->B > 0 && seg->B < 65536 && H > 0 && seg->rows > 0 && seg->max_pitch > 0 && seg->max_pitch % SC_SEG_ROWS == 0 && (!work || nwork > 0),
                  "sc_attn_fwd_bf16: B=%d rows=%d max_pitch=%d", seg->B, seg->rows, seg->max_pitch);
     else
-        // R % 128 != 0 (round 4): a last q-block of 32 / 64 / 96 rows; the K / V^T tiles of 64 keys may then read up to 32 rows / 64
-        // elements past an utterance (into the next one, or - behind the last - into slack the caller provides: 64 rows of qk, 64
-        // elements of vt); what they read there is masked
+        // R % 128 != 0 (round 4): a last q-block of fewer rows; the K / V^T tiles of 64 keys may then read up to 56 rows / elements past
+        // an utterance (into the next one, or - behind the last - into slack the caller provides: SC_ATTN_SLACK rows of qk, elements
+        // of vt); what they read there is masked: K may hold any bits, V^T must be finite (speechclip_hip.h, "Reads")
         SC_CHECK(B > 0 && H > 0 && R > 0 && R % 8 == 0, "sc_attn_fwd_bf16: R=%d must be a positive multiple of 8", R);
     SC_CHECK(D == H * 64, "sc_attn_fwd_bf16: head_dim must be 64 (D=%d, H=%d)", D, H);
     // what the kernel takes as R (uniform: the pitch; ragged: the largest one, which sizes the q-block rectangle), and its rows_total /

@@ -32,8 +32,10 @@ extern "C" int64_t sc_workspace_bytes(int32_t what, int64_t a, int64_t b, int64_
     switch (what) {
         case SC_WS_INFONCE:          // a = Bg
             return 4 * sc_infonce_workspace_floats((int32_t)a);
-        case SC_WS_HUBERT_LAYER: {   // a = B * R rows, b = D, c = F: qk [M, 2D] + vt [M, D] + ctx [M, D] + pre [M, D] + x1 [M, D] + ffn [M, F], bf16
-            return 2 * a * (6 * b + c);
+        case SC_WS_HUBERT_LAYER: {   // a = B * R rows, b = D, c = F, bf16: qk [M + S, 2D] + vt [M D + S] + ctx [M, D] + pre [M, D] + x1 [M, D] + ffn [M, F]
+            // S = SC_ATTN_SLACK: the rows behind qk and the elements behind vt that a 64-key attention tile reads past the last
+            // utterance (sc_attn_fwd_bf16, "Reads").  Without them those reads land in vt and in ctx, which the attention launch writes
+            return 2 * (a * (6 * b + c) + SC_ATTN_SLACK * 2 * b + SC_ATTN_SLACK);
         }
         default:
             sc_set_error("sc_workspace_bytes: unknown kind %d", what);

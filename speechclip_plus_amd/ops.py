@@ -251,6 +251,29 @@ def hubert_layer_fwd(x: torch.Tensor, out: torch.Tensor, valid_len: torch.Tensor
     check(L.sc_hubert_layer_fwd(ctypes.byref(a), _stream()), "sc_hubert_layer_fwd", L)
 
 
+ATTN_SLACK = 64     # SC_ATTN_SLACK: rows behind qk / elements behind vt that a 64-key attention tile may read past the last utterance
+
+
+def hubert_layer_workspace(rows: int, D: int, F_: int, device):
+    """The scratch of ``hubert_layer_fwd`` for ``rows`` rows as ONE allocation of sc_workspace_bytes(SC_WS_HUBERT_LAYER) bytes, laid out
+    as the header documents it: qk [rows + 64, 2 D] | vt [rows D + 64] | ctx | pre | x1 [rows, D] | ffn [rows, F].  The 64 rows behind
+    qk and the 64 elements behind vt are what the attention kernel reads past the last utterance: no kernel writes them, they are
+    zeroed here, once (0 x NaN in the P.V product is NaN); everything else is left as the allocator hands it out - the layer writes
+    it before it reads it.  -> namespace(qk, vt, ctx, pre, x1, ffn) of [rows, .] views for the ``pl`` argument."""
+    from types import SimpleNamespace
+    n = int(lib().sc_workspace_bytes(1, rows, D, F_)) // 2
+    ws = torch.empty(n, device=device, dtype=torch.bfloat16)
+    pl, off = {}, 0
+    for name, cols, slack in (("qk", 2 * D, ATTN_SLACK * 2 * D), ("vt", D, ATTN_SLACK), ("ctx", D, 0), ("pre", D, 0), ("x1", D, 0), ("ffn", F_, 0)):
+        pl[name] = ws[off: off + rows * cols].view(rows, cols)
+        off += rows * cols
+        if slack:
+            ws[off: off + slack].zero_()
+            off += slack
+    assert off == n, (off, n)
+    return SimpleNamespace(ws=ws, **pl)
+
+
 def gemm_stats_strips(M: int, N: int) -> int:
     """Row-statistics strips a producer GEMM [M, N] writes (one per N-tile of the width the dispatcher picks)."""
     a = GemmArgs()

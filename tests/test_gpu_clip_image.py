@@ -135,14 +135,16 @@ def test_layer_driver_quickgelu_matches_op_by_op(name, B):
     x = torch.randn(rows, D, generator=g).to(torch.bfloat16).to(dev)
     out = torch.empty_like(x)
     from types import SimpleNamespace
-    pl = SimpleNamespace(qk=torch.empty(rows, 2 * D, device=dev, dtype=torch.bfloat16), vt=torch.empty(rows, D, device=dev, dtype=torch.bfloat16),
+    # qk and vt with the zeroed slack the attention tiles read behind the last image (SC_ATTN_SLACK rows / elements)
+    slack_qk = lambda: torch.zeros(rows + 64, 2 * D, device=dev, dtype=torch.bfloat16)[:rows]
+    slack_vt = lambda: torch.zeros(rows * D + 64, device=dev, dtype=torch.bfloat16)[: rows * D].view(rows, D)
+    pl = SimpleNamespace(qk=slack_qk(), vt=slack_vt(),
                          ctx=torch.empty(rows, D, device=dev, dtype=torch.bfloat16), pre=torch.empty(rows, D, device=dev, dtype=torch.bfloat16),
                          x1=torch.empty(rows, D, device=dev, dtype=torch.bfloat16), ffn=torch.empty(rows, F_, device=dev, dtype=torch.bfloat16))
     ops.hubert_layer_fwd(x, out, vl, w, 0, pl, B, m.pitch, m.tokens, D, F_, H, pre_ln=True, seg=seg, ffn_act=2)
     # the same entry points, one by one
     x1 = ops.layernorm_bf16(x, w["l0_ln1_g"], w["l0_ln1_b"])
-    qk = torch.empty(rows, 2 * D, device=dev, dtype=torch.bfloat16)
-    vt = torch.empty(rows, D, device=dev, dtype=torch.bfloat16)
+    qk, vt = slack_qk(), slack_vt()
     ops.gemm_raw(x1, D, w["l0_qkv_w"], D, qk, 2 * D, rows, 3 * D, D, bias=w["l0_qkv_b"], Ct=vt, n_split=2 * D, R=m.pitch, dh=64, seg=seg)
     ctx = torch.empty(rows, D, device=dev, dtype=torch.bfloat16)
     ops.attn_fwd(qk, vt, vl, ctx, B, m.pitch, H, D, 0.125, seg=seg)
