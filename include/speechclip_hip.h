@@ -95,7 +95,8 @@ typedef struct {
     int32_t nb1, nb2;             /* batch = nb1*nb2 (>= 1 each) */
     int64_t sA1, sA2, sW1, sW2, sC1, sC2, sBias1, sBias2, sR1, sR2;
     int32_t tile;                 /* 0 auto | 1: 128x128 (4 waves) | 2: 256-row tile, 8 waves, width 256 or 192 by wave quantisation
-                                     (7 / 8 force 192 / 256) | 3: 128x64 (13: four LDS stages) | 14 / 15: 64x64 with two / four stages
+                                     (7 / 8 force 192 / 256; with n_split >= 0 the forced width must divide n_split, else an
+                                     error) | 3: 128x64 (13: four LDS stages) | 14 / 15: 64x64 with two / four stages
                                      (few rows, narrow output, long K).  Every tile family accumulates k in the same order and
                                      shares the epilogue arithmetic: results do not depend on the choice.  (32 / 34: diagnostic
                                      kernels of libspeechclip_hip_diag.so only; the product library returns an error) */

@@ -509,6 +509,9 @@ extern "C" int sc_gemm_bf16(const sc_gemm_args* args, void* stream) {
         case 2: case 32: case 34: case 7: case 8:   // 2 = 256-row tile, width (256 / 192) chosen by wave quantisation; 7 / 8 force it
             SC_CHECK(a.n_split < 0 || a.n_split % 192 == 0 || a.n_split % 256 == 0,
                      "sc_gemm_bf16: 256-row tiles need n_split %% 192 == 0 or %% 256 == 0");
+            // a forced width must itself divide n_split: a tile that straddles it would store its transposed columns row-major
+            SC_CHECK(a.n_split < 0 || (tile == 7 ? a.n_split % 192 == 0 : tile == 2 || a.n_split % 256 == 0),
+                     "sc_gemm_bf16: tile=%d forces a %d-wide tile, which n_split=%d is no multiple of", tile, tile == 7 ? 192 : 256, a.n_split);
             return sc_gemm256_launch(a, s);
         case 3: case 13: {
             SC_CHECK(a.n_split < 0, "sc_gemm_bf16: 128x64 tile has no transposed store");
