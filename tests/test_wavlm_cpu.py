@@ -110,6 +110,117 @@ def test_not_built_switches_raise(monkeypatch):
         se.S3prlSpeechEncoderPlus("wav2vec2", device="cpu")
 
 
+# ------------------------------------------------------------------- rehearsal of tests/test_gpu_wavlm_stages.py's criteria
+# H = 12, pitches 152 / 72 / 136 / 8, valid 150 / 65 / 127 / 5 (base_small, segment rows).  The kernel is stood in for by
+# attn_cases.emulate_fwd_bias (its arithmetic order in torch fp32) on random bf16 operands with a gate from gate_ref in fp32 and a real
+# bucket table: the reference alone has to stay inside the bound of docs/parity.md ("Attention on peaked and drifting scores", BIAS),
+# and every wrong reference the GPU module plants has to be rejected by the element-wise criterion alone.
+_REHEARSAL = {}
+
+
+def _rehearsal(H=wc.STAGE_H):
+    """operands, the fp32 gates of both layers' parameters on the same rows, the emulation's output and the fp64 reference per
+    utterance (layer 1's parameters are the right ones): computed once, left unchanged"""
+    if H not in _REHEARSAL:
+        c = wc.rehearsal_operands(H=H)
+        c["gates"] = [wc.gate_ref(c["x"].float(), *p, H) for p in c["gate_params"]]
+        c["gates64"] = [wc.gate_ref(c["x"].double(), *p, H) for p in c["gate_params"]]
+        c["emu"] = [wc.emulate_segment(c, c["gates"][1], b, v) for b, v in enumerate(wc.STAGE_VALID)]
+        c["ref"] = [wc.segment_attention_ref(c["qk"], c["vt"], c["gates"][1], c["table"], c["r0"][b], c["pitch"][b], v, H, 0.125)
+                    for b, v in enumerate(wc.STAGE_VALID)]
+        _REHEARSAL[H] = c
+    return _REHEARSAL[H]
+
+
+def _share_rejected(c, gate=None, table=None):
+    """share of the valid query rows of the four utterances that the element-wise criterion rejects when the reference is built from
+    ``gate`` / ``table`` instead of the right ones, and the largest error / bound"""
+    H = c["H"]
+    rej = tot = 0
+    worst = 0.0
+    for b, v in enumerate(wc.STAGE_VALID):
+        f = wc.segment_attention_ref(c["qk"], c["vt"], c["gates"][1] if gate is None else gate, c["table"] if table is None else table,
+                                     c["r0"][b], c["pitch"][b], v, H, 0.125)
+        rej += int(wc.rows_rejected(c["emu"][b], f["out"], f["bound"])[:v].sum())
+        tot += v
+        worst = max(worst, float(((c["emu"][b].double() - f["out"]).abs() / f["bound"]).max()))
+    return rej / tot, worst
+
+
+def test_rehearsal_unpacking_round_trip():
+    c = _rehearsal()
+    g = torch.Generator().manual_seed(1)
+    v = torch.randn(c["M"], c["D"], generator=g).to(torch.bfloat16)
+    vt = wc.pack_vt(v, c["r0"], c["pitch"], c["H"], slack=64)
+    assert vt.numel() == c["D"] * (c["M"] + 64) and not bool(vt[c["D"] * c["M"]:].any())
+    for r0, p in zip(c["r0"], c["pitch"]):
+        assert torch.equal(wc.rows_of(wc.vt_segment(vt, r0, p, c["H"])), v[r0: r0 + p])
+    assert torch.equal(wc.rows_of(wc.heads_of(v[:8], c["H"])), v[:8])
+    assert c["table"].shape == (12, 2 * wc.STAGE_R - 1) and sum(wc.STAGE_PITCH) == c["M"] == 368
+    # the shifted table holds the embedding of offset d + 1 where the right one holds offset d's
+    sh = wc.table_shifted(c["rel"], wc.STAGE_R)
+    assert sh.shape == c["table"].shape and torch.equal(sh[:, :-1], c["table"][:, 1:]) and not torch.equal(sh, c["table"])
+
+
+def test_rehearsal_emulation_stays_within_the_bound():
+    c = _rehearsal()
+    for b, v in enumerate(wc.STAGE_VALID):
+        f, got = c["ref"][b], c["emu"][b].double()
+        ratio = float(((got - f["out"]).abs() / f["bound"]).max())
+        e = wc.rel_l2(got, f["out"])
+        print(f"WAVLM|rehearsal b={b} pitch={c['pitch'][b]} valid={v}|max error / bound {ratio:.3f}|rel-L2 {e:.3e}")
+        assert got.shape == (12, c["pitch"][b], 64) and bool((got != f["out"]).any())
+        assert ratio <= 1.0 and e <= 1e-2
+    assert float(c["gates"][1].min()) > 0.9 and float(c["gates"][1].max()) < 3.1
+
+
+def test_rehearsal_rejects_wrong_gate_parameters_and_tables():
+    """layer 0's gate parameters on layer 1's rows, the table one offset off, heads 0 and 1 of the table exchanged (H = 12 and 16):
+    the majority of the valid query rows is rejected, not one element"""
+    c = _rehearsal()
+    ok, worst = _share_rejected(c)
+    assert ok == 0.0 and worst <= 1.0
+    planted = [("gate of layer 0's parameters", c, dict(gate=c["gates64"][0])),
+               ("table shifted by one offset", c, dict(table=wc.table_shifted(c["rel"], c["R"]))),
+               ("table heads 0 / 1 exchanged, H = 12", c, dict(table=wc.table_heads_swapped(c["table"])))]
+    c16 = _rehearsal(16)
+    assert _share_rejected(c16)[0] == 0.0
+    planted.append(("table heads 0 / 1 exchanged, H = 16", c16, dict(table=wc.table_heads_swapped(c16["table"]))))
+    for tag, cc, kw in planted:
+        share, worst = _share_rejected(cc, **kw)
+        print(f"WAVLM|rehearsal sensitivity|{tag}|rows rejected {share:.3f}|max error / bound {worst:.3g}")
+        assert share > 0.5, (tag, share)
+
+
+def test_rehearsal_rejects_a_removed_key():
+    c = _rehearsal()
+    b, v, q = 0, wc.STAGE_VALID[0], 140
+    f = c["ref"][b]
+    key = wc.likeliest_key(f, q, 128, v)                  # the last key tile of 150 valid keys
+    g = wc.segment_attention_ref(c["qk"], c["vt"], c["gates"][1], c["table"], c["r0"][b], c["pitch"][b], v, c["H"], 0.125, drop_key=key)
+    assert torch.equal(g["out"][:, :q], f["out"][:, :q]) and not torch.equal(g["out"][key[0], q], f["out"][key[0], q])
+    rej = wc.rows_rejected(c["emu"][b], g["out"], g["bound"])
+    ratio = float(((c["emu"][b].double() - g["out"]).abs() / g["bound"])[key[0], q].max())
+    print(f"WAVLM|rehearsal sensitivity|key {key[2]} (p = {float(f['P'][key]):.3f}) removed from query {q} head {key[0]}|error / bound {ratio:.3g}")
+    assert bool(rej[q]) and int(rej.sum()) == 1
+
+
+def test_rehearsal_gate_criterion_rejects_the_wrong_rows():
+    """the gate taken from x where the encoder takes it from LayerNorm(x) (wavlm_large): test_gate_kernel's criterion sees it, and
+    passes the fp32 evaluation of the right rows"""
+    c = _rehearsal()
+    p = c["gate_params"][0]
+    g = torch.Generator().manual_seed(9)
+    hidden = (c["x"].float() * (2.0 + 0.5 * torch.randn(c["D"], generator=g)) + 0.3 * torch.randn(c["D"], generator=g)).to(torch.bfloat16)
+    ln = torch.nn.functional.layer_norm(hidden.float(), (c["D"],)).to(torch.bfloat16)
+    got = wc.gate_ref(ln.float(), *p, c["H"]) * (1.0 + 2.0 ** -23)             # a stand-in kernel: fp32, one rounding off
+    right, yard = wc.gate_ref(ln.double(), *p, c["H"]), wc.gate_ref(ln.float(), *p, c["H"])
+    assert not wc.gate_criterion_rejects(got, right, yard)[0]
+    wrong, wyard = wc.gate_ref(hidden.double(), *p, c["H"]), wc.gate_ref(hidden.float(), *p, c["H"])
+    bad, lines = wc.gate_criterion_rejects(got, wrong, wyard)
+    assert bad, lines
+
+
 @pytest.mark.parametrize("typ", ["s3prl_plus", "FairseqHubert"])
 def test_model_builds_from_a_wavlm_config(typ):
     cfg = base_parallel_config()

@@ -1,4 +1,4 @@
-"""References for the WavLM tests (tests/test_wavlm_cpu.py, tests/test_gpu_wavlm.py): one function per quantity, generic in dtype -
+"""References for the WavLM tests (tests/test_wavlm_cpu.py, tests/test_gpu_wavlm.py, tests/test_gpu_wavlm_stages.py): one function per quantity, generic in dtype -
 the fp64 call is the reference, the fp32 call the yardstick.  Shared stages (conv extractor, padding mask, length rules) come from
 ``oracle``; what WavLM adds to HuBERT - the bucket table, the gate, the biased softmax, the encoder with them - is restated here
 from microsoft/unilm wavlm/modules.py ``MultiheadAttention`` and transformers ``WavLMAttention`` (the two agree formula by formula).
@@ -161,3 +161,111 @@ def wavlm_forward(W, arch: HubertArch, wavs, dtype=torch.float64, zero_bias: boo
 def rel_l2(got, ref):
     got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
     return float((got - ref).norm() / (ref.norm() + 1e-300))
+
+
+# ------------------------------------------------------------------------------------ the product's attention call, segment rows
+# What tests/test_gpu_wavlm_stages.py records of one ``attn_fwd`` call of the frozen encoder - qk [M, 2 D] bf16 rows, the flat V^T
+# buffer (per utterance [H, 64, pitch] back to back at D * row0), gate [H, M] fp32, table [H, 2 R - 1] fp32 - turned into
+# attn_cases.fwd_ref calls, one per utterance over its pitch.  Device-agnostic: everything is taken to the CPU in fp64.
+STAGE_H, STAGE_PITCH, STAGE_VALID, STAGE_R = 12, (152, 72, 136, 8), (150, 65, 127, 5), 200   # base_small: R of the plan's 64000-sample bucket
+
+
+def heads_of(x, H):
+    """[P, H * 64] -> [H, P, 64]"""
+    return x.reshape(x.shape[0], H, 64).transpose(0, 1)
+
+
+def rows_of(x):
+    """[H, P, 64] -> [P, H * 64]"""
+    return x.transpose(0, 1).reshape(x.shape[1], -1)
+
+
+def vt_segment(vt, r0, pitch, H):
+    """utterance at row ``r0`` of the flat V^T buffer -> v [H, pitch, 64]"""
+    D = H * 64
+    return vt.reshape(-1)[D * r0: D * (r0 + pitch)].view(H, 64, pitch).transpose(1, 2)
+
+
+def pack_vt(v_rows, r0s, pitches, H, slack=0):
+    """the inverse (the QKV GEMM's store): v rows [M, H * 64] -> the flat buffer, ``slack`` rows of zeros behind"""
+    D = H * 64
+    out = torch.zeros(D * (v_rows.shape[0] + slack), dtype=v_rows.dtype)
+    for r0, p in zip(r0s, pitches):
+        out[D * r0: D * (r0 + p)] = v_rows[r0: r0 + p].view(p, H, 64).permute(1, 2, 0).reshape(-1)
+    return out
+
+
+def segment_attention_ref(qk, vt, gate, table, r0, pitch, valid, H, scale, drop=None, drop_key=None):
+    """attn_cases.fwd_ref of the utterance at rows r0 .. r0 + pitch: keys < valid, bias = gate[h, i] table[h, Tmax - 1 + j - i], fp64.
+    ``drop`` = (rows of the batch, largest pitch, seed, p): the probability dropout rebuilt from the segment layout's element index;
+    ``drop_key`` = (h, query, key) removed from that query's softmax.  -> fwd_ref's dict (out / bound [H, pitch, 64])"""
+    import attn_cases as ac
+    D = H * 64
+    cpu64 = lambda t: t.detach().double().cpu()
+    rows = cpu64(qk[r0: r0 + pitch])
+    q, k = heads_of(rows[:, :D], H), heads_of(rows[:, D: 2 * D], H)
+    v = cpu64(vt_segment(vt, r0, pitch, H))
+    bias = ac.bias_matrix(cpu64(gate[:, r0: r0 + pitch]), cpu64(table), pitch)
+    mult = None
+    if drop is not None:
+        rows_total, max_pitch, seed, p = drop
+        mult = ac.drop_mult(ac.drop_index_segment(r0, pitch, rows_total, max_pitch, nh=H), seed, p)[0]
+    return ac.fwd_ref(q, k, v, ac.key_mask(pitch, valid)[None], scale, bias=bias, mult=mult, drop_key=drop_key)
+
+
+def rows_rejected(got, ref, bound):
+    """[H, P, 64] each -> [P] bool: the query rows with an element outside its bound (the element-wise criterion alone)"""
+    d = (got.detach().double().cpu() - ref).abs()
+    return (~(d <= bound)).any(2).any(0)
+
+
+def table_shifted(rel_embed, R):
+    """the table read one offset off: entry R - 1 + d holds the embedding of offset d + 1 (j - i + 1)"""
+    return bias_table(rel_embed, R + 1)[:, 2:].contiguous()
+
+
+def table_heads_swapped(table, a=0, b=1):
+    t = table.clone()
+    t[a], t[b] = table[b], table[a]
+    return t
+
+
+def likeliest_key(f, query, lo, hi):
+    """(h, query, key): the key in lo .. hi - 1 and the head whose reference probability for ``query`` is largest - removing a key
+    moves the output by about its probability, and only a key that carries some is a fair planted error"""
+    p = f["P"][:, query, lo:hi]
+    h, j = divmod(int(p.argmax()), hi - lo)
+    return h, query, lo + j
+
+
+def gate_criterion_rejects(got, ref, yard):
+    """test_gate_kernel's criterion (head_cases.Report.yard: every element within 4 x the fp32 evaluation's worst) -> (rejected, lines)"""
+    import head_cases as hc
+    rep = hc.Report()
+    rep.yard("sensitivity", "gate", got, ref, yard, dims=())
+    return bool(rep.bad), rep.lines
+
+
+def rehearsal_operands(H=STAGE_H, pitches=STAGE_PITCH, R=STAGE_R, seed=0):
+    """Random operands in the recorded call's form, for the CPU rehearsal: LayerNorm-like bf16 rows x [M, D], qk [M + 64, 2 D] and the
+    packed V^T of N(0, 1) bf16 values, two layers' gate parameters as random_wavlm_state_dict draws them, a real bucket table"""
+    g = torch.Generator().manual_seed(4100 + 7 * H + seed)
+    D, M = H * 64, sum(pitches)
+    r0s = [sum(pitches[:b]) for b in range(len(pitches))]
+    x = torch.randn(M, D, generator=g).to(torch.bfloat16)
+    qk = torch.zeros(M + 64, 2 * D, dtype=torch.bfloat16)
+    qk[:M] = torch.randn(M, 2 * D, generator=g).to(torch.bfloat16)
+    vt = pack_vt(torch.randn(M, D, generator=g).to(torch.bfloat16), r0s, pitches, H, slack=64)
+    gp = [(torch.randn(8, 64, generator=g) * 0.125, torch.randn(8, generator=g) * 0.1, 1.0 + 0.3 * torch.randn(H, generator=g)) for _ in range(2)]
+    rel = torch.randn(NUM_BUCKETS, H, generator=g)
+    return {"H": H, "D": D, "M": M, "r0": r0s, "pitch": list(pitches), "x": x, "qk": qk, "vt": vt, "gate_params": gp, "rel": rel,
+            "table": bias_table(rel, R), "R": R}
+
+
+def emulate_segment(c, gate, b, valid):
+    """attn_cases.emulate_fwd_bias (the kernel's arithmetic order in torch fp32) on utterance b of rehearsal_operands -> [H, pitch, 64] bf16"""
+    import attn_cases as ac
+    H, D, r0, P = c["H"], c["D"], c["r0"][b], c["pitch"][b]
+    rows = c["qk"][r0: r0 + P]
+    return ac.emulate_fwd_bias(heads_of(rows[:, :D], H), heads_of(rows[:, D:], H), vt_segment(c["vt"], r0, P, H),
+                               ac.key_mask(P, valid)[None], gate[:, r0: r0 + P], c["table"])[0]
