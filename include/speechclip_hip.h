@@ -244,6 +244,35 @@ int sc_wavlm_gate_bf16(const sc_bf16* x, int64_t ldx, const float* wg, const flo
  *   qT, kT, doT        : per-head transposed copies [B, H, 64, R] (sc_head_transpose_bf16)
  *   delta              : [B, H, R] fp32 workspace (rowsum(dout . out), written here)
  *   query rows t >= q_rows must carry dout = 0; keys t >= valid_len[b] (and t' > t when causal) get zero gradient
+ * Reads (what the kernels load but the mathematics excludes; line numbers are csrc/attention_bwd.hip's; tested by
+ * tests/test_gpu_poison_bwd.py, docs/parity.md "What a kernel reads and must ignore", "Backward").  n = max(1, min(valid_len[b], R))
+ * (:91, :252), up32 / up64 / up128 = rounded up to a multiple.  Nothing outside the B*R rows of an operand is read: R % 128 == 0
+ * (:523) makes every tile whole - the dq kernel loads 64-key tiles of K, V, K^T up to key up64(n) - 1 (:138-159) and its own 128
+ * query rows (:89-107), the dk/dv kernel its own 128 keys (:251-275) and 64-row tiles of q, dout, q^T, dout^T, lse2, delta up to row
+ * up64(q_rows) - 1 (:288-311), the preparation every row (:416-433, :465-503).
+ *   keys n <= t < up32(n) (the last partly valid 32-key block):
+ *       K any bits: a masked key is one row of S^T (:170) / one column of S (:335), replaced by a select (:189-190, :375, :390).
+ *       V FINITE AND OF ORDINARY MAGNITUDE: dP = V . dO of the masked key is a sum (:171, :336) that is then multiplied by P = 0 (:191,
+ *         :392); a NaN, an Inf or an overflowing sum there makes dq of the utterance's valid rows and dk of the masked key NaN.
+ *       K^T columns FINITE: multiplied by dS = 0 in dQ^T += K^T dS^T (:201-202).  sc_attn_bwd_fused_bf16 makes K^T from K, so there K
+ *         of these keys must be finite as well.
+ *   keys up32(n) <= t < up128(n) (later blocks of a partly valid 128-key block): the dq kernel skips them (:164; K, V, K^T of the rest
+ *       of a 64-key tile are loaded, never multiplied: any bits).  The dk/dv kernel has no early exit per wave: K any bits (:390), V
+ *       FINITE AND OF ORDINARY MAGNITUDE (:336, :392) - otherwise dk of these keys is NaN instead of 0 (valid rows do not notice).
+ *   keys t >= up128(n) (wholly padded 128-key blocks): never loaded by the dq kernel; the dk/dv workgroup stores zeros and returns
+ *       (:261-265).  K, V, K^T any bits.
+ *   query rows n <= t < up32(q_rows) (pad queries of a shorter utterance below q_rows, and the rest of the 32-row block q_rows falls
+ *       in): the dk/dv kernel forms P = exp2(s c - lse2) for them (:374, :389) and multiplies it by dout^T = 0 (:404) and dS = P (0 - 0)
+ *       by q^T (:406); the dq kernel computes their own dq the same way (:190-207).  So: q FINITE AND OF ORDINARY MAGNITUDE, lse2 THE
+ *       FORWARD'S OWN VALUE for that q (then P <= 1), out FINITE (delta = sum 0 x out, :428, :485), dout and the dout^T columns EXACTLY
+ *       ZERO, q^T columns FINITE.
+ *   query rows t >= up32(q_rows): the dk/dv kernel loads them with the 64-row tile and never multiplies them (:328); the dq kernel uses
+ *       a row for that row's own dq only.  No gradient of another row depends on them (any bits, dout included); their own dq is zero
+ *       under the conditions of the line above.
+ *   delta, and qT / kT / doT of sc_attn_bwd_fused_bf16: written over all B*H*R entries / all rows before they are read; any bits on entry.
+ * Guarantee, under these classes: dq of the rows t < valid_len[b] and dk / dv of the keys t < valid_len[b] do not depend on the
+ * excluded regions by value (bit for bit); dk / dv of the keys t >= valid_len[b] are exactly zero; dq of every row with dout = 0 is
+ * exactly zero.  The row-reducing weight-gradient kernels behind this call sum dq / dk / dv over ALL B*R rows, and rely on it.
  * sc_head_transpose_bf16: xT[b, h, d, t] = x[b*R + t, h*64 + d]
  * ---------------------------------------------------------------------------------------------- */
 int sc_attn_bwd_bf16(const sc_bf16* q, int64_t ldq, const sc_bf16* k, int64_t ldk, const sc_bf16* v, int64_t ldv,
@@ -266,7 +295,10 @@ int sc_head_transpose_bf16(const sc_bf16* x, int64_t ldx, sc_bf16* xT, int32_t B
  *   qkv  [nseq * 32, ld >= 3 heads 64] bf16 rows, Q | K | V side by side, head h at columns h*64.. of each third
  *   forward   out[nseq * 32, heads 64] = softmax(scale Q K^T | key <= query) V
  *   backward  dqkv (laid out like qkv) from qkv and dout alone: the probabilities are recomputed, delta = sum_k P dP in fp32
- * Rows behind a prompt are ordinary causal rows (finite values; zero gradient iff their dout rows are zero). */
+ * Rows behind a prompt are ordinary causal rows (finite values; zero gradient iff their dout rows are zero).  Backward: with dout = 0
+ * there, their q / k / v must be finite and of ordinary magnitude (P of the row is recomputed and multiplied by 0, dP = V . dout is a
+ * sum multiplied by P = 0); dqkv of the prompt rows then does not depend on them and dqkv behind the prompt is exactly zero
+ * (tests/test_gpu_poison_bwd.py). */
 int sc_attn32_fwd_bf16(const sc_bf16* qkv, int64_t ld, sc_bf16* out, int64_t ldo, int32_t nseq, int32_t heads, float scale, void* stream);
 int sc_attn32_bwd_bf16(const sc_bf16* qkv, int64_t ld, const sc_bf16* dout, int64_t ldd, sc_bf16* dqkv, int64_t ldg, int32_t nseq,
                        int32_t heads, float scale, void* stream);

@@ -1,5 +1,6 @@
-"""Helpers of tests/test_gpu_poison.py (not collected on their own; pure torch, no device code): the bit patterns, the layouts and the
-masks of the places a kernel READS but the mathematics EXCLUDES (docs/parity.md, "What a kernel reads and must ignore").
+"""Helpers of tests/test_gpu_poison.py and tests/test_gpu_poison_bwd.py (not collected on their own; pure torch, no device code): the bit
+patterns, the layouts and the masks of the places a kernel READS but the mathematics EXCLUDES (docs/parity.md, "What a kernel reads
+and must ignore"; the backward's regions and cases are at the end of the file).
 
 For sc_attn_fwd_bf16 both row layouts share one addressing: utterance b owns ``pitch[b]`` rows at ``row0[b]`` of ``qk`` and the
 per-utterance ``[H, 64, pitch[b]]`` block at element ``D * row0[b]`` of the flat ``vt`` (uniform rows: every pitch = R).  A layout here
@@ -222,3 +223,117 @@ def poisoned_empty():
         yield
     finally:
         torch.empty, torch.empty_like, torch.Tensor.new_empty = orig
+
+
+# ================================================================================================================== backward: regions
+# sc_attn_bwd_bf16 / sc_attn_bwd_fused_bf16 (csrc/attention_bwd.hip), uniform rows, R % 128 == 0.  A row t of utterance b is a KEY of
+# one of four regions and a QUERY of one of four (docs/parity.md, "Backward"); n = valid_len[b], up = ceil to a multiple:
+#   keys      valid [0, n) | tail32 [n, up32(n)) | tail128 [up32(n), up128(n)) | padded [up128(n), R)
+#   queries   valid [0, n) | q_pad  [n, q_rows)  | q_blk   [q_rows, up32(q_rows)) | q_far [up32(q_rows), R)
+BWD_KEY_REGIONS = ("valid", "tail32", "tail128", "padded")
+BWD_QUERY_REGIONS = ("valid", "q_pad", "q_blk", "q_far")
+# name -> (R, lens, q_rows): the smallest geometries that reach every branch (tests/test_gpu_poison_bwd.py names them)
+BWD_GEOMETRIES = {"R=128": (128, [128, 1, 37], 128), "R=256": (256, [200, 129, 65], 200)}
+BWD_INSTANCES = ("plain", "drop", "causal")
+BWD_ENTRIES = ("fused", "unfused")
+ORDINARY = 64.0                                              # the N(0, 64^2) scratch of test_layer_driver_ignores_pad_rows_and_workspace_content
+
+
+def _up(n, m):
+    return (n + m - 1) // m * m
+
+
+def bwd_layout(R, lens, q_rows, H=H_ATT):
+    """-> SimpleNamespace: B, R, lens, q_rows, H, D, rows = B R and one boolean [rows] mask per region name (``key`` / ``query``
+    dicts); ``valid`` is the same mask in both"""
+    lens = [int(n) for n in lens]
+    assert R % 128 == 0 and all(1 <= n <= R for n in lens) and max(lens) <= q_rows <= R
+    B = len(lens)
+    t = torch.arange(R)
+    key = {n: torch.zeros(B, R, dtype=torch.bool) for n in BWD_KEY_REGIONS}
+    query = {n: torch.zeros(B, R, dtype=torch.bool) for n in BWD_QUERY_REGIONS}
+    for b, n in enumerate(lens):
+        key["valid"][b] = t < n
+        key["tail32"][b] = (t >= n) & (t < _up(n, 32))
+        key["tail128"][b] = (t >= _up(n, 32)) & (t < _up(n, 128))
+        key["padded"][b] = t >= _up(n, 128)
+        query["valid"][b] = t < n
+        query["q_pad"][b] = (t >= n) & (t < q_rows)
+        query["q_blk"][b] = (t >= max(n, q_rows)) & (t < _up(q_rows, 32))
+        query["q_far"][b] = t >= _up(q_rows, 32)
+    flat = lambda d: {n: m.reshape(-1) for n, m in d.items()}
+    return SimpleNamespace(B=B, R=R, lens=lens, q_rows=q_rows, H=H, D=64 * H, rows=B * R, key=flat(key), query=flat(query),
+                           valid=key["valid"].reshape(-1))
+
+
+def bwd_case_layout(name):
+    return bwd_layout(*BWD_GEOMETRIES[name])
+
+
+def row_mask(rows_mask, cols):
+    """[rows] -> [rows, cols]"""
+    return rows_mask[:, None].expand(-1, cols).contiguous()
+
+
+def col_mask_T(lay, rows_mask):
+    """[B R] -> [B, H, 64, R]: the columns of a per-head transposed copy (sc_head_transpose_bf16) that hold those rows"""
+    return rows_mask.view(lay.B, 1, 1, lay.R).expand(lay.B, lay.H, 64, lay.R).contiguous()
+
+
+def stat_mask(lay, rows_mask):
+    """[B R] -> [B, H, R]: lse2 / delta of those rows"""
+    return rows_mask.view(lay.B, 1, lay.R).expand(lay.B, lay.H, lay.R).contiguous()
+
+
+def head_transpose(x, lay):
+    """host form of sc_head_transpose_bf16: [B R, H 64] -> [B, H, 64, R]"""
+    return x.view(lay.B, lay.R, lay.H, 64).permute(0, 2, 3, 1).contiguous()
+
+
+def bwd_operands(lay, seed):
+    """seeded N(0, 1) q / k / v / dout [B R, D] bf16 on the valid rows, exact zeros elsewhere, and ``scratch`` [B R, D] bf16 ~ N(0, 64^2)
+    (what a region of class "finite and of ordinary magnitude" is given)"""
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for n in ("q", "k", "v", "dout"):
+        t = torch.zeros(lay.rows, lay.D)
+        t[lay.valid] = torch.randn(int(lay.valid.sum()), lay.D, generator=g)
+        out[n] = t.to(torch.bfloat16)
+    out["scratch"] = (ORDINARY * torch.randn(lay.rows, lay.D, generator=g)).to(torch.bfloat16)
+    return out
+
+
+def put(t, mask, src):
+    """a copy of ``t`` with the elements of ``src`` under ``mask`` (same shapes)"""
+    t = t.clone()
+    t[mask] = src[mask]
+    return t
+
+
+def bwd_read_extent(lay):
+    """The largest row of an utterance that csrc/attention_bwd.hip touches, per kernel -> dict (all must be < R; R % 128 == 0 is what
+    makes it so, attention_bwd.hip:523):
+      dq_query   every row of the utterance: R - 1 (:89-107, no use of q_rows)
+      dq_key     whole 64-key tiles of K, V and K^T up to 64 ceil(n / 64) - 1 (:138-159)
+      dkv_key    the 128 keys of every workgroup: R - 1 (:251-275)
+      dkv_query  whole 64-row tiles of q, dout, q^T, dout^T, lse2, delta up to 64 ceil(q_rows / 64) - 1 (:288-311)
+      prep       the transposes and delta: every row, R - 1 (:416-433, :465-503)"""
+    n = max(max(1, min(v, lay.R)) for v in lay.lens)
+    return {"dq_query": lay.R - 1, "dq_key": _up(n, 64) - 1, "dkv_key": lay.R - 1, "dkv_query": _up(lay.q_rows, 64) - 1, "prep": lay.R - 1}
+
+
+# ================================================================================================================== backward: row reducers
+REDUCER_LENS = [128, 1, 37]                                  # rows = 3 x 128, valid rows per block of 128
+REDUCER_PITCH = 128
+REDUCERS = ("wgrad_tn", "wgrad_transposing", "wgrad_list", "colsum", "ln_acc", "ln_acc_drop_sum", "ln_dres", "posconv_wgrad", "wsum_seg")
+SHORT_PROMPTS = [32, 1, 17]                                  # sc_attn32_bwd_bf16: prompt rows of the three 32-row sequences
+
+
+def reducer_valid(pitch=REDUCER_PITCH, lens=REDUCER_LENS):
+    """[len(lens) pitch] bool: rows t < len of every block"""
+    t = torch.arange(pitch)
+    return torch.cat([t < n for n in lens])
+
+
+def short_valid(prompts=SHORT_PROMPTS):
+    return reducer_valid(32, prompts)

@@ -131,3 +131,90 @@ def test_poisoned_empty_restores_when_the_body_raises():
             assert bool(torch.isnan(torch.empty(1)).all())
         assert bool(torch.isnan(torch.empty(1)).all())
     assert (torch.empty, torch.empty_like, torch.Tensor.new_empty) == orig
+
+
+# ================================================================================================================== backward (tests/test_gpu_poison_bwd.py)
+def _bwd_reference(lay, o, causal):
+    """attn_cases.bwd_ref per utterance on q / k / v / dout cut to the valid rows and keys"""
+    outs = []
+    for b, n in enumerate(lay.lens):
+        q, k, v, d = (_heads(o[name][b * lay.R: b * lay.R + n], lay.H) for name in ("q", "k", "v", "dout"))
+        r = ac.bwd_ref(q, k, v, d, ac.key_mask(n, n, causal)[None].expand(lay.H, -1, -1))
+        outs += [r["dq"], r["dk"], r["dv"]]
+    return outs
+
+
+@pytest.mark.parametrize("name", list(pc.BWD_GEOMETRIES))
+def test_backward_regions_partition_the_rows(name):
+    lay = pc.bwd_case_layout(name)
+    for regions, names in ((lay.key, pc.BWD_KEY_REGIONS), (lay.query, pc.BWD_QUERY_REGIONS)):
+        assert tuple(regions) == names
+        count = sum(m.long() for m in regions.values())
+        assert bool((count == 1).all()), "every row lies in exactly one region"
+        assert torch.equal(regions["valid"], lay.valid) and int(lay.valid.sum()) == sum(lay.lens)
+    size = lambda d: {n: int(m.sum()) for n, m in d.items()}
+    if name == "R=128":             # 37: 5 valid + 27 masked keys in one 32-key block, the next one skipped; 1: the single-key utterance
+        assert size(lay.key) == {"valid": 166, "tail32": 0 + 31 + 27, "tail128": 0 + 96 + 64, "padded": 0}
+        assert size(lay.query) == {"valid": 166, "q_pad": 0 + 127 + 91, "q_blk": 0, "q_far": 0}
+    else:                           # 129: one valid key in the second 128-key block; 65: that block wholly padded; q_rows = 200 < 224 < R
+        assert size(lay.key) == {"valid": 394, "tail32": 24 + 31 + 31, "tail128": 32 + 96 + 32, "padded": 0 + 0 + 128}
+        assert size(lay.query) == {"valid": 394, "q_pad": 0 + 71 + 135, "q_blk": 3 * 24, "q_far": 3 * 32}
+        assert all(int(m.sum()) > 0 for m in list(lay.key.values()) + list(lay.query.values())), "this geometry reaches every region"
+    # the transposed copies' column masks mark the same rows
+    m = lay.key["tail32"]
+    assert bool(((pc.head_transpose(pc.row_mask(m, lay.D).to(torch.bfloat16), lay) != 0) == pc.col_mask_T(lay, m)).all())
+    assert int(pc.stat_mask(lay, m).sum()) == lay.H * int(m.sum())
+
+
+@pytest.mark.parametrize("causal", [0, 1])
+@pytest.mark.parametrize("name", list(pc.BWD_GEOMETRIES))
+def test_backward_masks_are_disjoint_from_what_the_reference_reads(name, causal):
+    lay = pc.bwd_case_layout(name)
+    o = pc.bwd_operands(lay, seed=5)
+    clean = _bwd_reference(lay, o, causal)
+    excluded = pc.row_mask(~lay.valid, lay.D)
+    dirty = {n: pc.poison_bf16(o[n], excluded, pc.NONFINITE_POISON) for n in ("q", "k", "v", "dout")}
+    assert all(bool((~torch.isfinite(t.float()) == excluded).all()) for t in dirty.values())
+    assert all(bool(torch.isfinite(x).all()) for x in clean) and all(float(x.abs().max()) > 0 for x in clean[2::3])      # (dq = dk = 0 at one key)
+    assert all(pc.bits_equal(a, b) for a, b in zip(clean, _bwd_reference(lay, dirty, causal)))
+    # the exact complement: what is unmarked is what the reference was given, and the clean operands are exact zeros under the masks
+    assert int((~excluded).sum()) == sum(lay.lens) * lay.D
+    assert all(bool((o[n][excluded] == 0).all()) for n in ("q", "k", "v", "dout"))
+    s = o["scratch"].float()
+    assert bool(torch.isfinite(s).all()) and 32 < float(s.std()) < 128, "the ordinary-magnitude scratch is N(0, 64^2)"
+
+
+def test_every_backward_case_keeps_its_reads_inside_its_tensors():
+    for name, (R, lens, q_rows) in pc.BWD_GEOMETRIES.items():
+        lay = pc.bwd_case_layout(name)
+        ext = pc.bwd_read_extent(lay)
+        print(f"POISON|attn_bwd {name}|rows per utterance {R}|largest row read {ext}")
+        assert R % 128 == 0 and all(0 <= v < R for v in ext.values())          # whole tiles: no read leaves the utterance's R rows
+        assert ext["dq_key"] == (max(lens) + 63) // 64 * 64 - 1 and ext["dkv_query"] == (q_rows + 63) // 64 * 64 - 1
+        assert max(lens) <= q_rows, "a row with dout != 0 lies below q_rows"
+    valid = pc.reducer_valid()
+    assert valid.numel() == 384 and valid.numel() % 128 == 0 and int(valid.sum()) == 128 + 1 + 37        # wgrad: rows % 64, posconv: % 128
+    assert (3 * (128 + 2 * 64)) % (128 * 3) == 0                                                         # the posconv slab rows, Z = 3 slices
+    short = pc.short_valid()
+    assert short.numel() == 96 and int(short.sum()) == 32 + 1 + 17
+    assert len(pc.REDUCERS) == len(set(pc.REDUCERS)) == 9
+
+
+def test_bit_comparison_rejects_one_nan_a_payload_and_the_sign_of_zero():
+    """the comparison every poison test ends in: one NaN written into a clean result is rejected (NaN != NaN would also reject a NaN
+    that was there before: bit equality does not), so is another NaN payload and -0 for +0"""
+    a = torch.randn(16, 8, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16)
+    b = a.clone()
+    assert pc.bits_equal(a, b)
+    b[3, 5] = float("nan")
+    assert not pc.bits_equal(a, b) and pc.bits_equal(b, b.clone())
+    one = torch.zeros(4, dtype=torch.bool)
+    one[0] = True
+    n1 = pc.poison_bf16(torch.zeros(4, dtype=torch.bfloat16), one, (0x7FC0,))
+    n2 = pc.poison_bf16(torch.zeros(4, dtype=torch.bfloat16), one, (0xFFC1,))
+    assert bool(torch.isnan(n1[0])) and bool(torch.isnan(n2[0])) and not pc.bits_equal(n1, n2)
+    assert not pc.bits_equal(torch.zeros(2), -torch.zeros(2)) and bool((torch.zeros(2) == -torch.zeros(2)).all())
+    f = torch.randn(5, generator=torch.Generator().manual_seed(2))
+    g = f.clone()
+    g[4] = float("nan")
+    assert not pc.bits_equal(f, g) and not pc.bits_equal(f, f.double())
