@@ -730,6 +730,41 @@ int sc_search_merge_u64(const uint64_t* part, int32_t nQ, int32_t S, int32_t k, 
 int sc_topk_rows_filtered_f32(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, const int64_t* q_ids,
                               const int64_t* g_ids, const uint8_t* live, float* vals, int32_t* idx, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Filtered compact gallery search: sc_search_coarse_bf16 / sc_search_rerank_f32 over the admissible gallery rows only
+ * (csrc/search_compact_filter.hip).  Additive in round 17; sc_abi_version() stays 7.
+ *   replaces: what the filtered entries above replace, on the compact index's 2 Ep bytes per gallery row.
+ *   THE RULE is the one above, unchanged: gallery row j is ADMISSIBLE for query i iff
+ *       j < N,  and  live == NULL or live[j] != 0,  and  the ids are NULL or g_ids[j] != q_ids[i]
+ *   (int64, all 64 bits compared, negative values legal).  An inadmissible row never appears, whatever its score (NaN and inf
+ *   included), and it spoils nothing.
+ *   THE CERTIFICATE OVER ADMISSIBLE ROWS.  The candidates of a query are its D best ADMISSIBLE rows by coarse score (the order
+ *   contract is unchanged); t is the coarse value of the last candidate.  Every admissible row outside the candidates has a coarse
+ *   score <= t and an exact score within eps of it, so round 15's proof holds verbatim on the admissible set.  Evaluated in fp64:
+ *       0 if eps is not finite, or if any candidate's coarse or exact value is not finite;
+ *       else 1 if the merged candidate list holds fewer than D entries - every admissible row is then a candidate (this covers fewer
+ *            than k admissible rows, where the tail is -inf / -1, and no admissible row at all, where the empty list is the exact
+ *            answer; it replaces sc_search_rerank_f32's N <= D clause);
+ *       else 1 iff e_k - |e_k| 2^-23 > t + eps.
+ *   eps must bound |exact - coarse| over the rows that can be admissible: the caller takes the three gallery norms over the LIVE rows
+ *   (a superset of every query's admissible rows is sound, so id exclusions need not enter the bounds).
+ *   sc_search_coarse_filtered_bf16  sc_search_coarse_bf16's operands, arithmetic, tile and K-tile order: an admissible row carries the
+ *                                   fp32 bits sc_search_coarse_bf16 gives it.  q_ids [nQ] / g_ids [N] int64 (both or neither), live
+ *                                   [N] uint8 or NULL, none of them padded: nothing at or past N is read.  S >= 1 slabs of
+ *                                   ceil(tiles / S) column tiles, any S (a slab past the last tile is empty).  Writes the per-slab
+ *                                   lists as 64-bit words, part [nQ, S, D] uint64, best first: key << 32 | ~row, 0 = no entry
+ *                                   (sc_search_topk_filtered_bf16's format).  Always merge and decode with sc_search_merge_u64.
+ *                                   1 <= D <= 32; Ep % 64 == 0; nQ == 0: no-op; N == 0: empty lists.
+ *   sc_search_rerank_filtered_f32   sc_search_rerank_f32's operands and its fp64 accumulation of the fp32-scaled rows (a candidate
+ *                                   index outside [0, N) is a filler), with the certificate above.
+ *   Both: argument checks in front of any launch, no atomics, nothing allocated, bit-identical results for every S and run.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_search_coarse_filtered_bf16(const sc_bf16* q_bf16, const sc_bf16* g_bf16, int32_t nQ, int32_t N, int32_t Ep, int32_t D, int32_t S,
+                                   const int64_t* q_ids, const int64_t* g_ids, const uint8_t* live, uint64_t* part, void* stream);
+int sc_search_rerank_filtered_f32(const float* q, int64_t ldq, const float* q_scale, const float* rows, int64_t ldr, const float* g_scale,
+                                  const int32_t* cand_idx, const float* cand_vals, const float* eps, int32_t nQ, int32_t N, int32_t E,
+                                  int32_t D, int32_t k, float* vals, int32_t* idx, uint8_t* certified, void* stream);
+
 /* Keyword BatchNorm: nn.BatchNorm1d over the keyword positions (avssl/module/speechclip_c_modules/kw_bn.py:167-228).
  *   x [N, E] fp32 (N = batch x keyword slots), per-channel statistics.  training: batch statistics (biased variance for the
  *   normalisation, unbiased for the running estimate; run_mean / run_var updated in place with `momentum`), save_mean / save_rstd

@@ -773,7 +773,8 @@ class KWClip_GeneralTransformer(nn.Module):
         and gallery rows are brought to unit length as ``forward`` does, so the scores are cosines.  ``k``: None = max(recall_at).
         ``query_ids`` [nQ] / ``gallery_ids`` [N] (int64 device tensors): a gallery row whose id equals the query's is left out of that
         query's list (retrieval.search's filter - a spoken caption must not retrieve itself or its siblings).  A tensor gallery takes
-        ``gallery_ids``; a GalleryIndex brings its own ``ids`` and its ``live`` mask.  Without ids the call is the unfiltered one."""
+        ``gallery_ids``; a GalleryIndex or CompactGalleryIndex brings its own ``ids`` and its ``live`` mask (the compact one goes
+        through retrieval.search_compact's filtered call and its exact fallback).  Without ids the call is the unfiltered one."""
         from .retrieval import CompactGalleryIndex, GalleryIndex, search
         if isinstance(gallery, CompactGalleryIndex):
             g_cuda = gallery.coarse.is_cuda
@@ -799,6 +800,9 @@ class KWClip_GeneralTransformer(nn.Module):
             gallery = unit_rows(gallery.detach().float())
         if query_ids is None and gallery_ids is None:
             return search(queries, gallery, k)
+        if isinstance(gallery, CompactGalleryIndex):                  # the filtered compact call is search_compact's (it certifies)
+            from .retrieval import search_compact
+            return search_compact(queries, gallery, k, query_ids=query_ids, gallery_ids=gallery_ids)[:2]
         return search(queries, gallery, k, query_ids=query_ids, gallery_ids=gallery_ids)
 
     def extract_keywords(self, wav) -> dict:

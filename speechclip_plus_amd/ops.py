@@ -1156,6 +1156,70 @@ def search_rerank(q: torch.Tensor, q_scale: Optional[torch.Tensor], rows: torch.
     return vals, idx, certified
 
 
+def search_coarse_filtered(q_bf16: torch.Tensor, g_bf16: torch.Tensor, nQ: int, N: int, D: int, q_ids: Optional[torch.Tensor] = None,
+                           g_ids: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None, slabs: Optional[int] = None):
+    """``search_coarse`` over the admissible gallery rows only (sc_search_coarse_filtered_bf16, csrc/search_compact_filter.hip):
+    gallery row j is admissible for query i iff j < N, ``live`` is None or live[j] != 0, and the ids are None or g_ids[j] != q_ids[i]
+    (``q_ids`` [nQ] / ``g_ids`` [N] int64, both or neither, all 64 bits compared; ``live`` [N] bool or uint8).  Operands and scores are
+    ``search_coarse``'s: an admissible row carries the same fp32 bits.  -> part [nQ, S, D] int64, the per-slab list words
+    (key << 32 | ~row, best first, 0 = no entry); ``search_merge(part, D)`` merges and decodes them (S = 1 included).  ``slabs``:
+    None = sc_search_slabs(nQ, N, D); any S >= 1 is legal (a slab may hold no admissible row) and the merged lists do not depend on it."""
+    if not (q_bf16.is_cuda and g_bf16.is_cuda):
+        raise RuntimeError("search_coarse_filtered runs on the HIP kernels: no CPU path")
+    assert q_bf16.dtype == torch.bfloat16 and g_bf16.dtype == torch.bfloat16 and q_bf16.dim() == 2 and g_bf16.dim() == 2
+    assert q_bf16.is_contiguous() and g_bf16.is_contiguous()
+    Ep = q_bf16.shape[1]
+    assert g_bf16.shape[1] == Ep, (q_bf16.shape, g_bf16.shape)
+    nQ, N, D = int(nQ), int(N), int(D)
+    assert q_bf16.shape[0] >= -(-nQ // 128) * 128 and g_bf16.shape[0] >= -(-N // 128) * 128, (q_bf16.shape, nQ, g_bf16.shape, N)
+    dev = q_bf16.device
+    q_ids, g_ids, live = filter_operands("search_coarse_filtered", nQ, N, q_ids, g_ids, live, dev)
+    S = search_slabs(nQ, N, D) if slabs is None else int(slabs)
+    part = torch.empty(nQ, max(S, 1), D, device=dev, dtype=torch.int64)
+    null = ctypes.c_void_p(0)
+    check(lib().sc_search_coarse_filtered_bf16(_p(q_bf16) if nQ else null, _p(g_bf16) if N else null, nQ, N, Ep, D, S,
+                                               _p(q_ids) if nQ and N else null, _p(g_ids) if nQ and N else null, _p(live) if N else null,
+                                               _p(part) if nQ else null, _stream()), "sc_search_coarse_filtered_bf16")
+    return part
+
+
+def search_rerank_filtered(q: torch.Tensor, q_scale: Optional[torch.Tensor], rows: torch.Tensor, g_scale: Optional[torch.Tensor],
+                           cand_idx: torch.Tensor, cand_vals: torch.Tensor, eps: torch.Tensor, k: int, vals: Optional[torch.Tensor] = None,
+                           idx: Optional[torch.Tensor] = None, certified: Optional[torch.Tensor] = None):
+    """``search_rerank`` with the certificate over the admissible rows (sc_search_rerank_filtered_f32, csrc/search_compact_filter.hip):
+    the same operands - ``cand_idx`` / ``cand_vals`` [nQ, D] the merged lists of ``search_coarse_filtered``, -1 = no candidate - and the
+    same fp64 re-rank; certified = 1 where every value is finite and (the query has fewer than D candidates, so every admissible row
+    is one, or e_k - |e_k| 2^-23 > cand_vals[:, D - 1] + eps).  ``eps`` must bound |exact - coarse| over the rows that can be admissible."""
+    if not (q.is_cuda and rows.is_cuda and cand_idx.is_cuda):
+        raise RuntimeError("search_rerank_filtered runs on the HIP kernels: no CPU path")
+    assert q.dtype == torch.float32 and rows.dtype == torch.float32 and q.dim() == 2 and rows.dim() == 2
+    assert (q.stride(1) == 1 or q.shape[1] == 1) and (rows.stride(1) == 1 or rows.shape[1] == 1)
+    nQ, E = q.shape
+    N = rows.shape[0]
+    assert rows.shape[1] == E, (q.shape, rows.shape)
+    D, k = int(cand_idx.shape[1]), int(k)
+    assert cand_idx.dtype == torch.int32 and cand_vals.dtype == torch.float32 and cand_idx.is_contiguous() and cand_vals.is_contiguous()
+    assert tuple(cand_idx.shape) == (nQ, D) and tuple(cand_vals.shape) == (nQ, D) and 1 <= k <= D <= 32, (cand_idx.shape, cand_vals.shape, k)
+    assert eps.dtype == torch.float32 and tuple(eps.shape) == (nQ,) and eps.is_contiguous()
+    for s, n in ((q_scale, nQ), (g_scale, N)):
+        assert s is None or (s.dtype == torch.float32 and tuple(s.shape) == (n,) and s.is_contiguous())
+    dev = q.device
+    if vals is None:
+        vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
+    if idx is None:
+        idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
+    if certified is None:
+        certified = torch.empty(nQ, device=dev, dtype=torch.uint8)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and certified.dtype == torch.uint8
+    assert vals.is_contiguous() and idx.is_contiguous() and certified.is_contiguous()
+    assert tuple(vals.shape) == (nQ, k) and tuple(idx.shape) == (nQ, k) and tuple(certified.shape) == (nQ,)
+    if nQ:
+        check(lib().sc_search_rerank_filtered_f32(_p(q), q.stride(0) if nQ > 1 else E, _p(q_scale), _p(rows) if N else ctypes.c_void_p(0),
+                                                  rows.stride(0) if N > 1 else E, _p(g_scale), _p(cand_idx), _p(cand_vals), _p(eps), nQ, N, E,
+                                                  D, k, _p(vals), _p(idx), _p(certified), _stream()), "sc_search_rerank_filtered_f32")
+    return vals, idx, certified
+
+
 def _rank_key_value(key: torch.Tensor) -> torch.Tensor:
     """the uint32 keys of csrc/rank.hip (held as int32 bits) -> the fp32 values they stand for; key 0 (no candidate) -> -inf"""
     bits = torch.where(key < 0, key & 0x7fffffff, ~key)                # key >= 2^31: a value >= 0 with its sign bit set; below: the complement

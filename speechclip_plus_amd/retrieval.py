@@ -87,7 +87,47 @@ def default_route(nQ: int, N: int) -> str:
     return "fused" if N >= FUSED_MIN_GALLERY or N == 0 else "composition"
 
 
-class GalleryIndex:
+class _LiveRows:
+    """``live`` / ``remove`` / ``restore`` / ``n_live`` of a built index (GalleryIndex, CompactGalleryIndex): the rows' data is never
+    touched, ``live`` is None (every row takes part) or a bool [N] device tensor changed in place"""
+
+    def _rows_arg(self, rows) -> torch.Tensor:
+        """row numbers (a tensor or a sequence of ints) -> int64 on the index's device, every one inside [0, N)"""
+        rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= self.N):
+            raise IndexError(f"{type(self).__name__}: rows outside [0, {self.N})")
+        return rows.to(self.device)
+
+    def _live_changed(self) -> None:
+        """``live`` has just been written"""
+
+    def remove(self, rows):
+        """Take gallery rows ``rows`` out of every later search (``live[rows] = False``, in place; the rows' data is not touched)."""
+        rows = self._rows_arg(rows)
+        if self.live is None:
+            self.live = torch.ones(self.N, device=self.device, dtype=torch.bool)
+        self.live[rows] = False
+        self._live_changed()
+        return self
+
+    def restore(self, rows=None):
+        """Put ``rows`` back (None: every row; ``live`` becomes None again, so a search runs exactly as before any ``remove``)."""
+        if rows is None:
+            self.live = None
+            self._live_changed()
+        elif self.live is not None:
+            self.live[self._rows_arg(rows)] = True
+            self._live_changed()
+        else:
+            self._rows_arg(rows)                                      # nothing is removed; the rows are still checked
+        return self
+
+    @property
+    def n_live(self) -> int:
+        return self.N if self.live is None else int(self.live.sum())
+
+
+class GalleryIndex(_LiveRows):
     """A gallery [N, E] prepared for ``search``: the side-1 three-way bf16 split of its rows ([roundup(N, 128), 6 Ep] bf16, Ep = E
     rounded up to 64: 12 Ep bytes per gallery row), built in chunks of rows so that no second fp32 copy of a large gallery is made.
     ``cosine=True``: every row is scaled by 1 / max(|g|, 1e-8) on the way in, so the scores against unit (or ``cosine=True``)
@@ -123,47 +163,18 @@ class GalleryIndex:
     def __len__(self) -> int:
         return self.N
 
-    def _rows_arg(self, rows) -> torch.Tensor:
-        """row numbers (a tensor or a sequence of ints) -> int64 on the index's device, every one inside [0, N)"""
-        rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
-        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= self.N):
-            raise IndexError(f"GalleryIndex: rows outside [0, {self.N})")
-        return rows.to(self.device)
 
-    def remove(self, rows) -> "GalleryIndex":
-        """Take gallery rows ``rows`` out of every later ``search`` (``live[rows] = False``, in place; the split is not touched)."""
-        rows = self._rows_arg(rows)
-        if self.live is None:
-            self.live = torch.ones(self.N, device=self.device, dtype=torch.bool)
-        self.live[rows] = False
-        return self
-
-    def restore(self, rows=None) -> "GalleryIndex":
-        """Put ``rows`` back (None: every row; ``live`` becomes None again, so ``search`` runs exactly as before any ``remove``)."""
-        if rows is None:
-            self.live = None
-        elif self.live is not None:
-            self.live[self._rows_arg(rows)] = True
-        else:
-            self._rows_arg(rows)                                      # nothing is removed; the rows are still checked
-        return self
-
-    @property
-    def n_live(self) -> int:
-        return self.N if self.live is None else int(self.live.sum())
-
-
-def _search_filter(queries: torch.Tensor, gallery, query_ids, gallery_ids, live):
-    """The filter of a ``search`` call, checked before anything is launched (ops.filter_operands): ``gallery_ids`` / ``live`` default
-    to a GalleryIndex's own.  -> (query_ids, gallery_ids, live), all None when the call has no filter."""
+def _search_filter(queries: torch.Tensor, gallery, query_ids, gallery_ids, live, name: str = "search"):
+    """The filter of a ``search`` / ``search_compact`` call, checked before anything is launched (ops.filter_operands): ``gallery_ids`` /
+    ``live`` default to an index's own.  -> (query_ids, gallery_ids, live), all None when the call has no filter."""
     from . import ops
-    own = isinstance(gallery, GalleryIndex)
+    own = isinstance(gallery, (GalleryIndex, CompactGalleryIndex))
     if gallery_ids is None and query_ids is not None and own:
         gallery_ids = gallery.ids
     if live is None and own:
         live = gallery.live
     nQ, N = queries.shape[0], (gallery.N if own else gallery.shape[0])
-    return ops.filter_operands("search", nQ, N, query_ids, gallery_ids, live, gallery.device if gallery.device.type == "cuda" else None,
+    return ops.filter_operands(name, nQ, N, query_ids, gallery_ids, live, gallery.device if gallery.device.type == "cuda" else None,
                                names=("query_ids", "gallery_ids", "live"))
 
 
@@ -194,12 +205,14 @@ def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex, "Co
     appears whatever its score (NaN included), -inf / -1 stand behind the last admissible row, an admissible row has the same fp32
     bits as without the filter, and one whose score is a real -inf ranks ahead of the fillers.  Both routes run with a filter and
     ``default_route`` picks as before.  Without ids and without a live mask the call runs exactly the unfiltered code.  A
-    CompactGalleryIndex with any filter is a ValueError: its certificate is stated over all N rows."""
+    CompactGalleryIndex with any filter ARGUMENT is a ValueError: the filtered compact call returns its certificate, so it is
+    ``search_compact``'s; without filter arguments the index's own removed rows are honoured."""
     from . import ops
     if isinstance(gallery, CompactGalleryIndex):      # the compact route (below): exact lists through the certificate and its fallback
         if query_ids is not None or gallery_ids is not None or live is not None:
-            raise ValueError("search: a CompactGalleryIndex takes no filter - its certificate (no row outside the candidates can belong "
-                             "to the list) would have to be restated over the admissible rows; use a GalleryIndex")
+            raise ValueError("search: a CompactGalleryIndex takes no filter arguments here - the filtered call returns its certificate "
+                             "(restated over the admissible rows), so it is search_compact(queries, index, k, query_ids=..., "
+                             "gallery_ids=..., live=...); search(queries, index, k) honours the index's own removed rows")
         if route is not None:
             raise ValueError("search: route applies to a GalleryIndex or a tensor, not to a CompactGalleryIndex")
         return search_compact(queries, gallery, k, cosine=cosine, slabs=slabs)[:2]
@@ -287,17 +300,20 @@ def _search_filtered(queries: torch.Tensor, index: GalleryIndex, k: int, cosine:
     return vals, idx.long()
 
 
-def hard_negatives(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex], a_ids: torch.Tensor, b_ids: Optional[torch.Tensor], k: int,
-                   cosine: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+def hard_negatives(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex, "CompactGalleryIndex"], a_ids: torch.Tensor,
+                   b_ids: Optional[torch.Tensor], k: int, cosine: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """Hard-negative mining: for every anchor A[i] the k highest-scoring rows of B that are WRONG for it - rows j with
     b_ids[j] != a_ids[i] - as (vals [nA, k] fp32, idx [nA, k] int64), hardest first.  ``a_ids`` [nA] / ``b_ids`` [nB]: int64 device
     tensors (the ids ``mutual_ranks`` takes to decide what is correct); ``b_ids`` None: the ids of the GalleryIndex ``B``.  This is
     ``search(A, B, k, cosine, query_ids=a_ids, gallery_ids=b_ids)``: scores, order, ties and tails are ``search``'s, an anchor with
-    fewer than k wrong rows ends in -inf / -1, and a removed row of an index (``live``) is never mined."""
+    fewer than k wrong rows ends in -inf / -1, and a removed row of an index (``live``) is never mined.  ``B`` a CompactGalleryIndex:
+    the same lists through ``search_compact(..., query_ids=a_ids, gallery_ids=b_ids)`` and its exact fallback (vals are the re-rank's)."""
     if a_ids is None:
         raise ValueError("hard_negatives: a_ids is required (without ids every row is a negative: that is search)")
-    if b_ids is None and not (isinstance(B, GalleryIndex) and B.ids is not None):
-        raise ValueError("hard_negatives: b_ids is required unless B is a GalleryIndex built with ids=")
+    if b_ids is None and not (isinstance(B, (GalleryIndex, CompactGalleryIndex)) and B.ids is not None):
+        raise ValueError("hard_negatives: b_ids is required unless B is a GalleryIndex or a CompactGalleryIndex built with ids=")
+    if isinstance(B, CompactGalleryIndex):
+        return search_compact(A, B, k, cosine=cosine, query_ids=a_ids, gallery_ids=b_ids)[:2]
     return search(A, B, k, cosine=cosine, query_ids=a_ids, gallery_ids=b_ids)
 
 
@@ -321,15 +337,22 @@ def compact_eps(q_norms: torch.Tensor, gmax: float, gtmax: float, dmax: float, E
     return (n[2] * float(gmax) + n[1] * float(dmax) + (Ep + 8) * 2.0 ** -24 * n[1] * float(gtmax)) * (1.0 + 2.0 ** -20)
 
 
-class CompactGalleryIndex:
+class CompactGalleryIndex(_LiveRows):
     """A gallery [N, E] prepared for ``search_compact``: ``coarse`` = its rows rounded to bf16 ([roundup(N, 128), Ep] bf16, Ep = E
     rounded up to 64: 2 Ep bytes per gallery row, a sixth of a GalleryIndex), built in chunks of rows; ``rows`` = the fp32 gallery the
     exact re-rank reads - kept BY REFERENCE when it is already fp32 on the device with unit column stride (the caller must not modify
     it afterwards), one fp32 copy otherwise; ``rnorm`` [N] = 1 / max(|g|, 1e-8) for ``cosine=True`` (the scores against unit or
     ``cosine=True`` queries are then cosines), else None; ``gmax`` / ``gtmax`` / ``dmax`` = the largest norm of a scaled row, of its
-    bf16 image and of their difference (``compact_eps``); ``nbytes`` = what the index itself allocated."""
+    bf16 image and of their difference (``compact_eps``); ``nbytes`` = what the index itself allocated.
 
-    def __init__(self, gallery: torch.Tensor, cosine: bool = False):
+    ``ids`` / ``live`` / ``remove(rows)`` / ``restore(rows=None)`` / ``n_live``: as on a GalleryIndex (the same checks and errors).
+    ``search_compact`` skips a removed row, and ``gmax`` / ``gtmax`` / ``dmax`` are taken over the LIVE rows only - removing a NaN or
+    huge row makes ``compact_eps`` finite and small again, so the index certifies as if the row had never been there.  For that the
+    per-row norms ``ops.rows_bf16`` reports are kept as ``norms`` [3, N] fp32 from the first time a row is dead (the first ``remove``
+    or the first ``search_compact(..., live=)``: one more pass over the fp32 rows, 12 N bytes added to ``nbytes``); an index that
+    never had a dead row holds nothing more than before.  ``restore()`` brings the three bounds of the whole gallery back bit for bit."""
+
+    def __init__(self, gallery: torch.Tensor, cosine: bool = False, ids: Optional[torch.Tensor] = None):
         from . import ops
         if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2:
             raise ValueError("CompactGalleryIndex: gallery must be a [N, E] tensor")
@@ -337,6 +360,9 @@ class CompactGalleryIndex:
             raise RuntimeError("CompactGalleryIndex runs on the HIP kernels: device tensors only")
         self.N, self.E = int(gallery.shape[0]), int(gallery.shape[1])
         assert self.E >= 1, gallery.shape
+        if ids is not None:
+            ops.filter_operands("CompactGalleryIndex", self.N, self.N, ids, ids, None, gallery.device, names=("ids", "ids", "live"))
+        self.ids, self.live, self.norms = ids, None, None
         self.cosine = bool(cosine)
         self.Ep = -(-self.E // 64) * 64
         self.rows = _rows_f32(gallery)
@@ -353,7 +379,8 @@ class CompactGalleryIndex:
                 scale = self.rnorm[r0:r1]
             _, norms = ops.rows_bf16(x, scale, out=self.coarse[r0: r0 + -(-(r1 - r0) // 128) * 128])
             top = torch.maximum(top, norms.amax(dim=1))               # amax / maximum carry a NaN on
-        self.gmax, self.gtmax, self.dmax = (float(v) for v in top.tolist())
+        self._top_all = tuple(float(v) for v in top.tolist())         # the bounds over the whole gallery: what restore() brings back
+        self.gmax, self.gtmax, self.dmax = self._top_all
         self.nbytes = self.coarse.numel() * 2 + (self.rnorm.numel() * 4 if self.cosine else 0) + (0 if held else self.rows.numel() * 4)
 
     @property
@@ -362,6 +389,35 @@ class CompactGalleryIndex:
 
     def __len__(self) -> int:
         return self.N
+
+    def _row_norms(self) -> torch.Tensor:
+        """``norms`` [3, N] fp32, computed on first use: ``ops.rows_bf16`` over the fp32 rows again, in the constructor's chunks and
+        with its scales (the same bits the constructor's maxima were taken from), the bf16 images going to a scratch buffer"""
+        if self.norms is None:
+            from . import ops
+            norms = torch.empty(3, self.N, device=self.device, dtype=torch.float32)
+            scratch = torch.empty(min(-(-self.N // 128) * 128, _INDEX_CHUNK_ROWS), self.Ep, device=self.device, dtype=torch.bfloat16)
+            for r0 in range(0, self.N, _INDEX_CHUNK_ROWS):
+                r1 = min(self.N, r0 + _INDEX_CHUNK_ROWS)
+                scale = self.rnorm[r0:r1] if self.cosine else None
+                norms[:, r0:r1] = ops.rows_bf16(self.rows[r0:r1], scale, out=scratch[: -(-(r1 - r0) // 128) * 128])[1]
+            self.norms = norms
+            self.nbytes += norms.numel() * 4
+        return self.norms
+
+    def _bounds(self, live: Optional[torch.Tensor]) -> Tuple[float, float, float]:
+        """(gmax, gtmax, dmax) over the rows with live[j] != 0 (None: every row; no such row: zeros).  A dead row's norms do not
+        enter, whatever they are; a live NaN row still makes its bound NaN.  The host reads three floats."""
+        if live is None:
+            return self._top_all
+        if self.N == 0:
+            return (0.0, 0.0, 0.0)
+        norms = self._row_norms()
+        top = torch.where((live != 0).unsqueeze(0), norms, torch.zeros((), device=norms.device, dtype=norms.dtype)).amax(dim=1)
+        return tuple(float(v) for v in top.tolist())
+
+    def _live_changed(self) -> None:
+        self.gmax, self.gtmax, self.dmax = self._bounds(self.live)
 
 
 def _exact_fallback(q: torch.Tensor, index: CompactGalleryIndex, k: int, cosine: bool):
@@ -388,8 +444,79 @@ def _exact_fallback(q: torch.Tensor, index: CompactGalleryIndex, k: int, cosine:
     return vals, idx
 
 
+def _exact_fallback_filtered(q: torch.Tensor, index: CompactGalleryIndex, k: int, cosine: bool, query_ids: Optional[torch.Tensor],
+                             gallery_ids: Optional[torch.Tensor], live: Optional[torch.Tensor]):
+    """``_exact_fallback`` over the admissible rows: the filtered ``search`` on every gallery chunk (``gallery_ids`` / ``live`` sliced
+    per chunk, ``query_ids`` [nU] the uncertified queries' own), the per-chunk lists merged and the k survivors re-scored.  With a
+    filter ANY chunk can end in fillers, so they are moved behind every entry first (a stable sort on one bit: the entries keep
+    their chunk order, which is index order); ``ops.topk_rows`` then breaks a tie by position - equal scores keep the lower gallery row
+    first, and a real -inf, an entry, stands ahead of every filler."""
+    from . import ops
+    nU, dev = q.shape[0], q.device
+    pv, pi = [], []
+    for c0 in range(0, max(index.N, 1), _FALLBACK_CHUNK_ROWS):
+        c1 = min(index.N, c0 + _FALLBACK_CHUNK_ROWS)
+        v, i = search(q, GalleryIndex(index.rows[c0:c1], cosine=index.cosine), k, cosine=cosine, query_ids=query_ids,
+                      gallery_ids=None if gallery_ids is None else gallery_ids[c0:c1], live=None if live is None else live[c0:c1])
+        pv.append(v)
+        pi.append(torch.where(i >= 0, i + c0, i))
+    if len(pv) == 1:
+        cv, ci = pv[0], pi[0].int()
+    else:
+        allv, alli = torch.cat(pv, dim=1), torch.cat(pi, dim=1)
+        _, order = torch.sort((alli < 0).to(torch.int8), dim=1, stable=True)
+        allv, alli = torch.gather(allv, 1, order), torch.gather(alli, 1, order)
+        cv, pos = ops.topk_rows(allv, allv.shape[1], k)
+        ci = torch.gather(alli, 1, pos.long()).int()
+    q_scale = ops.vq_prep(q)[1] if cosine else None
+    vals, idx, _ = ops.search_rerank(q, q_scale, index.rows, index.rnorm, ci.contiguous(), cv.contiguous(),
+                                     torch.zeros(nU, device=dev, dtype=torch.float32), k)
+    return vals, idx
+
+
+def _search_compact_filtered(queries: torch.Tensor, index: CompactGalleryIndex, k: int, cosine: bool, D: int, fallback: str,
+                             slabs: Optional[int], query_ids: Optional[torch.Tensor], gallery_ids: Optional[torch.Tensor],
+                             live: Optional[torch.Tensor], bounds: Tuple[float, float, float]):
+    """``search_compact`` with a filter: the same chunking and buffers, the candidates by csrc/search_compact_filter.hip (a loop of its
+    own, so that the unfiltered one stays exactly as it was).  ``live``: the effective mask (uint8) or None; ``bounds``: gmax / gtmax /
+    dmax over its rows."""
+    from . import ops
+    nQ, dev = queries.shape[0], queries.device
+    vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
+    cert = torch.empty(nQ, device=dev, dtype=torch.uint8)
+    if nQ == 0:
+        return vals, idx.long(), cert.bool()
+    q = _rows_f32(queries)
+    S = None if slabs is None else max(int(slabs), 1)                 # any number of slabs is legal here: an empty one writes no entry
+    chunk = min(_INDEX_CHUNK_ROWS, -(-nQ // 128) * 128)
+    qbuf = torch.empty(chunk, index.Ep, device=dev, dtype=torch.bfloat16)                # the one query buffer of the call
+    for r0 in range(0, nQ, chunk):
+        r1 = min(nQ, r0 + chunk)
+        qc = q[r0:r1]
+        q_scale = ops.vq_prep(qc)[1] if cosine else None
+        q16, norms = ops.rows_bf16(qc, q_scale, out=qbuf[: -(-(r1 - r0) // 128) * 128])
+        eps = compact_eps(norms, *bounds, index.Ep).float()
+        part = ops.search_coarse_filtered(q16, index.coarse, r1 - r0, index.N, D, q_ids=None if query_ids is None else query_ids[r0:r1],
+                                          g_ids=gallery_ids, live=live, slabs=S)
+        cv, ci = ops.search_merge(part, D)
+        ops.search_rerank_filtered(qc, q_scale, index.rows, index.rnorm, ci, cv, eps, k, vals=vals[r0:r1], idx=idx[r0:r1],
+                                   certified=cert[r0:r1])
+    cert = cert.bool()
+    if fallback == "exact":
+        todo = torch.nonzero(~cert).squeeze(1)                        # the host reads the mask here
+        if todo.numel():
+            fv, fi = _exact_fallback_filtered(q[todo].contiguous(), index, k, cosine, None if query_ids is None else query_ids[todo],
+                                              gallery_ids, live)
+            vals[todo] = fv
+            idx[todo] = fi
+    return vals, idx.long(), cert
+
+
 def search_compact(queries: torch.Tensor, gallery: Union[torch.Tensor, CompactGalleryIndex], k: int, cosine: bool = False, depth: int = 32,
-                   fallback: str = "exact", slabs: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                   fallback: str = "exact", slabs: Optional[int] = None, *, query_ids: Optional[torch.Tensor] = None,
+                   gallery_ids: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """queries [nQ, E], gallery [N, E] (or a CompactGalleryIndex of it) -> (vals [nQ, k] fp32, idx [nQ, k] int64, certified [nQ] bool):
     ``search``'s lists from a bf16 copy of the gallery.  1 <= k <= depth <= 32.  Per query: the ``depth`` best rows by the bf16 x bf16
     score (one K-block instead of six), re-ranked by their inner products accumulated in fp64 from the fp32 rows, and the certificate
@@ -404,20 +531,47 @@ def search_compact(queries: torch.Tensor, gallery: Union[torch.Tensor, CompactGa
     is searched again by ``search`` against the fp32 rows, in gallery chunks of 131072 rows, and re-scored the same way; their
     ``certified`` stays False.  This costs a PASS OVER THE WHOLE GALLERY (a three-way split of every chunk included) whenever any row
     is uncertified.  ``fallback="none"``: no synchronisation; an uncertified row holds the best k of its candidates.  ``slabs``:
-    at most so many slabs of the coarse kernel's gallery axis (tests; empty slabs are dropped, the result does not depend on it)."""
+    at most so many slabs of the coarse kernel's gallery axis (tests; empty slabs are dropped, the result does not depend on it).
+
+    Filter (csrc/search_compact_filter.hip): gallery row j is ADMISSIBLE for query i iff j < N, ``live`` is absent or live[j] != 0, and
+    ids are absent or gallery_ids[j] != query_ids[i] - ``search``'s rule and operands (int64 ids, both or neither, all 64 bits
+    compared; ``live`` bool or uint8; checked before anything is launched).  ``gallery_ids`` defaults to the index's ``ids``; the
+    effective mask is the index's ``live`` AND the argument.  The result is the contract above over the admissible rows only: an
+    inadmissible row never appears, whatever its score (NaN and inf included), and it spoils nothing.  The certificate is restated
+    over them: the candidates are the ``depth`` best ADMISSIBLE rows by coarse score; a query with fewer than ``depth`` candidates has
+    every admissible row among them and is certified (its tail is -inf / -1; with no admissible row the empty list is the exact
+    answer), every other one by the inequality above, and ``compact_eps`` takes the gallery's three norms over the LIVE rows (a
+    superset of every query's admissible rows, so ids do not enter the bounds) - a removed NaN or huge row no longer costs every
+    query its certificate.  The exact fallback runs the filtered ``search`` per gallery chunk with the same ids and mask.  A call
+    without ids and without ``live=`` on an index with nothing removed runs exactly the unfiltered code."""
     from . import ops
     if not isinstance(queries, torch.Tensor) or queries.dim() != 2:
         raise ValueError("search_compact: queries must be a [nQ, E] tensor")
-    g_cuda = gallery.coarse.is_cuda if isinstance(gallery, CompactGalleryIndex) else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
+    own = isinstance(gallery, CompactGalleryIndex)
+    filtered = query_ids is not None or gallery_ids is not None or live is not None or (own and gallery.live is not None)
+    if filtered:
+        if not own and not (isinstance(gallery, torch.Tensor) and gallery.dim() == 2):
+            raise ValueError("search_compact: gallery must be a [N, E] tensor or a CompactGalleryIndex")
+        call_live = live
+        query_ids, gallery_ids, live = _search_filter(queries, gallery, query_ids, gallery_ids, live, name="search_compact")
+    g_cuda = gallery.coarse.is_cuda if own else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
     if not queries.is_cuda or not g_cuda:
         raise RuntimeError("search_compact runs on the HIP kernels: device tensors only")
     if fallback not in ("exact", "none"):
         raise ValueError(f"search_compact: fallback = {fallback!r} (\"exact\" or \"none\")")
-    index = gallery if isinstance(gallery, CompactGalleryIndex) else CompactGalleryIndex(gallery, cosine=cosine)
+    index = gallery if own else CompactGalleryIndex(gallery, cosine=cosine)
     nQ, E = queries.shape
     assert E == index.E, (queries.shape, index.E)
     k, D = int(k), int(depth)
     assert 1 <= k <= D <= 32, f"k = {k}, depth = {D}: 1 <= k <= depth <= 32"
+    if filtered:
+        if call_live is None:
+            bounds = (index.gmax, index.gtmax, index.dmax)            # the index's own mask (or none): its bounds are kept up to date
+        else:
+            if index.live is not None:
+                live = ((live != 0) & index.live).view(torch.uint8)
+            bounds = index._bounds(live)
+        return _search_compact_filtered(queries, index, k, cosine, D, fallback, slabs, query_ids, gallery_ids, live, bounds)
     dev = queries.device
     vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
     idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
