@@ -765,6 +765,32 @@ int sc_search_rerank_filtered_f32(const float* q, int64_t ldq, const float* q_sc
                                   const int32_t* cand_idx, const float* cand_vals, const float* eps, int32_t nQ, int32_t N, int32_t E,
                                   int32_t D, int32_t k, float* vals, int32_t* idx, uint8_t* certified, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Wide gallery search: per-row top-K for k in the hundreds over a score matrix (csrc/topk_wide.hip).  Additive in round 18;
+ * sc_abi_version() stays 7.
+ *   replaces: torch.argsort(score, descending=True) over the whole score matrix (avssl/module/retrieval.py:45-46), the ranking that is
+ *             computed and dropped - here the first k <= 1024 entries of every row of it, for callers that want the list itself at
+ *             @50 / @100, 64 to 256 hard negatives per anchor, or a top-200 shortlist for a slower re-scorer.
+ *   sc_topk_rows_wide_f32  scores [rows, ld] fp32 with V valid columns (ld >= V; columns >= V are padding, never candidates and never
+ *                          read) -> vals [rows, k] fp32, idx [rows, k] int32, best first.  33 <= k <= 1024 is the range it is meant
+ *                          for; 1 <= k <= 1024 is accepted so that it can be compared with sc_topk_rows_f32.  V <= 2^30.
+ *                          q_ids [rows] / g_ids [V] int64 (both or both NULL), live [V] uint8 or NULL.
+ *                          THE ORDER is sc_topk_rows_f32's, word for word: larger value first; the lower column first among equal
+ *                          values (-0 == +0); NaN above every number, the lower column first among NaNs; fewer than k eligible
+ *                          columns: -inf / -1 behind them; vals are the matrix's own bits (-0, NaN payloads), re-read at the end;
+ *                          rows == 0: no-op; no float atomics, the same input gives the same bits.
+ *                          THE FILTER is the rule above: column j is eligible iff j < V, live is NULL or live[j] != 0, and the ids
+ *                          are NULL or g_ids[j] != q_ids[row].  An ineligible column behaves as absent, whatever its score (NaN
+ *                          included); an eligible real -inf ranks ahead of every filler.  The score matrix is not modified.
+ *                          One workgroup per row: an exact radix select of the k-th key over LDS histograms (three passes), one
+ *                          admitting pass (a block prefix count in column order decides among the columns equal to the k-th key, so
+ *                          a row of V equal scores is no special case), a sort of the k words in LDS.  16-byte loads when ``scores``
+ *                          is 16-byte aligned and ld % 4 == 0, element loads otherwise.  Argument checks in front of the launch,
+ *                          nothing allocated.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_topk_rows_wide_f32(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, const int64_t* q_ids,
+                          const int64_t* g_ids, const uint8_t* live, float* vals, int32_t* idx, void* stream);
+
 /* Keyword BatchNorm: nn.BatchNorm1d over the keyword positions (avssl/module/speechclip_c_modules/kw_bn.py:167-228).
  *   x [N, E] fp32 (N = batch x keyword slots), per-channel statistics.  training: batch statistics (biased variance for the
  *   normalisation, unbiased for the running estimate; run_mean / run_var updated in place with `momentum`), save_mean / save_rstd

@@ -770,7 +770,8 @@ class KWClip_GeneralTransformer(nn.Module):
         "parallel"; None: ``config.retrieval.audio_feat_src``) picks the branch output.  ``gallery``: image or caption embeddings
         [N, E] (what ``forward_image`` / ``forward_text`` return) or a retrieval.GalleryIndex / CompactGalleryIndex built with
         ``cosine=True``.  Query
-        and gallery rows are brought to unit length as ``forward`` does, so the scores are cosines.  ``k``: None = max(recall_at).
+        and gallery rows are brought to unit length as ``forward`` does, so the scores are cosines.  ``k``: None = max(recall_at); 1 <= k <= 1024 on a tensor or a
+        GalleryIndex (k > 32 runs retrieval.search's wide selection), k <= 32 on a CompactGalleryIndex.
         ``query_ids`` [nQ] / ``gallery_ids`` [N] (int64 device tensors): a gallery row whose id equals the query's is left out of that
         query's list (retrieval.search's filter - a spoken caption must not retrieve itself or its siblings).  A tensor gallery takes
         ``gallery_ids``; a GalleryIndex or CompactGalleryIndex brings its own ``ids`` and its ``live`` mask (the compact one goes

@@ -1006,6 +1006,51 @@ def topk_rows_filtered(scores: torch.Tensor, V: int, k: int, q_ids: Optional[tor
     return vals, idx
 
 
+def topk_rows_wide(scores: torch.Tensor, V: int, k: int, *, q_ids: Optional[torch.Tensor] = None, g_ids: Optional[torch.Tensor] = None,
+                   live: Optional[torch.Tensor] = None, vals: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None):
+    """``topk_rows`` / ``topk_rows_filtered`` for k up to 1024 (sc_topk_rows_wide_f32, csrc/topk_wide.hip; meant for 33 <= k <= 1024,
+    1 <= k accepted): scores [rows, >= V] fp32 (unit column stride, any row pitch and base alignment) -> (vals [rows, k] fp32, idx
+    [rows, k] int32), the k best eligible columns of every row, best first in ``topk_rows``' order - larger value first, ties to the
+    lower column (-0 == +0), NaN above every number, -inf / -1 behind the last eligible column; vals are the matrix's own bits.
+    Column j is eligible for row i iff j < V, ``live`` is None or live[j] != 0, and the ids are None or g_ids[j] != q_ids[i]
+    (``q_ids`` [rows] / ``g_ids`` [V] int64, both or neither; ``live`` [V] bool or uint8); an eligible -inf keeps its column.
+    ``scores`` is not modified.  ``vals`` / ``idx``: caller-owned contiguous outputs."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2:
+        raise ValueError("topk_rows_wide: scores must be a [rows, >= V] tensor")
+    if not scores.is_cuda:
+        raise RuntimeError("topk_rows_wide runs on the HIP kernels: no CPU path")
+    if scores.dtype != torch.float32:
+        raise ValueError(f"topk_rows_wide: scores must be torch.float32, not {scores.dtype}")
+    rows, V, k = scores.shape[0], int(V), int(k)
+    if not (scores.stride(1) == 1 or scores.shape[1] == 1):
+        raise ValueError("topk_rows_wide: scores must have unit column stride")
+    if not 1 <= V <= scores.shape[1]:
+        raise ValueError(f"topk_rows_wide: scores has shape {tuple(scores.shape)}, expected at least ({rows}, {V}) with V >= 1")
+    if not 1 <= k <= 1024:
+        raise RuntimeError(f"topk_rows_wide: 1 <= k <= 1024 (k {k})")
+    q_ids, g_ids, live = filter_operands("topk_rows_wide", rows, V, q_ids, g_ids, live, scores.device)
+    ld = scores.stride(0) if rows > 1 else max(V, 1)
+    if vals is None:
+        vals = torch.empty(rows, k, device=scores.device, dtype=torch.float32)
+    if idx is None:
+        idx = torch.empty(rows, k, device=scores.device, dtype=torch.int32)
+    for what, t, dtype in (("vals", vals, torch.float32), ("idx", idx, torch.int32)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"topk_rows_wide: {what} must be a tensor")
+        if t.dtype != dtype:
+            raise ValueError(f"topk_rows_wide: {what} must be {dtype}, not {t.dtype}")
+        if tuple(t.shape) != (rows, k):
+            raise ValueError(f"topk_rows_wide: {what} has shape {tuple(t.shape)}, expected ({rows}, {k})")
+        if not t.is_contiguous():
+            raise ValueError(f"topk_rows_wide: {what} must be contiguous")
+        if t.device != scores.device:
+            raise ValueError(f"topk_rows_wide: {what} is on {t.device}, the operands on {scores.device}")
+    null = ctypes.c_void_p(0)
+    check(lib().sc_topk_rows_wide_f32(_p(scores) if rows else null, ld, rows, V, k, _p(q_ids), _p(g_ids), _p(live),
+                                      _p(vals) if rows else null, _p(idx) if rows else null, _stream()), "sc_topk_rows_wide_f32")
+    return vals, idx
+
+
 def search_merge(part: torch.Tensor, k: int, vals: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None):
     """part [nQ, S, k] int64 - the per-slab list words ``search_topk_filtered``'s kernel writes (key << 32 | ~row, best first, 0 = no
     entry) -> (vals [nQ, k] fp32, idx [nQ, k] int32): per query the k largest words, decoded; -inf / -1 where a query has fewer than

@@ -183,7 +183,11 @@ def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex, "Co
            gallery_ids: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """queries [nQ, E], gallery [N, E] (or a GalleryIndex of it) -> (vals [nQ, k] fp32, idx [nQ, k] int64): for every query the k
     gallery rows with the largest inner product, best first, on the device.  ``cosine=True`` scales query and gallery rows by
-    1 / max(|x|, 1e-8) first (a GalleryIndex carries its own choice; the flag then applies to the queries).  1 <= k <= 32.
+    1 / max(|x|, 1e-8) first (a GalleryIndex carries its own choice; the flag then applies to the queries).  1 <= k <= 1024.
+    k <= 32 runs the routes below.  32 < k <= 1024 ("wide", csrc/topk_wide.hip): always the composition route's scores, selected by
+    ``ops.topk_rows_wide`` under the same order and filter rules; ``default_route`` is not consulted, ``route="fused"`` or ``slabs=`` is a
+    ValueError (the fused kernel keeps 32 rows per query), so is a CompactGalleryIndex (its certificate is built on 32 candidates:
+    use a GalleryIndex) and a gallery of more than 262 144 rows (128 query rows of scores must fit the 128 MiB scratch).
 
     Order: larger score first, the lower gallery index first among equal scores, NaN above every number; fewer than k gallery rows:
     -inf / -1 behind them.  ``vals`` are the kernel's fp32 scores: the three-way bf16 splits of both rows multiplied on the bf16
@@ -208,6 +212,8 @@ def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex, "Co
     CompactGalleryIndex with any filter ARGUMENT is a ValueError: the filtered compact call returns its certificate, so it is
     ``search_compact``'s; without filter arguments the index's own removed rows are honoured."""
     from . import ops
+    if int(k) > 32:                                   # the wide selection (below); everything from here on is the k <= 32 code, unchanged
+        return _search_wide(queries, gallery, int(k), cosine, slabs, route, query_ids, gallery_ids, live)
     if isinstance(gallery, CompactGalleryIndex):      # the compact route (below): exact lists through the certificate and its fallback
         if query_ids is not None or gallery_ids is not None or live is not None:
             raise ValueError("search: a CompactGalleryIndex takes no filter arguments here - the filtered call returns its certificate "
@@ -229,7 +235,8 @@ def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex, "Co
     nQ, E = queries.shape
     assert E == index.E, (queries.shape, index.E)
     k = int(k)
-    assert 1 <= k <= 32, f"k = {k}: the selection keeps at most 32 gallery rows per query"
+    if not 1 <= k <= WIDE_MAX_K:
+        raise ValueError(f"search: 1 <= k <= {WIDE_MAX_K} (k {k})")
     dev = queries.device
     if query_ids is not None or live is not None:
         return _search_filtered(queries, index, k, cosine, slabs, route, query_ids, gallery_ids, live)
@@ -300,6 +307,70 @@ def _search_filtered(queries: torch.Tensor, index: GalleryIndex, k: int, cosine:
     return vals, idx.long()
 
 
+WIDE_MAX_K = 1024                  # csrc/topk_wide.hip sorts the list in 8 KiB of LDS
+
+
+def wide_max_gallery() -> int:
+    """The largest gallery ``search`` serves at k > 32: 128 query rows (one row tile of the score GEMM) of fp32 scores, the gallery axis
+    rounded up to 128, must fit the 128 MiB score scratch of the composition route -> 262 144 rows."""
+    from .keyword_neighbors import SCORE_SCRATCH_BYTES
+    return SCORE_SCRATCH_BYTES // (4 * 128) // 128 * 128
+
+
+def _search_wide(queries: torch.Tensor, gallery, k: int, cosine: bool, slabs: Optional[int], route: Optional[str],
+                 query_ids: Optional[torch.Tensor], gallery_ids: Optional[torch.Tensor], live: Optional[torch.Tensor]):
+    """``search`` for 32 < k <= 1024: the composition route's chunks, buffers and score kernel (ops.cosine_scores_split into the one
+    score scratch), the selection by csrc/topk_wide.hip, with or without a filter (a loop of its own, so that the k <= 32 code stays
+    exactly as it was).  Format errors come before device errors."""
+    from . import ops
+    if k > WIDE_MAX_K:
+        raise ValueError(f"search: 1 <= k <= {WIDE_MAX_K} (k {k})")
+    if isinstance(gallery, CompactGalleryIndex):
+        raise ValueError(f"search: k = {k} on a CompactGalleryIndex - its certificate is built on at most 32 candidates per query "
+                         "(k <= depth <= 32); build a GalleryIndex of the gallery for 32 < k <= 1024")
+    if route == "fused" or slabs is not None:
+        raise ValueError(f"search: k = {k} with route=\"fused\" / slabs= - the fused kernel keeps at most 32 gallery rows per query; "
+                         "32 < k <= 1024 runs the composition route (route=None or \"composition\")")
+    if route not in (None, "composition"):
+        raise ValueError(f"search: route = {route!r} (\"fused\" or \"composition\")")
+    if not isinstance(queries, torch.Tensor) or queries.dim() != 2:
+        raise ValueError("search: queries must be a [nQ, E] tensor")
+    if not isinstance(gallery, (torch.Tensor, GalleryIndex)) or (isinstance(gallery, torch.Tensor) and gallery.dim() != 2):
+        raise ValueError("search: gallery must be a [N, E] tensor or a GalleryIndex")
+    if query_ids is not None or gallery_ids is not None or live is not None or (isinstance(gallery, GalleryIndex) and gallery.live is not None):
+        query_ids, gallery_ids, live = _search_filter(queries, gallery, query_ids, gallery_ids, live)
+    g_cuda = gallery.split.is_cuda if isinstance(gallery, GalleryIndex) else gallery.is_cuda
+    if not queries.is_cuda or not g_cuda:
+        raise RuntimeError("search runs on the HIP kernels: device tensors only")
+    N = gallery.N if isinstance(gallery, GalleryIndex) else int(gallery.shape[0])
+    if N > wide_max_gallery():
+        raise ValueError(f"search: k = {k} against {N} gallery rows - 128 query rows of scores no longer fit the score scratch; "
+                         f"32 < k <= {WIDE_MAX_K} serves at most N = {wide_max_gallery()} gallery rows (k <= 32 has no such limit)")
+    index = gallery if isinstance(gallery, GalleryIndex) else GalleryIndex(gallery, cosine=cosine)
+    nQ, E = queries.shape
+    assert E == index.E, (queries.shape, index.E)
+    dev = queries.device
+    vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
+    if nQ > 0 and N == 0:                                                 # no gallery row: fillers only (nothing to score)
+        vals.fill_(float("-inf"))
+        idx.fill_(-1)
+    elif nQ > 0:
+        from .keyword_neighbors import default_chunk_rows
+        q = _rows_f32(queries)
+        chunk = min(default_chunk_rows(N), -(-nQ // 128) * 128)
+        scores = torch.empty(chunk, index.split.shape[0], device=dev, dtype=torch.float32)       # the one score scratch of the call
+        split = torch.empty(chunk, 6 * index.Ep, device=dev, dtype=torch.bfloat16)           # the one query-split buffer of the call
+        for r0 in range(0, nQ, chunk):
+            r1 = min(nQ, r0 + chunk)
+            rp = -(-(r1 - r0) // 128) * 128
+            rnorm = ops.vq_prep(q[r0:r1])[1] if cosine else None
+            ops.cosine_scores_split(q[r0:r1], rnorm, index.split, index.split.shape[0], out=scores[:rp], split_out=split[:rp])
+            ops.topk_rows_wide(scores[: r1 - r0], N, k, q_ids=None if query_ids is None else query_ids[r0:r1], g_ids=gallery_ids,
+                               live=live, vals=vals[r0:r1], idx=idx[r0:r1])
+    return vals, idx.long()
+
+
 def hard_negatives(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex, "CompactGalleryIndex"], a_ids: torch.Tensor,
                    b_ids: Optional[torch.Tensor], k: int, cosine: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """Hard-negative mining: for every anchor A[i] the k highest-scoring rows of B that are WRONG for it - rows j with
@@ -307,7 +378,9 @@ def hard_negatives(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex, "Compac
     tensors (the ids ``mutual_ranks`` takes to decide what is correct); ``b_ids`` None: the ids of the GalleryIndex ``B``.  This is
     ``search(A, B, k, cosine, query_ids=a_ids, gallery_ids=b_ids)``: scores, order, ties and tails are ``search``'s, an anchor with
     fewer than k wrong rows ends in -inf / -1, and a removed row of an index (``live``) is never mined.  ``B`` a CompactGalleryIndex:
-    the same lists through ``search_compact(..., query_ids=a_ids, gallery_ids=b_ids)`` and its exact fallback (vals are the re-rank's)."""
+    the same lists through ``search_compact(..., query_ids=a_ids, gallery_ids=b_ids)`` and its exact fallback (vals are the re-rank's).
+    1 <= k <= 1024 on a tensor or a GalleryIndex (k > 32: ``search``'s wide selection, at most 262 144 rows in ``B``); k <= 32 on a
+    CompactGalleryIndex."""
     if a_ids is None:
         raise ValueError("hard_negatives: a_ids is required (without ids every row is a negative: that is search)")
     if b_ids is None and not (isinstance(B, (GalleryIndex, CompactGalleryIndex)) and B.ids is not None):
