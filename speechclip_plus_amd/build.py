@@ -16,6 +16,10 @@ GELU_EXACT_SOURCES = ["backward.hip", "frontend.hip", "gemm_bf16.hip", "gemm256_
 SOURCES = ["sc_error.cpp", "hubert_layer.cpp", "gemm_bf16.hip", "gemm256_bf16.hip", "attention.hip", "attention_bwd.hip", "rowops.hip", "wavlm_gate.hip", "frontend.hip", "posconv.hip", "posconv_bwd.hip", "clspool.hip", "kwpool.hip",
            "loss_optim.hip", "headtail.hip", "rowtail.hip", "backward.hip", "softmax.hip", "cif.hip", "vq.hip", "prompt.hip", "attn_short.hip", "vit.hip", "topk.hip", "image_prep.hip", "search.hip", "rank.hip", "search_compact.hip",
            "search_filter.hip", "search_compact_filter.hip", "topk_wide.hip"]
+# The fused top-k scan (csrc/search_kernels.h) is sensitive to where its loops fall in the instruction stream: the same instructions 60
+# bytes further on ran 1 - 7 % slower (docs/rounds/r19_search_family.md).  The files that instantiate it pin every loop head to 32 bytes,
+# so their speed no longer depends on what stands in front of the loops.
+ALIGN_LOOPS_SOURCES = ["search.hip", "search_filter.hip", "search_compact.hip", "search_compact_filter.hip"]
 
 
 def _stale(target, deps):
@@ -39,7 +43,7 @@ def build(force: bool = False, verbose: bool = True, diag: bool = True) -> str:
         stem = os.path.splitext(src)[0]
         obj = os.path.join(CSRC, stem + ".o")
         objs.append(obj)
-        variants = [(obj, [])]
+        variants = [(obj, ["-falign-loops=32"] if src in ALIGN_LOOPS_SOURCES else [])]
         if diag and src in DIAG_SOURCES:
             dobj = os.path.join(CSRC, stem + "_diag.o")
             diag_objs.append(dobj)

@@ -4,15 +4,14 @@
 //   replaces: the sort-and-look-up of avssl/module/retrieval.py:45-121 (and the half dozen [nA, nB] temporaries a masked-maximum form
 //             of it needs per direction) on the scores of avssl/model/kwClip.py:447-482.
 //
-// Scores: csrc/search.hip's, to the bit.  A is the side-0 three-way split sc_split3_bf16 writes, B the side-1 split, rows padded to 128,
-// K6 = 6 Ep columns; a score is the fp32 sum of the six K-blocks on v_mfma_f32_16x16x32_bf16, K-tiles in increasing order.  The K loop is
-// search.hip's (gemm_bf16.hip's 128 x 128 tile) written again: 256 threads = 2 x 2 waves, LDS-DMA staging into two buffers, 16-byte chunk
-// index XOR ((row >> 1) & 7) applied on the global source address, one barrier per K-tile.
+// Scores: csrc/search.hip's, to the bit - the same code.  A is the side-0 three-way split sc_split3_bf16 writes, B the side-1 split, rows
+// padded to 128, K6 = 6 Ep columns; a score is the fp32 sum of the six K-blocks, K-tiles in increasing order: search_tile.h's tile, with
+// its grid of row tiles x S slabs of column tiles.
 //
 // The pair (i, j) is CORRECT iff a_ids[i] == b_ids[j].  One 128 x 128 score tile serves both directions: its rows for A -> B, its columns
 // for B -> A.  Two launches of one kernel body (template parameter PHASE), both over the same K loop, so the score compared in the second
 // is bit for bit the score that produced ``best`` in the first:
-//   PHASE 0, best:   per row the largest key (tk_key of csrc/topk.hip: float order, -0 == +0, every NaN on top) over correct, non-NaN
+//   PHASE 0, best:   per row the largest key (search_common.h's tk_key: float order, -0 == +0, every NaN on top) over correct, non-NaN
 //                    columns; per column the same over correct, non-NaN rows.  Combined across tiles with atomicMax on a uint32 key
 //                    per row / per column; key 0 = no correct non-NaN candidate.  A tile whose 128 + 128 ids hold no matching pair
 //                    (every thread compares its column's id with half of the rows' ids in LDS, one workgroup-wide OR) contributes
@@ -31,37 +30,14 @@
 //
 // Only integer atomicMax / atomicAdd from vector lanes: the result is bitwise reproducible and independent of S.  Every buffer is the
 // caller's, the four outputs zeroed by the caller; nothing is allocated here.
-#include "sc_common.h"
+#include "search_tile.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int ROWB = BK * 2;                        // bytes per LDS tile row
-constexpr int A_BYTES = BM * ROWB, B_BYTES = BN * ROWB;
-constexpr int RING_BYTES = 2 * (A_BYTES + B_BYTES);
-static_assert(RING_BYTES == BM * BN * 4, "the 32-bit key tile lies exactly over the two-stage ring");
-constexpr int TM = 64, TN = 64, FM = 4, FN = 4;     // per-wave tile, 16 x 16 fragments
 constexpr int SIDE_BYTES = BM * 8 + BM * 4 + 2 * BN * 4;   // ids and best keys of the 128 rows, the two halves' column partials
 constexpr int LDS_BYTES = RING_BYTES + SIDE_BYTES;
-
-constexpr uint32_t TK_NAN = 0xffffffffu;     // above +inf (0xff800000); 0 is below every real key (-inf maps to 0x007fffff)
-
-// fp32 -> uint32 with the order of csrc/topk.hip's contract: a < b as floats <=> key(a) < key(b); -0 and +0 share a key; every NaN is
-// TK_NAN
-__device__ __forceinline__ uint32_t tk_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    uint32_t k = u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
-    if ((u & 0x7fffffffu) > 0x7f800000u) k = TK_NAN;
-    if (k == 0x7fffffffu) k = 0x80000000u;
-    return k;
-}
-
-__device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #pragma unroll
@@ -90,24 +66,11 @@ template <int PHASE>
 __global__ __launch_bounds__(256) void rank_kernel(const RankArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
+    const TileBlock blk(p.nA, p.nB, p.tiles);
+    const int m0 = blk.m0;
+    const ScoreTile tile(p.a, p.b, m0, p.K6);
+    const int lane = tile.lane, wave = tile.wave;
 
-    // ---- block -> (row tile, slab): search.hip's XCD remap (bijective; blocks b, b + 8, ... share an L2), then row tiles fastest
-    const int nM = (p.nA + BM - 1) / BM;
-    const int nT = (p.nB + BN - 1) / BN;
-    int L;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    const int slab = L / nM, m_tile = L - slab * nM;
-    const int m0 = m_tile * BM;
-    const int t_begin = slab * p.tiles, t_end = min(nT, t_begin + p.tiles);
-
-    char* const As = smem;
-    char* const Bs = smem + 2 * A_BYTES;
     uint32_t* const Ks = (uint32_t*)smem;                               // [BM][BN] keys of the tile's scores
     int64_t* const aid_s = (int64_t*)(smem + RING_BYTES);               // [BM] ids of the tile's rows
     uint32_t* const abest_s = (uint32_t*)(smem + RING_BYTES + BM * 8);  // [BM] their best keys (PHASE 1)
@@ -128,31 +91,7 @@ __global__ __launch_bounds__(256) void rank_kernel(const RankArgs p) {
     const int rows_here = min(32, p.nA - m0 - wave * 32);              // wave-uniform; <= 0: nothing to scan
     uint32_t row_acc = 0;
 
-    // ---- DMA source pointers of the row tile (per lane; the swizzle lives in the source address) ------------------------
-    constexpr int A_INST = BM / 32, B_INST = BN / 32;
-    const uint16_t* a_src[A_INST];
-#pragma unroll
-    for (int i = 0; i < A_INST; ++i) {
-        const int row = (i * 4 + wave) * 8 + (lane >> 3);
-        const int ch = (lane & 7) ^ ((row >> 1) & 7);
-        a_src[i] = p.a + (int64_t)(m0 + row) * p.K6 + ch * 8;         // rows are padded to 128: in bounds
-    }
-    int a_off[FM][2], b_off[FN][2];
-#pragma unroll
-    for (int mi = 0; mi < FM; ++mi) {
-        const int row = wm * TM + mi * 16 + (lane & 15);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) a_off[mi][kk] = row * ROWB + (((kk * 4 + (lane >> 4)) ^ ((row >> 1) & 7)) << 4);
-    }
-#pragma unroll
-    for (int ni = 0; ni < FN; ++ni) {
-        const int row = wn * TN + ni * 16 + (lane & 15);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) b_off[ni][kk] = row * ROWB + (((kk * 4 + (lane >> 4)) ^ ((row >> 1) & 7)) << 4);
-    }
-    const int nk = p.K6 / BK;
-
-    for (int t = t_begin; t < t_end; ++t) {
+    for (int t = blk.t_begin; t < blk.t_end; ++t) {
         const int n0 = t * BN;
         // ids (and best keys) of this thread's columns: straight from global memory, in flight under the K loop
         const bool okc = n0 + c < p.nB;
@@ -169,60 +108,9 @@ __global__ __launch_bounds__(256) void rank_kernel(const RankArgs p) {
             if (!__syncthreads_or(hit)) continue;
         }
 
-        const uint16_t* b_src[B_INST];
-#pragma unroll
-        for (int i = 0; i < B_INST; ++i) {
-            const int row = (i * 4 + wave) * 8 + (lane >> 3);
-            const int ch = (lane & 7) ^ ((row >> 1) & 7);
-            b_src[i] = p.b + (int64_t)(n0 + row) * p.K6 + ch * 8;     // rows are padded to 128: in bounds
-        }
-        auto stage = [&](int buf, int kt) {
-#pragma unroll
-            for (int i = 0; i < A_INST; ++i) glds16(a_src[i] + kt * BK, As + buf * A_BYTES + (i * 4 + wave) * 1024);
-#pragma unroll
-            for (int i = 0; i < B_INST; ++i) glds16(b_src[i] + kt * BK, Bs + buf * B_BYTES + (i * 4 + wave) * 1024);
-        };
         f32x4 acc[FM][FN];
-#pragma unroll
-        for (int mi = 0; mi < FM; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < FN; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-        stage(0, 0);
-        __syncthreads();   // hipcc drains the DMA (vmcnt(0)) in front of the barrier
-        for (int kt = 0; kt < nk; ++kt) {
-            const int buf = kt & 1;
-            if (kt + 1 < nk) stage(buf ^ 1, kt + 1);
-            const char* as = As + buf * A_BYTES;
-            const char* bs = Bs + buf * B_BYTES;
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                bf16x8 af[FM], bfr[FN];
-#pragma unroll
-                for (int mi = 0; mi < FM; ++mi) af[mi] = *(const bf16x8*)(as + a_off[mi][kk]);
-#pragma unroll
-                for (int ni = 0; ni < FN; ++ni) bfr[ni] = *(const bf16x8*)(bs + b_off[ni][kk]);
-#pragma unroll
-                for (int mi = 0; mi < FM; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < FN; ++ni)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mi], bfr[ni], acc[mi][ni], 0, 0, 0);
-            }
-            __syncthreads();
-        }
-
-        // ---- keys of the scores -> LDS tile (every wave is past the ring: the K loop ends in a barrier) -------------------
-#pragma unroll
-        for (int ni = 0; ni < FN; ++ni) {
-            const int nl = wn * TN + ni * 16 + (lane & 15);
-#pragma unroll
-            for (int mi = 0; mi < FM; ++mi) {
-                const int ml = wm * TM + mi * 16 + 4 * (lane >> 4);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Ks[(ml + r) * BN + nl] = tk_key(acc[mi][ni][r]);
-            }
-        }
-        __syncthreads();
+        tile.scores(smem, n0, acc);
+        tile.store(Ks, acc, [](float s) { return tk_key(s); });      // the tile holds KEYS
 
         // ---- row direction: wave w scans rows 32 w .. 32 w + 31, a lane the columns lane and lane + 64 ---------------------
         for (int rr = 0; rr < rows_here; ++rr) {

@@ -12,8 +12,8 @@
 // distinct words, so the same input gives the same bits.
 //
 // One 256-thread workgroup per row, four steps:
-//   1. SELECT.  An exact radix select over the 32-bit keys (tk_key), most significant digit first, 11 + 11 + 10 bits: a 2048-bin
-//      LDS histogram per pass (ds_add, no return), a block scan over the bins from the top, the bin holding the kk-th key
+//   1. SELECT.  An exact radix select over the 32-bit keys (search_common.h's tk_key: no column has key 0, so the word 0 is free to
+//      mean "no entry"), most significant digit first, 11 + 11 + 10 bits: a 2048-bin LDS histogram per pass (ds_add, no return), a block scan over the bins from the top, the bin holding the kk-th key
 //      (kk = min(k, eligible columns)) fixes the digit.  After three passes T is the kk-th key itself, ``need`` the number of
 //      columns with key == T that belong to the list and ``cnt`` how many such columns the row has.  Passes two and three test
 //      admissibility only for columns whose key carries the prefix, so a filter costs its id / live loads once, not per pass.
@@ -29,21 +29,9 @@
 // The row is read four times (16-byte loads when the row base is 16-byte aligned and the pitch a multiple of four floats, element
 // loads 256 columns apart otherwise; columns at or past V are never touched); at the sizes the score scratch holds it stays in the
 // Infinity Cache.  No runtime-indexed register arrays.
-#include "sc_common.h"
+#include "search_common.h"
 
 namespace {
-
-constexpr uint32_t TK_NAN = 0xffffffffu;     // above +inf (0xff800000)
-
-// topk.hip's key, copied: a < b as floats <=> key(a) < key(b); -0 and +0 share a key; every NaN is TK_NAN; -inf is 0x007fffff, so no
-// column has key 0 and the word 0 is free to mean "no entry"
-__device__ __forceinline__ uint32_t tk_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    uint32_t k = u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
-    if ((u & 0x7fffffffu) > 0x7f800000u) k = TK_NAN;
-    if (k == 0x7fffffffu) k = 0x80000000u;
-    return k;
-}
 
 constexpr int TW_THREADS = 256;
 constexpr int TW_BINS = 2048;                // 11 bits per pass (the last pass has 10: its upper 1024 bins stay zero)
