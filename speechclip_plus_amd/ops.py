@@ -887,6 +887,18 @@ def sgemm_mfma(A: torch.Tensor, Bm: torch.Tensor, a_kmajor: bool = False, b_kmaj
     return out
 
 
+def _lists_out(rows: int, k: int, dev, vals: Optional[torch.Tensor], idx: Optional[torch.Tensor]):
+    """the output pair of a selection entry, (vals [rows, k] fp32, idx [rows, k] int32): allocated on ``dev`` where None, the caller's
+    own (contiguous) checked otherwise"""
+    if vals is None:
+        vals = torch.empty(rows, k, device=dev, dtype=torch.float32)
+    if idx is None:
+        idx = torch.empty(rows, k, device=dev, dtype=torch.int32)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
+    assert tuple(vals.shape) == (rows, k) and tuple(idx.shape) == (rows, k)
+    return vals, idx
+
+
 def topk_rows(scores: torch.Tensor, V: int, k: int, vals: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None):
     """scores [rows, >= V] fp32 (unit column stride, any row pitch and base alignment) -> (vals [rows, k] fp32, idx [rows, k] int32): the
     k largest of the first V columns of every row, best first - ties to the lower column, NaN above every number, -inf / -1 behind
@@ -895,12 +907,7 @@ def topk_rows(scores: torch.Tensor, V: int, k: int, vals: Optional[torch.Tensor]
     rows = scores.shape[0]
     assert scores.shape[1] >= V, (scores.shape, V)
     ld = scores.stride(0) if rows > 1 else max(V, 1)
-    if vals is None:
-        vals = torch.empty(rows, k, device=scores.device, dtype=torch.float32)
-    if idx is None:
-        idx = torch.empty(rows, k, device=scores.device, dtype=torch.int32)
-    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
-    assert tuple(vals.shape) == (rows, k) and tuple(idx.shape) == (rows, k)
+    vals, idx = _lists_out(rows, k, scores.device, vals, idx)
     check(lib().sc_topk_rows_f32(_p(scores) if rows else ctypes.c_void_p(0), ld, rows, V, k, _p(vals) if rows else ctypes.c_void_p(0),
                                  _p(idx) if rows else ctypes.c_void_p(0), _stream()), "sc_topk_rows_f32")
     return vals, idx
@@ -919,34 +926,60 @@ def search_topk(q_split: torch.Tensor, g_split: torch.Tensor, nQ: int, N: int, k
     behind the N-th entry).  The scores are those of ``cosine_scores_split``; no [nQ, N] matrix is written.  ``slabs``: how many slabs
     the gallery axis is cut into (None: sc_search_slabs); the result does not depend on it.  More than one slab: the per-slab lists
     [nQ, S, k] are merged by ``topk_rows`` and one gather.  ``vals`` / ``idx``: caller-owned contiguous outputs."""
-    if not (q_split.is_cuda and g_split.is_cuda):
-        raise RuntimeError("search_topk runs on the HIP kernels: no CPU path")
-    assert q_split.dtype == torch.bfloat16 and g_split.dtype == torch.bfloat16 and q_split.dim() == 2 and g_split.dim() == 2
-    assert q_split.is_contiguous() and g_split.is_contiguous()
-    K6 = q_split.shape[1]
-    assert g_split.shape[1] == K6, (q_split.shape, g_split.shape)
+    return _search_lists("search_topk", q_split, g_split, nQ, N, k, slabs, vals, idx)
+
+
+def _search_operands(name: str, q: torch.Tensor, g: torch.Tensor, nQ: int, N: int) -> int:
+    """the bf16 operand pair of the scan ``name`` (``search_topk`` / ``search_coarse`` and their filtered forms), checked: contiguous
+    [>= roundup(nQ, 128), K] / [>= roundup(N, 128), K] on the device -> K"""
+    if not (q.is_cuda and g.is_cuda):
+        raise RuntimeError(f"{name} runs on the HIP kernels: no CPU path")
+    assert q.dtype == torch.bfloat16 and g.dtype == torch.bfloat16 and q.dim() == 2 and g.dim() == 2
+    assert q.is_contiguous() and g.is_contiguous()
+    K = q.shape[1]
+    assert g.shape[1] == K, (q.shape, g.shape)
+    assert q.shape[0] >= -(-nQ // 128) * 128 and g.shape[0] >= -(-N // 128) * 128, (q.shape, nQ, g.shape, N)
+    return K
+
+
+def _search_lists(name: str, q: torch.Tensor, g: torch.Tensor, nQ: int, N: int, k: int, slabs: Optional[int], vals, idx):
+    """``search_topk`` / ``search_coarse`` (``name``; the C entry is sc_<name>_bf16): the per-slab lists [nQ, S, k], merged by ``topk_rows``
+    and one gather when S > 1"""
     nQ, N, k = int(nQ), int(N), int(k)
-    assert q_split.shape[0] >= -(-nQ // 128) * 128 and g_split.shape[0] >= -(-N // 128) * 128, (q_split.shape, nQ, g_split.shape, N)
-    dev = q_split.device
-    if vals is None:
-        vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
-    if idx is None:
-        idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
-    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
-    assert tuple(vals.shape) == (nQ, k) and tuple(idx.shape) == (nQ, k)
+    K = _search_operands(name, q, g, nQ, N)
+    dev = q.device
+    vals, idx = _lists_out(nQ, k, dev, vals, idx)
     S = search_slabs(nQ, N, k) if slabs is None else int(slabs)
     if S == 1 or nQ == 0:
         pv, pi = vals, idx
     else:
         pv = torch.empty(nQ, S * k, device=dev, dtype=torch.float32)
         pi = torch.empty(nQ, S * k, device=dev, dtype=torch.int32)
-    null = ctypes.c_void_p(0)
-    check(lib().sc_search_topk_bf16(_p(q_split) if nQ else null, _p(g_split) if N else null, nQ, N, K6, k, S, _p(pv) if nQ else null,
-                                    _p(pi) if nQ else null, _stream()), "sc_search_topk_bf16")
+    null, entry = ctypes.c_void_p(0), f"sc_{name}_bf16"
+    check(getattr(lib(), entry)(_p(q) if nQ else null, _p(g) if N else null, nQ, N, K, k, S, _p(pv) if nQ else null, _p(pi) if nQ else null,
+                                _stream()), entry)
     if pv is not vals:
         _, pos = topk_rows(pv, S * k, k, vals=vals)
         torch.gather(pi, 1, pos.long(), out=idx)
     return vals, idx
+
+
+def _search_words(name: str, q: torch.Tensor, g: torch.Tensor, nQ: int, N: int, k: int, q_ids, g_ids, live, slabs: Optional[int],
+                  merge: bool, vals=None, idx=None):
+    """``search_topk_filtered`` / ``search_coarse_filtered`` (``name``; the C entry is sc_<name>_bf16): the per-slab list words
+    part [nQ, max(S, 1), k] int64 -> ``merge``: ``search_merge``'s lists of them in ``vals`` / ``idx`` (checked before the launch), else part"""
+    nQ, N, k = int(nQ), int(N), int(k)
+    K = _search_operands(name, q, g, nQ, N)
+    dev = q.device
+    q_ids, g_ids, live = filter_operands(name, nQ, N, q_ids, g_ids, live, dev)
+    if merge:
+        vals, idx = _lists_out(nQ, k, dev, vals, idx)
+    S = search_slabs(nQ, N, k) if slabs is None else int(slabs)
+    part = torch.empty(nQ, max(S, 1), k, device=dev, dtype=torch.int64)
+    null, entry = ctypes.c_void_p(0), f"sc_{name}_bf16"
+    check(getattr(lib(), entry)(_p(q) if nQ else null, _p(g) if N else null, nQ, N, K, k, S, _p(q_ids) if nQ and N else null,
+                                _p(g_ids) if nQ and N else null, _p(live) if N else null, _p(part) if nQ else null, _stream()), entry)
+    return search_merge(part, k, vals=vals, idx=idx) if merge else part
 
 
 def check_filter_tensor(name: str, what: str, t, n: int, dtypes=(torch.int64,)) -> None:
@@ -994,12 +1027,7 @@ def topk_rows_filtered(scores: torch.Tensor, V: int, k: int, q_ids: Optional[tor
     assert scores.shape[1] >= V, (scores.shape, V)
     q_ids, g_ids, live = filter_operands("topk_rows_filtered", rows, V, q_ids, g_ids, live, scores.device)
     ld = scores.stride(0) if rows > 1 else max(V, 1)
-    if vals is None:
-        vals = torch.empty(rows, k, device=scores.device, dtype=torch.float32)
-    if idx is None:
-        idx = torch.empty(rows, k, device=scores.device, dtype=torch.int32)
-    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
-    assert tuple(vals.shape) == (rows, k) and tuple(idx.shape) == (rows, k)
+    vals, idx = _lists_out(rows, k, scores.device, vals, idx)
     null = ctypes.c_void_p(0)
     check(lib().sc_topk_rows_filtered_f32(_p(scores) if rows else null, ld, rows, V, k, _p(q_ids), _p(g_ids), _p(live),
                                           _p(vals) if rows else null, _p(idx) if rows else null, _stream()), "sc_topk_rows_filtered_f32")
@@ -1059,12 +1087,7 @@ def search_merge(part: torch.Tensor, k: int, vals: Optional[torch.Tensor] = None
         raise RuntimeError("search_merge runs on the HIP kernels: no CPU path")
     assert part.dtype == torch.int64 and part.dim() == 3 and part.is_contiguous() and part.shape[2] == int(k), (part.dtype, part.shape, k)
     nQ, S, k = part.shape[0], part.shape[1], int(k)
-    if vals is None:
-        vals = torch.empty(nQ, k, device=part.device, dtype=torch.float32)
-    if idx is None:
-        idx = torch.empty(nQ, k, device=part.device, dtype=torch.int32)
-    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
-    assert tuple(vals.shape) == (nQ, k) and tuple(idx.shape) == (nQ, k)
+    vals, idx = _lists_out(nQ, k, part.device, vals, idx)
     null = ctypes.c_void_p(0)
     check(lib().sc_search_merge_u64(_p(part) if nQ else null, nQ, S, k, _p(vals) if nQ else null, _p(idx) if nQ else null, _stream()),
           "sc_search_merge_u64")
@@ -1081,29 +1104,7 @@ def search_topk_filtered(q_split: torch.Tensor, g_split: torch.Tensor, nQ: int, 
     row, and an admissible row scoring a real -inf ranks ahead of them.  ``slabs``: None = sc_search_slabs; any S >= 1 is legal here
     (a slab may hold no admissible row at all) and the result does not depend on it.  The per-slab lists [nQ, S, k] are 64-bit
     words, merged and decoded by ``search_merge``.  ``vals`` / ``idx``: caller-owned contiguous outputs."""
-    if not (q_split.is_cuda and g_split.is_cuda):
-        raise RuntimeError("search_topk_filtered runs on the HIP kernels: no CPU path")
-    assert q_split.dtype == torch.bfloat16 and g_split.dtype == torch.bfloat16 and q_split.dim() == 2 and g_split.dim() == 2
-    assert q_split.is_contiguous() and g_split.is_contiguous()
-    K6 = q_split.shape[1]
-    assert g_split.shape[1] == K6, (q_split.shape, g_split.shape)
-    nQ, N, k = int(nQ), int(N), int(k)
-    assert q_split.shape[0] >= -(-nQ // 128) * 128 and g_split.shape[0] >= -(-N // 128) * 128, (q_split.shape, nQ, g_split.shape, N)
-    dev = q_split.device
-    q_ids, g_ids, live = filter_operands("search_topk_filtered", nQ, N, q_ids, g_ids, live, dev)
-    if vals is None:
-        vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
-    if idx is None:
-        idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
-    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
-    assert tuple(vals.shape) == (nQ, k) and tuple(idx.shape) == (nQ, k)
-    S = search_slabs(nQ, N, k) if slabs is None else int(slabs)
-    part = torch.empty(nQ, max(S, 1), k, device=dev, dtype=torch.int64)
-    null = ctypes.c_void_p(0)
-    check(lib().sc_search_topk_filtered_bf16(_p(q_split) if nQ else null, _p(g_split) if N else null, nQ, N, K6, k, S,
-                                             _p(q_ids) if nQ and N else null, _p(g_ids) if nQ and N else null, _p(live) if N else null,
-                                             _p(part) if nQ else null, _stream()), "sc_search_topk_filtered_bf16")
-    return search_merge(part, k, vals=vals, idx=idx)
+    return _search_words("search_topk_filtered", q_split, g_split, nQ, N, k, q_ids, g_ids, live, slabs, True, vals, idx)
 
 
 def rows_bf16(x: torch.Tensor, row_scale: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
@@ -1133,34 +1134,7 @@ def search_coarse(q_bf16: torch.Tensor, g_bf16: torch.Tensor, nQ: int, N: int, D
     (vals [nQ, D] fp32, idx [nQ, D] int32), best first in ``topk_rows``' order (ties to the lower gallery row, NaN first, -inf / -1
     behind the N-th entry).  ``slabs``: None = sc_search_slabs(nQ, N, D); the result does not depend on it.  More than one slab: the
     per-slab lists [nQ, S, D] are merged by ``topk_rows`` and one gather, as ``search_topk`` merges them."""
-    if not (q_bf16.is_cuda and g_bf16.is_cuda):
-        raise RuntimeError("search_coarse runs on the HIP kernels: no CPU path")
-    assert q_bf16.dtype == torch.bfloat16 and g_bf16.dtype == torch.bfloat16 and q_bf16.dim() == 2 and g_bf16.dim() == 2
-    assert q_bf16.is_contiguous() and g_bf16.is_contiguous()
-    Ep = q_bf16.shape[1]
-    assert g_bf16.shape[1] == Ep, (q_bf16.shape, g_bf16.shape)
-    nQ, N, D = int(nQ), int(N), int(D)
-    assert q_bf16.shape[0] >= -(-nQ // 128) * 128 and g_bf16.shape[0] >= -(-N // 128) * 128, (q_bf16.shape, nQ, g_bf16.shape, N)
-    dev = q_bf16.device
-    if vals is None:
-        vals = torch.empty(nQ, D, device=dev, dtype=torch.float32)
-    if idx is None:
-        idx = torch.empty(nQ, D, device=dev, dtype=torch.int32)
-    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.is_contiguous() and idx.is_contiguous()
-    assert tuple(vals.shape) == (nQ, D) and tuple(idx.shape) == (nQ, D)
-    S = search_slabs(nQ, N, D) if slabs is None else int(slabs)
-    if S == 1 or nQ == 0:
-        pv, pi = vals, idx
-    else:
-        pv = torch.empty(nQ, S * D, device=dev, dtype=torch.float32)
-        pi = torch.empty(nQ, S * D, device=dev, dtype=torch.int32)
-    null = ctypes.c_void_p(0)
-    check(lib().sc_search_coarse_bf16(_p(q_bf16) if nQ else null, _p(g_bf16) if N else null, nQ, N, Ep, D, S, _p(pv) if nQ else null,
-                                      _p(pi) if nQ else null, _stream()), "sc_search_coarse_bf16")
-    if pv is not vals:
-        _, pos = topk_rows(pv, S * D, D, vals=vals)
-        torch.gather(pi, 1, pos.long(), out=idx)
-    return vals, idx
+    return _search_lists("search_coarse", q_bf16, g_bf16, nQ, N, D, slabs, vals, idx)
 
 
 def search_rerank(q: torch.Tensor, q_scale: Optional[torch.Tensor], rows: torch.Tensor, g_scale: Optional[torch.Tensor],
@@ -1171,8 +1145,13 @@ def search_rerank(q: torch.Tensor, q_scale: Optional[torch.Tensor], rows: torch.
     first, -1 = no candidate), ``eps`` [nQ] fp32 -> (vals [nQ, k] fp32, idx [nQ, k] int32, certified [nQ] uint8): the k best
     candidates by their inner product accumulated in fp64 (rows scaled in fp32 first), and 1 where no row outside the candidates can
     belong to the list: every value finite and (N <= D or e_k - |e_k| 2^-23 > cand_vals[:, D - 1] + eps)."""
+    return _search_rerank("search_rerank", q, q_scale, rows, g_scale, cand_idx, cand_vals, eps, k, vals, idx, certified)
+
+
+def _search_rerank(name: str, q, q_scale, rows, g_scale, cand_idx, cand_vals, eps, k: int, vals, idx, certified):
+    """``search_rerank`` / ``search_rerank_filtered`` (``name``; the C entry is sc_<name>_f32): the same operands, checks and outputs"""
     if not (q.is_cuda and rows.is_cuda and cand_idx.is_cuda):
-        raise RuntimeError("search_rerank runs on the HIP kernels: no CPU path")
+        raise RuntimeError(f"{name} runs on the HIP kernels: no CPU path")
     assert q.dtype == torch.float32 and rows.dtype == torch.float32 and q.dim() == 2 and rows.dim() == 2
     assert (q.stride(1) == 1 or q.shape[1] == 1) and (rows.stride(1) == 1 or rows.shape[1] == 1)
     nQ, E = q.shape
@@ -1184,20 +1163,15 @@ def search_rerank(q: torch.Tensor, q_scale: Optional[torch.Tensor], rows: torch.
     assert eps.dtype == torch.float32 and tuple(eps.shape) == (nQ,) and eps.is_contiguous()
     for s, n in ((q_scale, nQ), (g_scale, N)):
         assert s is None or (s.dtype == torch.float32 and tuple(s.shape) == (n,) and s.is_contiguous())
-    dev = q.device
-    if vals is None:
-        vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
-    if idx is None:
-        idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
+    vals, idx = _lists_out(nQ, k, q.device, vals, idx)
     if certified is None:
-        certified = torch.empty(nQ, device=dev, dtype=torch.uint8)
-    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and certified.dtype == torch.uint8
-    assert vals.is_contiguous() and idx.is_contiguous() and certified.is_contiguous()
-    assert tuple(vals.shape) == (nQ, k) and tuple(idx.shape) == (nQ, k) and tuple(certified.shape) == (nQ,)
+        certified = torch.empty(nQ, device=q.device, dtype=torch.uint8)
+    assert certified.dtype == torch.uint8 and certified.is_contiguous() and tuple(certified.shape) == (nQ,)
     if nQ:
-        check(lib().sc_search_rerank_f32(_p(q), q.stride(0) if nQ > 1 else E, _p(q_scale), _p(rows) if N else ctypes.c_void_p(0),
-                                         rows.stride(0) if N > 1 else E, _p(g_scale), _p(cand_idx), _p(cand_vals), _p(eps), nQ, N, E, D, k,
-                                         _p(vals), _p(idx), _p(certified), _stream()), "sc_search_rerank_f32")
+        entry = f"sc_{name}_f32"
+        check(getattr(lib(), entry)(_p(q), q.stride(0) if nQ > 1 else E, _p(q_scale), _p(rows) if N else ctypes.c_void_p(0),
+                                    rows.stride(0) if N > 1 else E, _p(g_scale), _p(cand_idx), _p(cand_vals), _p(eps), nQ, N, E, D, k,
+                                    _p(vals), _p(idx), _p(certified), _stream()), entry)
     return vals, idx, certified
 
 
@@ -1209,23 +1183,7 @@ def search_coarse_filtered(q_bf16: torch.Tensor, g_bf16: torch.Tensor, nQ: int, 
     ``search_coarse``'s: an admissible row carries the same fp32 bits.  -> part [nQ, S, D] int64, the per-slab list words
     (key << 32 | ~row, best first, 0 = no entry); ``search_merge(part, D)`` merges and decodes them (S = 1 included).  ``slabs``:
     None = sc_search_slabs(nQ, N, D); any S >= 1 is legal (a slab may hold no admissible row) and the merged lists do not depend on it."""
-    if not (q_bf16.is_cuda and g_bf16.is_cuda):
-        raise RuntimeError("search_coarse_filtered runs on the HIP kernels: no CPU path")
-    assert q_bf16.dtype == torch.bfloat16 and g_bf16.dtype == torch.bfloat16 and q_bf16.dim() == 2 and g_bf16.dim() == 2
-    assert q_bf16.is_contiguous() and g_bf16.is_contiguous()
-    Ep = q_bf16.shape[1]
-    assert g_bf16.shape[1] == Ep, (q_bf16.shape, g_bf16.shape)
-    nQ, N, D = int(nQ), int(N), int(D)
-    assert q_bf16.shape[0] >= -(-nQ // 128) * 128 and g_bf16.shape[0] >= -(-N // 128) * 128, (q_bf16.shape, nQ, g_bf16.shape, N)
-    dev = q_bf16.device
-    q_ids, g_ids, live = filter_operands("search_coarse_filtered", nQ, N, q_ids, g_ids, live, dev)
-    S = search_slabs(nQ, N, D) if slabs is None else int(slabs)
-    part = torch.empty(nQ, max(S, 1), D, device=dev, dtype=torch.int64)
-    null = ctypes.c_void_p(0)
-    check(lib().sc_search_coarse_filtered_bf16(_p(q_bf16) if nQ else null, _p(g_bf16) if N else null, nQ, N, Ep, D, S,
-                                               _p(q_ids) if nQ and N else null, _p(g_ids) if nQ and N else null, _p(live) if N else null,
-                                               _p(part) if nQ else null, _stream()), "sc_search_coarse_filtered_bf16")
-    return part
+    return _search_words("search_coarse_filtered", q_bf16, g_bf16, nQ, N, D, q_ids, g_ids, live, slabs, False)
 
 
 def search_rerank_filtered(q: torch.Tensor, q_scale: Optional[torch.Tensor], rows: torch.Tensor, g_scale: Optional[torch.Tensor],
@@ -1235,34 +1193,7 @@ def search_rerank_filtered(q: torch.Tensor, q_scale: Optional[torch.Tensor], row
     the same operands - ``cand_idx`` / ``cand_vals`` [nQ, D] the merged lists of ``search_coarse_filtered``, -1 = no candidate - and the
     same fp64 re-rank; certified = 1 where every value is finite and (the query has fewer than D candidates, so every admissible row
     is one, or e_k - |e_k| 2^-23 > cand_vals[:, D - 1] + eps).  ``eps`` must bound |exact - coarse| over the rows that can be admissible."""
-    if not (q.is_cuda and rows.is_cuda and cand_idx.is_cuda):
-        raise RuntimeError("search_rerank_filtered runs on the HIP kernels: no CPU path")
-    assert q.dtype == torch.float32 and rows.dtype == torch.float32 and q.dim() == 2 and rows.dim() == 2
-    assert (q.stride(1) == 1 or q.shape[1] == 1) and (rows.stride(1) == 1 or rows.shape[1] == 1)
-    nQ, E = q.shape
-    N = rows.shape[0]
-    assert rows.shape[1] == E, (q.shape, rows.shape)
-    D, k = int(cand_idx.shape[1]), int(k)
-    assert cand_idx.dtype == torch.int32 and cand_vals.dtype == torch.float32 and cand_idx.is_contiguous() and cand_vals.is_contiguous()
-    assert tuple(cand_idx.shape) == (nQ, D) and tuple(cand_vals.shape) == (nQ, D) and 1 <= k <= D <= 32, (cand_idx.shape, cand_vals.shape, k)
-    assert eps.dtype == torch.float32 and tuple(eps.shape) == (nQ,) and eps.is_contiguous()
-    for s, n in ((q_scale, nQ), (g_scale, N)):
-        assert s is None or (s.dtype == torch.float32 and tuple(s.shape) == (n,) and s.is_contiguous())
-    dev = q.device
-    if vals is None:
-        vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
-    if idx is None:
-        idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
-    if certified is None:
-        certified = torch.empty(nQ, device=dev, dtype=torch.uint8)
-    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and certified.dtype == torch.uint8
-    assert vals.is_contiguous() and idx.is_contiguous() and certified.is_contiguous()
-    assert tuple(vals.shape) == (nQ, k) and tuple(idx.shape) == (nQ, k) and tuple(certified.shape) == (nQ,)
-    if nQ:
-        check(lib().sc_search_rerank_filtered_f32(_p(q), q.stride(0) if nQ > 1 else E, _p(q_scale), _p(rows) if N else ctypes.c_void_p(0),
-                                                  rows.stride(0) if N > 1 else E, _p(g_scale), _p(cand_idx), _p(cand_vals), _p(eps), nQ, N, E,
-                                                  D, k, _p(vals), _p(idx), _p(certified), _stream()), "sc_search_rerank_filtered_f32")
-    return vals, idx, certified
+    return _search_rerank("search_rerank_filtered", q, q_scale, rows, g_scale, cand_idx, cand_vals, eps, k, vals, idx, certified)
 
 
 def _rank_key_value(key: torch.Tensor) -> torch.Tensor:

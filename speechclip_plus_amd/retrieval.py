@@ -61,6 +61,11 @@ def mutualRetrieval(score_per_A: torch.Tensor, score_per_B: torch.Tensor, AB_ans
 _INDEX_CHUNK_ROWS = 16384          # gallery / query rows split per pass (a multiple of 128)
 
 
+def _up128(x: int) -> int:
+    """x rounded up to the kernels' 128-row tile"""
+    return -(-x // 128) * 128
+
+
 def _rows_f32(x: torch.Tensor) -> torch.Tensor:
     """fp32 rows with unit column stride (any row pitch: the split kernel takes one)"""
     x = x.detach().float()
@@ -71,9 +76,18 @@ def _split_rows(x: torch.Tensor, side: int, cosine: bool, out: torch.Tensor) -> 
     """x [R, E] fp32 -> out[: roundup(R, 128)] = its three-way bf16 split (ops.split3_bf16); ``cosine``: rows scaled by
     1 / max(|x|, 1e-8) (ops.vq_prep's rnorm as the split's row_scale)."""
     from . import ops
-    R = x.shape[0]
     rnorm = ops.vq_prep(x)[1] if cosine else None
-    ops.split3_bf16(x, side, row_scale=rnorm, out=out[: -(-R // 128) * 128])
+    ops.split3_bf16(x, side, row_scale=rnorm, out=out[: _up128(x.shape[0])])
+
+
+def _split_in_chunks(x: torch.Tensor, side: int, cosine: bool) -> torch.Tensor:
+    """x [R, E] -> its split [roundup(R, 128), 6 Ep] bf16 (``_split_rows``), made in chunks of ``_INDEX_CHUNK_ROWS`` rows so that no second
+    fp32 copy of a large ``x`` exists"""
+    R, E = x.shape
+    out = torch.empty(_up128(R), 6 * -(-E // 64) * 64, device=x.device, dtype=torch.bfloat16)
+    for r0 in range(0, R, _INDEX_CHUNK_ROWS):
+        _split_rows(_rows_f32(x[r0: r0 + _INDEX_CHUNK_ROWS]), side, cosine, out[r0:])
+    return out
 
 
 FUSED_MIN_GALLERY = 131072
@@ -90,6 +104,25 @@ def default_route(nQ: int, N: int) -> str:
 class _LiveRows:
     """``live`` / ``remove`` / ``restore`` / ``n_live`` of a built index (GalleryIndex, CompactGalleryIndex): the rows' data is never
     touched, ``live`` is None (every row takes part) or a bool [N] device tensor changed in place"""
+
+    def _init_rows(self, gallery: torch.Tensor, cosine: bool, ids: Optional[torch.Tensor]) -> None:
+        """the constructors' checks of ``gallery`` [N, E] and ``ids`` [N], under the class's own name -> N, E, Ep, ids, live, cosine"""
+        name = type(self).__name__
+        if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2:
+            raise ValueError(f"{name}: gallery must be a [N, E] tensor")
+        if not gallery.is_cuda:
+            raise RuntimeError(f"{name} runs on the HIP kernels: device tensors only")
+        self.N, self.E = int(gallery.shape[0]), int(gallery.shape[1])
+        assert self.E >= 1, gallery.shape
+        if ids is not None:
+            from . import ops
+            ops.filter_operands(name, self.N, self.N, ids, ids, None, gallery.device, names=("ids", "ids", "live"))
+        self.ids, self.live = ids, None
+        self.cosine = bool(cosine)
+        self.Ep = -(-self.E // 64) * 64
+
+    def __len__(self) -> int:
+        return self.N
 
     def _rows_arg(self, rows) -> torch.Tensor:
         """row numbers (a tensor or a sequence of ints) -> int64 on the index's device, every one inside [0, N)"""
@@ -139,29 +172,12 @@ class GalleryIndex(_LiveRows):
     (a NaN row, a withdrawn item) costs one small copy, and ``search`` skips them.  ``n_live`` counts the rows that take part."""
 
     def __init__(self, gallery: torch.Tensor, cosine: bool = False, ids: Optional[torch.Tensor] = None):
-        if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2:
-            raise ValueError("GalleryIndex: gallery must be a [N, E] tensor")
-        if not gallery.is_cuda:
-            raise RuntimeError("GalleryIndex runs on the HIP kernels: device tensors only")
-        self.N, self.E = int(gallery.shape[0]), int(gallery.shape[1])
-        assert self.E >= 1, gallery.shape
-        if ids is not None:
-            from . import ops
-            ops.filter_operands("GalleryIndex", self.N, self.N, ids, ids, None, gallery.device, names=("ids", "ids", "live"))
-        self.ids, self.live = ids, None
-        self.cosine = bool(cosine)
-        self.Ep = -(-self.E // 64) * 64
-        self.split = torch.empty(-(-self.N // 128) * 128, 6 * self.Ep, device=gallery.device, dtype=torch.bfloat16)
-        for r0 in range(0, self.N, _INDEX_CHUNK_ROWS):
-            r1 = min(self.N, r0 + _INDEX_CHUNK_ROWS)
-            _split_rows(_rows_f32(gallery[r0:r1]), 1, self.cosine, self.split[r0:])
+        self._init_rows(gallery, cosine, ids)
+        self.split = _split_in_chunks(gallery, 1, self.cosine)
 
     @property
     def device(self) -> torch.device:
         return self.split.device
-
-    def __len__(self) -> int:
-        return self.N
 
 
 def _search_filter(queries: torch.Tensor, gallery, query_ids, gallery_ids, live, name: str = "search"):
@@ -211,10 +227,14 @@ def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex, "Co
     ``default_route`` picks as before.  Without ids and without a live mask the call runs exactly the unfiltered code.  A
     CompactGalleryIndex with any filter ARGUMENT is a ValueError: the filtered compact call returns its certificate, so it is
     ``search_compact``'s; without filter arguments the index's own removed rows are honoured."""
-    from . import ops
-    if int(k) > 32:                                   # the wide selection (below); everything from here on is the k <= 32 code, unchanged
-        return _search_wide(queries, gallery, int(k), cosine, slabs, route, query_ids, gallery_ids, live)
+    k = int(k)
+    wide = k > 32                                     # the wide selection: the composition route's scores, ops.topk_rows_wide
+    if k > WIDE_MAX_K:
+        raise ValueError(f"search: 1 <= k <= {WIDE_MAX_K} (k {k})")
     if isinstance(gallery, CompactGalleryIndex):      # the compact route (below): exact lists through the certificate and its fallback
+        if wide:
+            raise ValueError(f"search: k = {k} on a CompactGalleryIndex - its certificate is built on at most 32 candidates per query "
+                             "(k <= depth <= 32); build a GalleryIndex of the gallery for 32 < k <= 1024")
         if query_ids is not None or gallery_ids is not None or live is not None:
             raise ValueError("search: a CompactGalleryIndex takes no filter arguments here - the filtered call returns its certificate "
                              "(restated over the admissible rows), so it is search_compact(queries, index, k, query_ids=..., "
@@ -222,89 +242,37 @@ def search(queries: torch.Tensor, gallery: Union[torch.Tensor, GalleryIndex, "Co
         if route is not None:
             raise ValueError("search: route applies to a GalleryIndex or a tensor, not to a CompactGalleryIndex")
         return search_compact(queries, gallery, k, cosine=cosine, slabs=slabs)[:2]
+    if wide and (route == "fused" or slabs is not None):
+        raise ValueError(f"search: k = {k} with route=\"fused\" / slabs= - the fused kernel keeps at most 32 gallery rows per query; "
+                         "32 < k <= 1024 runs the composition route (route=None or \"composition\")")
+    if wide and route not in (None, "composition"):
+        raise ValueError(f"search: route = {route!r} (\"fused\" or \"composition\")")
     if not isinstance(queries, torch.Tensor) or queries.dim() != 2:
         raise ValueError("search: queries must be a [nQ, E] tensor")
-    if query_ids is not None or gallery_ids is not None or live is not None or (isinstance(gallery, GalleryIndex) and gallery.live is not None):
-        if not isinstance(gallery, (torch.Tensor, GalleryIndex)) or (isinstance(gallery, torch.Tensor) and gallery.dim() != 2):
-            raise ValueError("search: gallery must be a [N, E] tensor or a GalleryIndex")
+    own = isinstance(gallery, GalleryIndex)
+    filtered = query_ids is not None or gallery_ids is not None or live is not None or (own and gallery.live is not None)
+    if (wide or filtered) and not own and not (isinstance(gallery, torch.Tensor) and gallery.dim() == 2):
+        raise ValueError("search: gallery must be a [N, E] tensor or a GalleryIndex")
+    if filtered:                                      # format errors come before device errors
         query_ids, gallery_ids, live = _search_filter(queries, gallery, query_ids, gallery_ids, live)
-    g_cuda = gallery.split.is_cuda if isinstance(gallery, GalleryIndex) else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
+    g_cuda = gallery.split.is_cuda if own else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
     if not queries.is_cuda or not g_cuda:
         raise RuntimeError("search runs on the HIP kernels: device tensors only")
-    index = gallery if isinstance(gallery, GalleryIndex) else GalleryIndex(gallery, cosine=cosine)
-    nQ, E = queries.shape
-    assert E == index.E, (queries.shape, index.E)
-    k = int(k)
+    N = gallery.N if own else int(gallery.shape[0])
+    if wide and N > wide_max_gallery():
+        raise ValueError(f"search: k = {k} against {N} gallery rows - 128 query rows of scores no longer fit the score scratch; "
+                         f"32 < k <= {WIDE_MAX_K} serves at most N = {wide_max_gallery()} gallery rows (k <= 32 has no such limit)")
+    index = gallery if own else GalleryIndex(gallery, cosine=cosine)
+    assert queries.shape[1] == index.E, (queries.shape, index.E)
     if not 1 <= k <= WIDE_MAX_K:
         raise ValueError(f"search: 1 <= k <= {WIDE_MAX_K} (k {k})")
-    dev = queries.device
-    if query_ids is not None or live is not None:
-        return _search_filtered(queries, index, k, cosine, slabs, route, query_ids, gallery_ids, live)
-    vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
-    idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
-    if route is None:
-        route = "fused" if slabs is not None else default_route(nQ, index.N)
+    if wide:                                          # ``default_route`` is not consulted
+        route = "composition"
+    elif route is None:
+        route = "fused" if slabs is not None else default_route(queries.shape[0], index.N)
     if route not in ("fused", "composition"):
         raise ValueError(f"search: route = {route!r} (\"fused\" or \"composition\")")
-    if nQ > 0:
-        q = _rows_f32(queries)
-        if route == "composition" and index.N > 0:
-            from .keyword_neighbors import default_chunk_rows
-            chunk = min(default_chunk_rows(index.N), -(-nQ // 128) * 128)
-            scores = torch.empty(chunk, index.split.shape[0], device=dev, dtype=torch.float32)   # the one score scratch of the call
-        else:
-            chunk = min(_INDEX_CHUNK_ROWS, -(-nQ // 128) * 128)
-            scores = None
-        split = torch.empty(chunk, 6 * index.Ep, device=dev, dtype=torch.bfloat16)       # the one query-split buffer of the call
-        for r0 in range(0, nQ, chunk):
-            r1 = min(nQ, r0 + chunk)
-            if scores is None:
-                _split_rows(q[r0:r1], 0, cosine, split)
-                ops.search_topk(split, index.split, r1 - r0, index.N, k, slabs=slabs, vals=vals[r0:r1], idx=idx[r0:r1])
-            else:
-                rp = -(-(r1 - r0) // 128) * 128
-                rnorm = ops.vq_prep(q[r0:r1])[1] if cosine else None
-                ops.cosine_scores_split(q[r0:r1], rnorm, index.split, index.split.shape[0], out=scores[:rp], split_out=split[:rp])
-                ops.topk_rows(scores[: r1 - r0], index.N, k, vals=vals[r0:r1], idx=idx[r0:r1])
-    return vals, idx.long()
-
-
-def _search_filtered(queries: torch.Tensor, index: GalleryIndex, k: int, cosine: bool, slabs: Optional[int], route: Optional[str],
-                     query_ids: Optional[torch.Tensor], gallery_ids: Optional[torch.Tensor], live: Optional[torch.Tensor]):
-    """``search`` with a filter: the same chunking, buffers and score kernels, the selection by csrc/search_filter.hip (a loop of its
-    own, so that the unfiltered one above stays exactly as it was)"""
-    from . import ops
-    nQ, dev = queries.shape[0], queries.device
-    vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
-    idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
-    if route is None:
-        route = "fused" if slabs is not None else default_route(nQ, index.N)
-    if route not in ("fused", "composition"):
-        raise ValueError(f"search: route = {route!r} (\"fused\" or \"composition\")")
-    if nQ > 0:
-        q = _rows_f32(queries)
-        if route == "composition" and index.N > 0:
-            from .keyword_neighbors import default_chunk_rows
-            chunk = min(default_chunk_rows(index.N), -(-nQ // 128) * 128)
-            scores = torch.empty(chunk, index.split.shape[0], device=dev, dtype=torch.float32)   # the one score scratch of the call
-        else:
-            chunk = min(_INDEX_CHUNK_ROWS, -(-nQ // 128) * 128)
-            scores = None
-        split = torch.empty(chunk, 6 * index.Ep, device=dev, dtype=torch.bfloat16)       # the one query-split buffer of the call
-        for r0 in range(0, nQ, chunk):
-            r1 = min(nQ, r0 + chunk)
-            qi = None if query_ids is None else query_ids[r0:r1]
-            if scores is None:
-                _split_rows(q[r0:r1], 0, cosine, split)
-                ops.search_topk_filtered(split, index.split, r1 - r0, index.N, k, q_ids=qi, g_ids=gallery_ids, live=live, slabs=slabs,
-                                         vals=vals[r0:r1], idx=idx[r0:r1])
-            else:
-                rp = -(-(r1 - r0) // 128) * 128
-                rnorm = ops.vq_prep(q[r0:r1])[1] if cosine else None
-                ops.cosine_scores_split(q[r0:r1], rnorm, index.split, index.split.shape[0], out=scores[:rp], split_out=split[:rp])
-                ops.topk_rows_filtered(scores[: r1 - r0], index.N, k, q_ids=qi, g_ids=gallery_ids, live=live, vals=vals[r0:r1],
-                                       idx=idx[r0:r1])
-    return vals, idx.long()
+    return _search_chunks(queries, index, k, cosine, slabs, route, query_ids, gallery_ids, live)
 
 
 WIDE_MAX_K = 1024                  # csrc/topk_wide.hip sorts the list in 8 KiB of LDS
@@ -317,57 +285,44 @@ def wide_max_gallery() -> int:
     return SCORE_SCRATCH_BYTES // (4 * 128) // 128 * 128
 
 
-def _search_wide(queries: torch.Tensor, gallery, k: int, cosine: bool, slabs: Optional[int], route: Optional[str],
-                 query_ids: Optional[torch.Tensor], gallery_ids: Optional[torch.Tensor], live: Optional[torch.Tensor]):
-    """``search`` for 32 < k <= 1024: the composition route's chunks, buffers and score kernel (ops.cosine_scores_split into the one
-    score scratch), the selection by csrc/topk_wide.hip, with or without a filter (a loop of its own, so that the k <= 32 code stays
-    exactly as it was).  Format errors come before device errors."""
+def _search_chunks(queries: torch.Tensor, index: GalleryIndex, k: int, cosine: bool, slabs: Optional[int], route: str,
+                   query_ids: Optional[torch.Tensor], gallery_ids: Optional[torch.Tensor], live: Optional[torch.Tensor]):
+    """``search`` on checked operands: the queries in chunks of rows through one query-split buffer and, on the composition route, one
+    score scratch.  The selection is the fused kernel's (ops.search_topk, with a filter ops.search_topk_filtered) or, on the scores
+    of ops.cosine_scores_split, ops.topk_rows / ops.topk_rows_filtered / (k > 32) ops.topk_rows_wide."""
     from . import ops
-    if k > WIDE_MAX_K:
-        raise ValueError(f"search: 1 <= k <= {WIDE_MAX_K} (k {k})")
-    if isinstance(gallery, CompactGalleryIndex):
-        raise ValueError(f"search: k = {k} on a CompactGalleryIndex - its certificate is built on at most 32 candidates per query "
-                         "(k <= depth <= 32); build a GalleryIndex of the gallery for 32 < k <= 1024")
-    if route == "fused" or slabs is not None:
-        raise ValueError(f"search: k = {k} with route=\"fused\" / slabs= - the fused kernel keeps at most 32 gallery rows per query; "
-                         "32 < k <= 1024 runs the composition route (route=None or \"composition\")")
-    if route not in (None, "composition"):
-        raise ValueError(f"search: route = {route!r} (\"fused\" or \"composition\")")
-    if not isinstance(queries, torch.Tensor) or queries.dim() != 2:
-        raise ValueError("search: queries must be a [nQ, E] tensor")
-    if not isinstance(gallery, (torch.Tensor, GalleryIndex)) or (isinstance(gallery, torch.Tensor) and gallery.dim() != 2):
-        raise ValueError("search: gallery must be a [N, E] tensor or a GalleryIndex")
-    if query_ids is not None or gallery_ids is not None or live is not None or (isinstance(gallery, GalleryIndex) and gallery.live is not None):
-        query_ids, gallery_ids, live = _search_filter(queries, gallery, query_ids, gallery_ids, live)
-    g_cuda = gallery.split.is_cuda if isinstance(gallery, GalleryIndex) else gallery.is_cuda
-    if not queries.is_cuda or not g_cuda:
-        raise RuntimeError("search runs on the HIP kernels: device tensors only")
-    N = gallery.N if isinstance(gallery, GalleryIndex) else int(gallery.shape[0])
-    if N > wide_max_gallery():
-        raise ValueError(f"search: k = {k} against {N} gallery rows - 128 query rows of scores no longer fit the score scratch; "
-                         f"32 < k <= {WIDE_MAX_K} serves at most N = {wide_max_gallery()} gallery rows (k <= 32 has no such limit)")
-    index = gallery if isinstance(gallery, GalleryIndex) else GalleryIndex(gallery, cosine=cosine)
-    nQ, E = queries.shape
-    assert E == index.E, (queries.shape, index.E)
-    dev = queries.device
+    nQ, N, dev = queries.shape[0], index.N, queries.device
+    wide, filtered = k > 32, query_ids is not None or live is not None
     vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
     idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
-    if nQ > 0 and N == 0:                                                 # no gallery row: fillers only (nothing to score)
+    if wide and nQ > 0 and N == 0:                                        # no gallery row: fillers only (nothing to score)
         vals.fill_(float("-inf"))
         idx.fill_(-1)
     elif nQ > 0:
-        from .keyword_neighbors import default_chunk_rows
         q = _rows_f32(queries)
-        chunk = min(default_chunk_rows(N), -(-nQ // 128) * 128)
-        scores = torch.empty(chunk, index.split.shape[0], device=dev, dtype=torch.float32)       # the one score scratch of the call
-        split = torch.empty(chunk, 6 * index.Ep, device=dev, dtype=torch.bfloat16)           # the one query-split buffer of the call
+        if route == "composition" and N > 0:
+            from .keyword_neighbors import default_chunk_rows
+            chunk = min(default_chunk_rows(N), _up128(nQ))
+            scores = torch.empty(chunk, index.split.shape[0], device=dev, dtype=torch.float32)   # the one score scratch of the call
+        else:
+            chunk = min(_INDEX_CHUNK_ROWS, _up128(nQ))
+            scores = None
+        split = torch.empty(chunk, 6 * index.Ep, device=dev, dtype=torch.bfloat16)       # the one query-split buffer of the call
         for r0 in range(0, nQ, chunk):
             r1 = min(nQ, r0 + chunk)
-            rp = -(-(r1 - r0) // 128) * 128
-            rnorm = ops.vq_prep(q[r0:r1])[1] if cosine else None
-            ops.cosine_scores_split(q[r0:r1], rnorm, index.split, index.split.shape[0], out=scores[:rp], split_out=split[:rp])
-            ops.topk_rows_wide(scores[: r1 - r0], N, k, q_ids=None if query_ids is None else query_ids[r0:r1], g_ids=gallery_ids,
-                               live=live, vals=vals[r0:r1], idx=idx[r0:r1])
+            out = {"vals": vals[r0:r1], "idx": idx[r0:r1]}
+            if filtered or wide:
+                out.update(q_ids=None if query_ids is None else query_ids[r0:r1], g_ids=gallery_ids, live=live)
+            if scores is None:
+                _split_rows(q[r0:r1], 0, cosine, split)
+                select = ops.search_topk_filtered if filtered else ops.search_topk
+                select(split, index.split, r1 - r0, N, k, slabs=slabs, **out)
+            else:
+                rp = _up128(r1 - r0)
+                rnorm = ops.vq_prep(q[r0:r1])[1] if cosine else None
+                ops.cosine_scores_split(q[r0:r1], rnorm, index.split, index.split.shape[0], out=scores[:rp], split_out=split[:rp])
+                select = ops.topk_rows_wide if wide else ops.topk_rows_filtered if filtered else ops.topk_rows
+                select(scores[: r1 - r0], N, k, **out)
     return vals, idx.long()
 
 
@@ -427,20 +382,11 @@ class CompactGalleryIndex(_LiveRows):
 
     def __init__(self, gallery: torch.Tensor, cosine: bool = False, ids: Optional[torch.Tensor] = None):
         from . import ops
-        if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2:
-            raise ValueError("CompactGalleryIndex: gallery must be a [N, E] tensor")
-        if not gallery.is_cuda:
-            raise RuntimeError("CompactGalleryIndex runs on the HIP kernels: device tensors only")
-        self.N, self.E = int(gallery.shape[0]), int(gallery.shape[1])
-        assert self.E >= 1, gallery.shape
-        if ids is not None:
-            ops.filter_operands("CompactGalleryIndex", self.N, self.N, ids, ids, None, gallery.device, names=("ids", "ids", "live"))
-        self.ids, self.live, self.norms = ids, None, None
-        self.cosine = bool(cosine)
-        self.Ep = -(-self.E // 64) * 64
+        self._init_rows(gallery, cosine, ids)
+        self.norms = None
         self.rows = _rows_f32(gallery)
         held = self.rows.data_ptr() == gallery.data_ptr() and gallery.dtype == torch.float32
-        self.coarse = torch.empty(-(-self.N // 128) * 128, self.Ep, device=gallery.device, dtype=torch.bfloat16)
+        self.coarse = torch.empty(_up128(self.N), self.Ep, device=gallery.device, dtype=torch.bfloat16)
         self.rnorm = torch.empty(self.N, device=gallery.device, dtype=torch.float32) if self.cosine else None
         top = torch.zeros(3, device=gallery.device, dtype=torch.float32)
         for r0 in range(0, self.N, _INDEX_CHUNK_ROWS):
@@ -450,7 +396,7 @@ class CompactGalleryIndex(_LiveRows):
             if self.cosine:
                 self.rnorm[r0:r1] = ops.vq_prep(x)[1]
                 scale = self.rnorm[r0:r1]
-            _, norms = ops.rows_bf16(x, scale, out=self.coarse[r0: r0 + -(-(r1 - r0) // 128) * 128])
+            _, norms = ops.rows_bf16(x, scale, out=self.coarse[r0: r0 + _up128(r1 - r0)])
             top = torch.maximum(top, norms.amax(dim=1))               # amax / maximum carry a NaN on
         self._top_all = tuple(float(v) for v in top.tolist())         # the bounds over the whole gallery: what restore() brings back
         self.gmax, self.gtmax, self.dmax = self._top_all
@@ -460,20 +406,17 @@ class CompactGalleryIndex(_LiveRows):
     def device(self) -> torch.device:
         return self.coarse.device
 
-    def __len__(self) -> int:
-        return self.N
-
     def _row_norms(self) -> torch.Tensor:
         """``norms`` [3, N] fp32, computed on first use: ``ops.rows_bf16`` over the fp32 rows again, in the constructor's chunks and
         with its scales (the same bits the constructor's maxima were taken from), the bf16 images going to a scratch buffer"""
         if self.norms is None:
             from . import ops
             norms = torch.empty(3, self.N, device=self.device, dtype=torch.float32)
-            scratch = torch.empty(min(-(-self.N // 128) * 128, _INDEX_CHUNK_ROWS), self.Ep, device=self.device, dtype=torch.bfloat16)
+            scratch = torch.empty(min(_up128(self.N), _INDEX_CHUNK_ROWS), self.Ep, device=self.device, dtype=torch.bfloat16)
             for r0 in range(0, self.N, _INDEX_CHUNK_ROWS):
                 r1 = min(self.N, r0 + _INDEX_CHUNK_ROWS)
                 scale = self.rnorm[r0:r1] if self.cosine else None
-                norms[:, r0:r1] = ops.rows_bf16(self.rows[r0:r1], scale, out=scratch[: -(-(r1 - r0) // 128) * 128])[1]
+                norms[:, r0:r1] = ops.rows_bf16(self.rows[r0:r1], scale, out=scratch[: _up128(r1 - r0)])[1]
             self.norms = norms
             self.nbytes += norms.numel() * 4
         return self.norms
@@ -493,37 +436,15 @@ class CompactGalleryIndex(_LiveRows):
         self.gmax, self.gtmax, self.dmax = self._bounds(self.live)
 
 
-def _exact_fallback(q: torch.Tensor, index: CompactGalleryIndex, k: int, cosine: bool):
+def _exact_fallback(q: torch.Tensor, index: CompactGalleryIndex, k: int, cosine: bool, query_ids: Optional[torch.Tensor] = None,
+                    gallery_ids: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None):
     """q [nU, E] fp32 -> (vals [nU, k] fp32, idx [nU, k] int32) by ``search`` against the fp32 rows, the gallery in chunks of
-    ``_FALLBACK_CHUNK_ROWS`` rows (a temporary GalleryIndex each), the per-chunk lists merged in index order and the k survivors
-    re-scored by ``ops.search_rerank``"""
-    from . import ops
-    nU, dev = q.shape[0], q.device
-    pv, pi = [], []
-    for c0 in range(0, max(index.N, 1), _FALLBACK_CHUNK_ROWS):
-        c1 = min(index.N, c0 + _FALLBACK_CHUNK_ROWS)
-        v, i = search(q, GalleryIndex(index.rows[c0:c1], cosine=index.cosine), k, cosine=cosine)
-        pv.append(v)
-        pi.append(torch.where(i >= 0, i + c0, i))
-    if len(pv) == 1:
-        cv, ci = pv[0], pi[0].int()
-    else:      # chunk order is index order and only the last chunk can end in fillers: position order keeps the tie rule
-        allv, alli = torch.cat(pv, dim=1), torch.cat(pi, dim=1)
-        cv, pos = ops.topk_rows(allv, allv.shape[1], k)
-        ci = torch.gather(alli, 1, pos.long()).int()
-    q_scale = ops.vq_prep(q)[1] if cosine else None
-    vals, idx, _ = ops.search_rerank(q, q_scale, index.rows, index.rnorm, ci.contiguous(), cv.contiguous(),
-                                     torch.zeros(nU, device=dev, dtype=torch.float32), k)
-    return vals, idx
-
-
-def _exact_fallback_filtered(q: torch.Tensor, index: CompactGalleryIndex, k: int, cosine: bool, query_ids: Optional[torch.Tensor],
-                             gallery_ids: Optional[torch.Tensor], live: Optional[torch.Tensor]):
-    """``_exact_fallback`` over the admissible rows: the filtered ``search`` on every gallery chunk (``gallery_ids`` / ``live`` sliced
-    per chunk, ``query_ids`` [nU] the uncertified queries' own), the per-chunk lists merged and the k survivors re-scored.  With a
-    filter ANY chunk can end in fillers, so they are moved behind every entry first (a stable sort on one bit: the entries keep
-    their chunk order, which is index order); ``ops.topk_rows`` then breaks a tie by position - equal scores keep the lower gallery row
-    first, and a real -inf, an entry, stands ahead of every filler."""
+    ``_FALLBACK_CHUNK_ROWS`` rows (a temporary GalleryIndex each; ``gallery_ids`` / ``live`` sliced per chunk, ``query_ids`` [nU] the
+    uncertified queries' own), the per-chunk lists merged in index order and the k survivors re-scored by ``ops.search_rerank``.
+    Without a filter only the last chunk can end in fillers, so position order keeps the tie rule.  With a filter ANY chunk can, so
+    the fillers are moved behind every entry first (a stable sort on one bit: the entries keep their chunk order, which is index
+    order); ``ops.topk_rows`` then breaks a tie by position - equal scores keep the lower gallery row first, and a real -inf, an
+    entry, stands ahead of every filler."""
     from . import ops
     nU, dev = q.shape[0], q.device
     pv, pi = [], []
@@ -537,53 +458,15 @@ def _exact_fallback_filtered(q: torch.Tensor, index: CompactGalleryIndex, k: int
         cv, ci = pv[0], pi[0].int()
     else:
         allv, alli = torch.cat(pv, dim=1), torch.cat(pi, dim=1)
-        _, order = torch.sort((alli < 0).to(torch.int8), dim=1, stable=True)
-        allv, alli = torch.gather(allv, 1, order), torch.gather(alli, 1, order)
+        if query_ids is not None or live is not None:
+            _, order = torch.sort((alli < 0).to(torch.int8), dim=1, stable=True)
+            allv, alli = torch.gather(allv, 1, order), torch.gather(alli, 1, order)
         cv, pos = ops.topk_rows(allv, allv.shape[1], k)
         ci = torch.gather(alli, 1, pos.long()).int()
     q_scale = ops.vq_prep(q)[1] if cosine else None
     vals, idx, _ = ops.search_rerank(q, q_scale, index.rows, index.rnorm, ci.contiguous(), cv.contiguous(),
                                      torch.zeros(nU, device=dev, dtype=torch.float32), k)
     return vals, idx
-
-
-def _search_compact_filtered(queries: torch.Tensor, index: CompactGalleryIndex, k: int, cosine: bool, D: int, fallback: str,
-                             slabs: Optional[int], query_ids: Optional[torch.Tensor], gallery_ids: Optional[torch.Tensor],
-                             live: Optional[torch.Tensor], bounds: Tuple[float, float, float]):
-    """``search_compact`` with a filter: the same chunking and buffers, the candidates by csrc/search_compact_filter.hip (a loop of its
-    own, so that the unfiltered one stays exactly as it was).  ``live``: the effective mask (uint8) or None; ``bounds``: gmax / gtmax /
-    dmax over its rows."""
-    from . import ops
-    nQ, dev = queries.shape[0], queries.device
-    vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
-    idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
-    cert = torch.empty(nQ, device=dev, dtype=torch.uint8)
-    if nQ == 0:
-        return vals, idx.long(), cert.bool()
-    q = _rows_f32(queries)
-    S = None if slabs is None else max(int(slabs), 1)                 # any number of slabs is legal here: an empty one writes no entry
-    chunk = min(_INDEX_CHUNK_ROWS, -(-nQ // 128) * 128)
-    qbuf = torch.empty(chunk, index.Ep, device=dev, dtype=torch.bfloat16)                # the one query buffer of the call
-    for r0 in range(0, nQ, chunk):
-        r1 = min(nQ, r0 + chunk)
-        qc = q[r0:r1]
-        q_scale = ops.vq_prep(qc)[1] if cosine else None
-        q16, norms = ops.rows_bf16(qc, q_scale, out=qbuf[: -(-(r1 - r0) // 128) * 128])
-        eps = compact_eps(norms, *bounds, index.Ep).float()
-        part = ops.search_coarse_filtered(q16, index.coarse, r1 - r0, index.N, D, q_ids=None if query_ids is None else query_ids[r0:r1],
-                                          g_ids=gallery_ids, live=live, slabs=S)
-        cv, ci = ops.search_merge(part, D)
-        ops.search_rerank_filtered(qc, q_scale, index.rows, index.rnorm, ci, cv, eps, k, vals=vals[r0:r1], idx=idx[r0:r1],
-                                   certified=cert[r0:r1])
-    cert = cert.bool()
-    if fallback == "exact":
-        todo = torch.nonzero(~cert).squeeze(1)                        # the host reads the mask here
-        if todo.numel():
-            fv, fi = _exact_fallback_filtered(q[todo].contiguous(), index, k, cosine, None if query_ids is None else query_ids[todo],
-                                              gallery_ids, live)
-            vals[todo] = fv
-            idx[todo] = fi
-    return vals, idx.long(), cert
 
 
 def search_compact(queries: torch.Tensor, gallery: Union[torch.Tensor, CompactGalleryIndex], k: int, cosine: bool = False, depth: int = 32,
@@ -622,10 +505,10 @@ def search_compact(queries: torch.Tensor, gallery: Union[torch.Tensor, CompactGa
         raise ValueError("search_compact: queries must be a [nQ, E] tensor")
     own = isinstance(gallery, CompactGalleryIndex)
     filtered = query_ids is not None or gallery_ids is not None or live is not None or (own and gallery.live is not None)
+    call_live = live
     if filtered:
         if not own and not (isinstance(gallery, torch.Tensor) and gallery.dim() == 2):
             raise ValueError("search_compact: gallery must be a [N, E] tensor or a CompactGalleryIndex")
-        call_live = live
         query_ids, gallery_ids, live = _search_filter(queries, gallery, query_ids, gallery_ids, live, name="search_compact")
     g_cuda = gallery.coarse.is_cuda if own else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
     if not queries.is_cuda or not g_cuda:
@@ -637,14 +520,11 @@ def search_compact(queries: torch.Tensor, gallery: Union[torch.Tensor, CompactGa
     assert E == index.E, (queries.shape, index.E)
     k, D = int(k), int(depth)
     assert 1 <= k <= D <= 32, f"k = {k}, depth = {D}: 1 <= k <= depth <= 32"
-    if filtered:
-        if call_live is None:
-            bounds = (index.gmax, index.gtmax, index.dmax)            # the index's own mask (or none): its bounds are kept up to date
-        else:
-            if index.live is not None:
-                live = ((live != 0) & index.live).view(torch.uint8)
-            bounds = index._bounds(live)
-        return _search_compact_filtered(queries, index, k, cosine, D, fallback, slabs, query_ids, gallery_ids, live, bounds)
+    bounds = (index.gmax, index.gtmax, index.dmax)                    # the index's own mask (or none): its bounds are kept up to date
+    if call_live is not None:                                         # a mask of the call: the effective mask (uint8) and its bounds
+        if index.live is not None:
+            live = ((live != 0) & index.live).view(torch.uint8)
+        bounds = index._bounds(live)
     dev = queries.device
     vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
     idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
@@ -652,24 +532,33 @@ def search_compact(queries: torch.Tensor, gallery: Union[torch.Tensor, CompactGa
     if nQ == 0:
         return vals, idx.long(), cert.bool()
     q = _rows_f32(queries)
-    if slabs is not None:      # at most ``slabs`` slabs of whole column tiles, none of them empty (sc_search_slabs' rule)
+    if slabs is not None and filtered:                                # any number of slabs is legal: an empty one writes no entry
+        slabs = max(int(slabs), 1)
+    elif slabs is not None:    # at most ``slabs`` slabs of whole column tiles, none of them empty (sc_search_slabs' rule)
         nT = max(-(-index.N // 128), 1)
         slabs = -(-nT // -(-nT // max(min(int(slabs), nT), 1)))
-    chunk = min(_INDEX_CHUNK_ROWS, -(-nQ // 128) * 128)
+    chunk = min(_INDEX_CHUNK_ROWS, _up128(nQ))
     qbuf = torch.empty(chunk, index.Ep, device=dev, dtype=torch.bfloat16)                # the one query buffer of the call
     for r0 in range(0, nQ, chunk):
         r1 = min(nQ, r0 + chunk)
         qc = q[r0:r1]
         q_scale = ops.vq_prep(qc)[1] if cosine else None
-        q16, norms = ops.rows_bf16(qc, q_scale, out=qbuf[: -(-(r1 - r0) // 128) * 128])
-        eps = compact_eps(norms, index.gmax, index.gtmax, index.dmax, index.Ep).float()
-        cv, ci = ops.search_coarse(q16, index.coarse, r1 - r0, index.N, D, slabs=slabs)
-        ops.search_rerank(qc, q_scale, index.rows, index.rnorm, ci, cv, eps, k, vals=vals[r0:r1], idx=idx[r0:r1], certified=cert[r0:r1])
+        q16, norms = ops.rows_bf16(qc, q_scale, out=qbuf[: _up128(r1 - r0)])
+        eps = compact_eps(norms, *bounds, index.Ep).float()
+        if filtered:                                                  # the candidates and the certificate over the admissible rows
+            part = ops.search_coarse_filtered(q16, index.coarse, r1 - r0, index.N, D, q_ids=None if query_ids is None else query_ids[r0:r1],
+                                              g_ids=gallery_ids, live=live, slabs=slabs)
+            cv, ci = ops.search_merge(part, D)
+            rerank = ops.search_rerank_filtered
+        else:
+            cv, ci = ops.search_coarse(q16, index.coarse, r1 - r0, index.N, D, slabs=slabs)
+            rerank = ops.search_rerank
+        rerank(qc, q_scale, index.rows, index.rnorm, ci, cv, eps, k, vals=vals[r0:r1], idx=idx[r0:r1], certified=cert[r0:r1])
     cert = cert.bool()
     if fallback == "exact":
         todo = torch.nonzero(~cert).squeeze(1)                        # the host reads the mask here
         if todo.numel():
-            fv, fi = _exact_fallback(q[todo].contiguous(), index, k, cosine)
+            fv, fi = _exact_fallback(q[todo].contiguous(), index, k, cosine, None if query_ids is None else query_ids[todo], gallery_ids, live)
             vals[todo] = fv
             idx[todo] = fi
     return vals, idx.long(), cert
@@ -709,10 +598,7 @@ def mutual_ranks(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex], a_ids: t
     dev = A.device
     a_ids = a_ids.to(device=dev, dtype=torch.int64).contiguous()
     b_ids = b_ids.to(device=dev, dtype=torch.int64).contiguous()
-    a_split = torch.empty(-(-nA // 128) * 128, 6 * index.Ep, device=dev, dtype=torch.bfloat16)
-    for r0 in range(0, nA, _INDEX_CHUNK_ROWS):
-        r1 = min(nA, r0 + _INDEX_CHUNK_ROWS)
-        _split_rows(_rows_f32(A[r0:r1]), 0, cosine, a_split[r0:])
+    a_split = _split_in_chunks(A, 0, cosine)
     best_a, ahead_a, best_b, ahead_b = ops.rank_counts(a_split, index.split, a_ids, b_ids, nA, nB, slabs=slabs)
     # key 0 (no correct, non-NaN candidate) came back as -inf; +inf: an overflowed score
     ahead_a = torch.where(torch.isfinite(best_a), ahead_a.long(), torch.full((), nB, dtype=torch.int64, device=dev))
