@@ -791,6 +791,34 @@ int sc_search_rerank_filtered_f32(const float* q, int64_t ldq, const float* q_sc
 int sc_topk_rows_wide_f32(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, const int64_t* q_ids,
                           const int64_t* g_ids, const uint8_t* live, float* vals, int32_t* idx, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sharded gallery search: the exact merge of per-shard lists of up to 1024 entries (csrc/search_merge_wide.hip).  Additive in round
+ * 21; sc_abi_version() stays 7.
+ *   replaces: the gather of every rank's embeddings onto one device before the ranking of avssl/module/retrieval.py:45-46 can run, and
+ *             the 262 144-row limit of the wide selection: every shard (a row range of the gallery, on this device or on another
+ *             rank) is searched on its own and only the k-entry lists meet.
+ *   sc_search_merge_lists_f32  part_vals (fp32) / part_idx (int32): entry (s, q, j) lies at s * shard_stride + q * k + j - the natural
+ *                              layout is [S, nQ, k]; with shard_stride >= nQ k a slice of query rows of a larger buffer merges
+ *                              without a copy.  List (s, q) is what the search entries above return for shard s: best first under
+ *                              the order contract, part_idx a row OF THE SHARD, -1 = no entry.  row0 [S] int64 (a device pointer):
+ *                              the global row of every shard's row 0; the shards are disjoint row ranges of one gallery and every
+ *                              global row must be < 2^31 - 1.  -> vals [nQ, k] fp32, idx [nQ, k] int32 (the GLOBAL row, or -1): per
+ *                              query the k best entries over all S lists, best first.
+ *                              THE ORDER is sc_topk_rows_f32's over global rows: larger value first; the lower global row first
+ *                              among equal values (-0 == +0); NaN above every number, the lower global row first among NaNs;
+ *                              -inf / -1 behind the last entry.  An input entry is a filler iff its part_idx < 0, whatever its
+ *                              value; a real -inf with part_idx >= 0 ranks ahead of every filler, whichever shard holds it.
+ *                              vals carry the INPUT'S OWN 32 bits (-0 stays -0, NaN payloads stay): the 64-bit word key << 32 | ~row
+ *                              is only the sort key, the value bits travel beside it.
+ *                              1 <= k <= 1024, S >= 1, shard_stride >= 0 (and >= nQ k when S > 1); nQ == 0: no-op; S == 1: a copy
+ *                              with the row offset applied.  One workgroup per group of queries, the running list in 12 KiB of LDS,
+ *                              log2(roundup_pow2(k)) compare-exchange steps per further shard.  The lists being best first matters
+ *                              for the result only, never for memory safety: no address depends on a value or a row.  Argument
+ *                              checks in front of the launch, no atomics, nothing allocated, the same input gives the same bits.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_search_merge_lists_f32(const float* part_vals, const int32_t* part_idx, int64_t shard_stride, const int64_t* row0, int32_t nQ,
+                              int32_t S, int32_t k, float* vals, int32_t* idx, void* stream);
+
 /* Keyword BatchNorm: nn.BatchNorm1d over the keyword positions (avssl/module/speechclip_c_modules/kw_bn.py:167-228).
  *   x [N, E] fp32 (N = batch x keyword slots), per-channel statistics.  training: batch statistics (biased variance for the
  *   normalisation, unbiased for the running estimate; run_mean / run_var updated in place with `momentum`), save_mean / save_rstd

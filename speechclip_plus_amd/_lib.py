@@ -181,6 +181,7 @@ SIGNATURES = {
     "sc_search_merge_u64": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "sc_topk_rows_filtered_f32": [c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sc_topk_rows_wide_f32": [c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "sc_search_merge_lists_f32": [c_void_p, c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "sc_search_coarse_filtered_bf16": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sc_search_rerank_filtered_f32": [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                       c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],

@@ -775,9 +775,16 @@ class KWClip_GeneralTransformer(nn.Module):
         ``query_ids`` [nQ] / ``gallery_ids`` [N] (int64 device tensors): a gallery row whose id equals the query's is left out of that
         query's list (retrieval.search's filter - a spoken caption must not retrieve itself or its siblings).  A tensor gallery takes
         ``gallery_ids``; a GalleryIndex or CompactGalleryIndex brings its own ``ids`` and its ``live`` mask (the compact one goes
-        through retrieval.search_compact's filtered call and its exact fallback).  Without ids the call is the unfiltered one."""
-        from .retrieval import CompactGalleryIndex, GalleryIndex, search
-        if isinstance(gallery, CompactGalleryIndex):
+        through retrieval.search_compact's filtered call and its exact fallback).  Without ids the call is the unfiltered one.
+        A retrieval.ShardedGalleryIndex (built with ``cosine=True``; one device or one shard per rank of a process group, where the call
+        is collective): retrieval.search_sharded - the same lists, global rows as ``idx``, the index's own ids and removed rows."""
+        from .retrieval import CompactGalleryIndex, GalleryIndex, ShardedGalleryIndex, search
+        sharded = isinstance(gallery, ShardedGalleryIndex)            # a gallery in shards: retrieval.search_sharded, the same lists
+        if sharded:
+            if gallery_ids is not None:
+                raise ValueError("retrieve: a ShardedGalleryIndex brings its own ids (build it with ids=); gallery_ids must be None")
+            g_cuda = gallery.device.type == "cuda"
+        elif isinstance(gallery, CompactGalleryIndex):
             g_cuda = gallery.coarse.is_cuda
         else:
             g_cuda = gallery.split.is_cuda if isinstance(gallery, GalleryIndex) else (isinstance(gallery, torch.Tensor) and gallery.is_cuda)
@@ -797,6 +804,9 @@ class KWClip_GeneralTransformer(nn.Module):
             raise ValueError("retrieve: queries must be a [nQ, E] tensor of embeddings or a list of waveforms")
         k = int(max(self.recall_at)) if k is None else int(k)
         queries = unit_rows(queries.detach().float())
+        if sharded:
+            from .retrieval import search_sharded
+            return search_sharded(queries, gallery, k, query_ids=query_ids)
         if not isinstance(gallery, (GalleryIndex, CompactGalleryIndex)):
             gallery = unit_rows(gallery.detach().float())
         if query_ids is None and gallery_ids is None:

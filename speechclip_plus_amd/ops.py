@@ -1094,6 +1094,45 @@ def search_merge(part: torch.Tensor, k: int, vals: Optional[torch.Tensor] = None
     return vals, idx
 
 
+def search_merge_lists(part_vals: torch.Tensor, part_idx: torch.Tensor, row0: torch.Tensor, k: int, *, vals: Optional[torch.Tensor] = None,
+                       idx: Optional[torch.Tensor] = None):
+    """part_vals [S, nQ, k] fp32 / part_idx [S, nQ, k] int32 - per shard s of a gallery the list ``search`` returns for it (best first, a
+    row of the shard, -1 = no entry) -, row0 [S] int64 on the device = the global row of every shard's row 0 -> (vals [nQ, k] fp32,
+    idx [nQ, k] int32 global rows): per query the k best entries over all S lists under the order contract on GLOBAL rows, the values'
+    own 32 bits kept, -inf / -1 behind the last entry (sc_search_merge_lists_f32, csrc/search_merge_wide.hip).  1 <= k <= 1024.  The
+    shard stride is taken from the tensors: both must have the strides (>= nQ k, k, 1), so ``buf[:, q0:q1]`` of a [S, nQall, k] buffer
+    merges without a copy.  ``vals`` / ``idx``: caller-owned contiguous outputs."""
+    k = int(k)
+    for what, t, dtype in (("part_vals", part_vals, torch.float32), ("part_idx", part_idx, torch.int32), ("row0", row0, torch.int64)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"search_merge_lists: {what} must be a tensor")
+        if t.dtype != dtype:
+            raise ValueError(f"search_merge_lists: {what} must be {dtype}, not {t.dtype}")
+    if part_vals.dim() != 3 or part_vals.shape[2] != k or part_idx.shape != part_vals.shape:
+        raise ValueError(f"search_merge_lists: part_vals {tuple(part_vals.shape)} / part_idx {tuple(part_idx.shape)} must both be [S, nQ, {k}]")
+    S, nQ = part_vals.shape[0], part_vals.shape[1]
+    if not 1 <= k <= 1024 or S < 1:
+        raise ValueError(f"search_merge_lists: 1 <= k <= 1024 and S >= 1 (k {k}, S {S})")
+    if row0.dim() != 1 or row0.numel() != S or not row0.is_contiguous():
+        raise ValueError(f"search_merge_lists: row0 has shape {tuple(row0.shape)}, expected a contiguous ({S},)")
+    stride = nQ * k
+    if nQ > 0:
+        for what, t in (("part_vals", part_vals), ("part_idx", part_idx)):
+            if t.stride(2) != 1 or (nQ > 1 and t.stride(1) != k) or (S > 1 and t.stride(0) < nQ * k):
+                raise ValueError(f"search_merge_lists: {what} has strides {t.stride()}, expected (>= {nQ * k}, {k}, 1)")
+        if S > 1:
+            stride = part_vals.stride(0)
+            if part_idx.stride(0) != stride:
+                raise ValueError(f"search_merge_lists: part_vals and part_idx differ in their shard stride ({stride}, {part_idx.stride(0)})")
+    if not (part_vals.is_cuda and part_idx.is_cuda and row0.is_cuda):
+        raise RuntimeError("search_merge_lists runs on the HIP kernels: no CPU path")
+    vals, idx = _lists_out(nQ, k, part_vals.device, vals, idx)
+    null = ctypes.c_void_p(0)
+    check(lib().sc_search_merge_lists_f32(_p(part_vals) if nQ else null, _p(part_idx) if nQ else null, stride, _p(row0), nQ, S, k,
+                                          _p(vals) if nQ else null, _p(idx) if nQ else null, _stream()), "sc_search_merge_lists_f32")
+    return vals, idx
+
+
 def search_topk_filtered(q_split: torch.Tensor, g_split: torch.Tensor, nQ: int, N: int, k: int, q_ids: Optional[torch.Tensor] = None,
                          g_ids: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None, slabs: Optional[int] = None,
                          vals: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None):

@@ -15,7 +15,7 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 import torch
 
 __all__ = ["mutualRetrieval", "GalleryIndex", "search", "mutual_ranks", "recall_from_ranks", "mutual_recall", "CompactGalleryIndex",
-           "search_compact", "compact_eps", "hard_negatives"]
+           "search_compact", "compact_eps", "hard_negatives", "ShardedGalleryIndex", "search_sharded"]
 
 
 def _recall(score: torch.Tensor, query_ids: torch.Tensor, cand_ids: torch.Tensor, ks: Sequence[int], cand_title: str) -> Dict[str, float]:
@@ -335,7 +335,12 @@ def hard_negatives(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex, "Compac
     fewer than k wrong rows ends in -inf / -1, and a removed row of an index (``live``) is never mined.  ``B`` a CompactGalleryIndex:
     the same lists through ``search_compact(..., query_ids=a_ids, gallery_ids=b_ids)`` and its exact fallback (vals are the re-rank's).
     1 <= k <= 1024 on a tensor or a GalleryIndex (k > 32: ``search``'s wide selection, at most 262 144 rows in ``B``); k <= 32 on a
-    CompactGalleryIndex."""
+    CompactGalleryIndex.  ``B`` a ShardedGalleryIndex built with ``ids=`` (``b_ids`` None): ``search_sharded(A, B, k, cosine,
+    query_ids=a_ids)`` - the same lists with global rows, any number of rows in ``B``, collective when the index is distributed."""
+    if isinstance(B, ShardedGalleryIndex):                            # the shards bring their ids: search_sharded, the same lists
+        if a_ids is None or b_ids is not None or B.ids is None:
+            raise ValueError("hard_negatives: a ShardedGalleryIndex takes a_ids and its own ids (build it with ids=, pass b_ids=None)")
+        return search_sharded(A, B, k, cosine=cosine, query_ids=a_ids)
     if a_ids is None:
         raise ValueError("hard_negatives: a_ids is required (without ids every row is a negative: that is search)")
     if b_ids is None and not (isinstance(B, (GalleryIndex, CompactGalleryIndex)) and B.ids is not None):
@@ -343,6 +348,205 @@ def hard_negatives(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex, "Compac
     if isinstance(B, CompactGalleryIndex):
         return search_compact(A, B, k, cosine=cosine, query_ids=a_ids, gallery_ids=b_ids)[:2]
     return search(A, B, k, cosine=cosine, query_ids=a_ids, gallery_ids=b_ids)
+
+
+# ------------------------------------------------------------------------------------------------ sharded gallery search
+# ``search`` serves one GalleryIndex on one device, and at k > 32 at most ``wide_max_gallery()`` rows of it.  A ShardedGalleryIndex is
+# consecutive row ranges of one logical gallery, each a GalleryIndex - cut from one tensor on this device, or one range per rank of a
+# process group.  ``search_sharded`` runs ``search`` per shard and merges the k-entry lists exactly (csrc/search_merge_wide.hip): a score
+# depends only on its query row, its gallery row and the fixed K order, so the result equals ``search`` on the whole gallery bit for bit.
+SHARD_LISTS_BYTES = 256 << 20      # the partial lists of one chunk of queries, S * chunk * k * 8 bytes, stay under this
+
+
+class ShardedGalleryIndex(_LiveRows):
+    """Consecutive row ranges of one gallery [N, E], each a GalleryIndex, for ``search_sharded``.
+
+    Local form, ``ShardedGalleryIndex(gallery, shard_rows=None, cosine=False, ids=None)``: ``gallery`` [N, E] on the device is cut into
+    shards of ``shard_rows`` rows (None: ``wide_max_gallery()``, the most ``search`` serves at k > 32; any positive int is legal, the
+    last shard may be short).  Every shard is built as a GalleryIndex is - in chunks of rows, no second fp32 copy of the gallery.
+    The default is the FEWEST shards, not the fastest call at k > 32: ``search`` scores as many query rows at a time as its 128 MiB
+    scratch holds of a shard's rows, 128 at 262 144; ``shard_rows=65536`` ran 1 024 x 1 000 000 x 512 at k = 100 in 8.3 ms against 21.2 ms
+    (docs/rounds/r21_sharded_search.md).
+
+    Distributed form, ``ShardedGalleryIndex(rows, cosine=False, ids=None, group=pg)``: COLLECTIVE over the process group ``pg``
+    (torch.distributed).  ``rows`` [n_rank, E] are this rank's rows of the gallery (0 rows are legal), ``ids`` this rank's ids; the global
+    gallery is the ranks' rows in rank order, so this rank's ``row0`` is the sum of the lower ranks' counts (exchanged once, here).  E
+    must be equal on every rank (a ValueError on every rank otherwise).
+
+    ``N`` (``len(index)``): the global row count.  ``E``, ``cosine``, ``shards`` (the GalleryIndex objects on this device), ``row0`` (the
+    global row of each of them), ``n_live`` (live rows of the whole gallery; in the distributed form reading it is collective).
+    ``remove(rows)`` / ``restore(rows=None)`` take GLOBAL rows, as on a GalleryIndex (IndexError outside [0, N)); in the distributed
+    form every rank passes the same rows and applies those in its range.  ``ids``: the constructor's argument (None: the index takes no
+    ``query_ids``); the shards hold their slices of it and their own ``live`` masks."""
+
+    def __init__(self, gallery: torch.Tensor, shard_rows: Optional[int] = None, cosine: bool = False, ids: Optional[torch.Tensor] = None,
+                 group=None):
+        if isinstance(gallery, (CompactGalleryIndex, GalleryIndex)) or (
+                isinstance(gallery, (list, tuple)) and any(isinstance(s, CompactGalleryIndex) for s in gallery)):
+            raise ValueError("ShardedGalleryIndex: built from the gallery's rows, every shard a GalleryIndex - a CompactGalleryIndex cannot "
+                             "be a shard (its lists are certified on 32 candidates, its values are re-rank scores)")
+        self._init_rows(gallery, cosine, ids)
+        self.group = group
+        n = self.N
+        if group is None:
+            shard_rows = wide_max_gallery() if shard_rows is None else int(shard_rows)
+            if shard_rows < 1:
+                raise ValueError(f"ShardedGalleryIndex: shard_rows must be a positive int (shard_rows {shard_rows})")
+            self.row0 = list(range(0, max(n, 1), shard_rows))
+            self.shards = [GalleryIndex(gallery[r0: r0 + shard_rows], cosine=cosine, ids=None if ids is None else ids[r0: r0 + shard_rows])
+                           for r0 in self.row0]
+            starts = self.row0
+        else:
+            import torch.distributed as dist
+            if shard_rows is not None:
+                raise ValueError("ShardedGalleryIndex: shard_rows applies to the local form; with group= every rank's rows are one shard")
+            W, rank = dist.get_world_size(group), dist.get_rank(group)
+            mine = torch.tensor([n, self.E, int(ids is not None)], device=gallery.device, dtype=torch.int64)
+            every = torch.empty(W * 3, device=gallery.device, dtype=torch.int64)
+            dist.all_gather_into_tensor(every, mine, group=group)
+            counts, Es, has = (every.view(W, 3)[:, j].tolist() for j in range(3))
+            if len(set(Es)) != 1:
+                raise ValueError(f"ShardedGalleryIndex: E differs between the ranks ({Es})")
+            if len(set(has)) != 1:
+                raise ValueError(f"ShardedGalleryIndex: ids on some ranks only ({has})")
+            starts = [sum(counts[:r]) for r in range(W)]
+            self.N = sum(counts)
+            self.row0 = [starts[rank]]
+            self.shards = [GalleryIndex(gallery, cosine=cosine, ids=ids)]
+        if self.N >= 2 ** 31 - 1:
+            raise ValueError(f"ShardedGalleryIndex: {self.N} rows - a global row must be below 2^31 - 1")
+        self._starts = torch.tensor(starts, device=gallery.device, dtype=torch.int64)     # row0 of every list the merge sees
+
+    @property
+    def device(self) -> torch.device:
+        return self.shards[0].device
+
+    def _per_shard(self, rows: torch.Tensor):
+        """global rows (checked, on the device) -> (shard, its own rows of them) for every shard on this device that has any"""
+        for r0, shard in zip(self.row0, self.shards):
+            own = rows[(rows >= r0) & (rows < r0 + shard.N)] - r0
+            if own.numel():
+                yield shard, own
+
+    def remove(self, rows):
+        """Take the GLOBAL gallery rows ``rows`` out of every later search (the shards' ``live`` masks; the rows' data is not touched)."""
+        for shard, own in self._per_shard(self._rows_arg(rows)):
+            shard.remove(own)
+        return self
+
+    def restore(self, rows=None):
+        """Put the GLOBAL rows ``rows`` back (None: every row, and every shard searches exactly as before any ``remove``)."""
+        if rows is None:
+            for shard in self.shards:
+                shard.restore()
+        else:
+            for shard, own in self._per_shard(self._rows_arg(rows)):
+                shard.restore(own)
+        return self
+
+    @property
+    def n_live(self) -> int:
+        n = sum(shard.n_live for shard in self.shards)
+        if self.group is not None:
+            import torch.distributed as dist
+            total = torch.tensor([n], device=self.device, dtype=torch.int64)
+            dist.all_reduce(total, group=self.group)
+            n = int(total)
+        return n
+
+
+def _gather_rows(x: torch.Tensor, counts: Sequence[int], group) -> torch.Tensor:
+    """x [counts[rank], ...] on every rank -> the ranks' rows in rank order [sum(counts), ...] on every rank: one all_gather_into_tensor
+    of blocks padded to the largest count (the collective wants equal sizes), the padding cut away"""
+    import torch.distributed as dist
+    W, top = len(counts), max(counts)
+    block = torch.zeros((top,) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype)
+    block[: x.shape[0]] = x
+    every = torch.empty((W * top,) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype)      # rank-major along dim 0: the collective's layout
+    dist.all_gather_into_tensor(every, block, group=group)
+    every = every.view((W, top) + tuple(x.shape[1:]))
+    return torch.cat([every[r, : counts[r]] for r in range(W)], dim=0)
+
+
+def search_sharded(queries: torch.Tensor, index: ShardedGalleryIndex, k: int, cosine: bool = False, *,
+                   query_ids: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """queries [nQ, E], a ShardedGalleryIndex -> (vals [nQ, k] fp32, idx [nQ, k] int64 GLOBAL gallery rows), 1 <= k <= 1024: what
+    ``search(queries, GalleryIndex(whole gallery), k, cosine, query_ids=...)`` returns - the same rows in the same places, the same 32
+    bits in every value - for every partition into shards, also where ``search`` itself stops (k > 32 on more than 262 144 rows; a
+    gallery spread over the ranks of a process group).  ``cosine`` applies to the queries (the index carries its own choice).
+    ``query_ids`` [nQ] int64: a gallery row whose id equals the query's is left out (the index must have been built with ``ids=``); the
+    shards' removed rows are never returned.
+
+    Per chunk of queries: ``search`` on every shard - so scores, filter, order and tails are ``search``'s, with its scratch, one shard at
+    a time -, the lists stacked [S, chunk, k], one ``ops.search_merge_lists``.  The chunk keeps the stacked lists, S * chunk * k * 8
+    bytes, under ``SHARD_LISTS_BYTES`` (256 MiB).
+
+    Distributed index: the call is COLLECTIVE.  Every rank passes its OWN queries (the counts may differ, 0 is legal), the same k, and
+    ids on every rank or on none.  The counts are exchanged, queries and ids all-gathered, every rank searches its shard for all of
+    them, the partial lists are all-gathered ([W, nQall, k], rank-major: the merge's layout) and every rank merges the slice of its own
+    queries.  The chunk loop's trip count comes from the global query count, so every rank runs the same collectives."""
+    from . import ops
+    k = int(k)
+    if not 1 <= k <= WIDE_MAX_K:
+        raise ValueError(f"search_sharded: 1 <= k <= {WIDE_MAX_K} (k {k})")
+    if not isinstance(index, ShardedGalleryIndex):
+        raise ValueError("search_sharded: index must be a ShardedGalleryIndex (a tensor or a GalleryIndex goes to search)")
+    if not isinstance(queries, torch.Tensor) or queries.dim() != 2:
+        raise ValueError("search_sharded: queries must be a [nQ, E] tensor")
+    nQ = queries.shape[0]
+    if query_ids is not None:
+        if index.ids is None:
+            raise ValueError("search_sharded: query_ids on a ShardedGalleryIndex built without ids=")
+        ops.check_filter_tensor("search_sharded", "query_ids", query_ids, nQ)
+    if not queries.is_cuda or (query_ids is not None and not query_ids.is_cuda):
+        raise RuntimeError("search_sharded runs on the HIP kernels: device tensors only")
+    assert queries.shape[1] == index.E, (queries.shape, index.E)
+    if k > 32 and any(shard.N > wide_max_gallery() for shard in index.shards):
+        raise ValueError(f"search_sharded: k = {k} on shards of more than {wide_max_gallery()} rows - search serves 32 < k <= {WIDE_MAX_K} "
+                         f"on at most that many; build the index with shard_rows <= {wide_max_gallery()}")
+    dev = queries.device
+    own0, own1 = 0, nQ                                                # this rank's queries among all of them
+    if index.group is not None:
+        import torch.distributed as dist
+        W, rank = dist.get_world_size(index.group), dist.get_rank(index.group)
+        mine = torch.tensor([nQ, int(query_ids is not None)], device=dev, dtype=torch.int64)
+        every = torch.empty(W * 2, device=dev, dtype=torch.int64)
+        dist.all_gather_into_tensor(every, mine, group=index.group)
+        counts, has = every.view(W, 2)[:, 0].tolist(), every.view(W, 2)[:, 1].tolist()
+        if len(set(has)) != 1:
+            raise ValueError(f"search_sharded: query_ids on some ranks only ({has})")
+        own0 = sum(counts[:rank])
+        own1 = own0 + nQ
+        queries = _gather_rows(_rows_f32(queries), counts, index.group)
+        if query_ids is not None:
+            query_ids = _gather_rows(query_ids, counts, index.group)
+    nAll, S = queries.shape[0], int(index._starts.numel())
+    vals = torch.empty(nQ, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(nQ, k, device=dev, dtype=torch.int32)
+    if nAll == 0:
+        return vals, idx.long()
+    chunk = min(max(SHARD_LISTS_BYTES // (S * k * 8), 1), nAll)
+    pv = torch.empty(S * chunk * k, device=dev, dtype=torch.float32)  # the stacked lists of the call
+    pi = torch.empty(S * chunk * k, device=dev, dtype=torch.int32)
+    for c0 in range(0, nAll, chunk):
+        c1 = min(nAll, c0 + chunk)
+        n = c1 - c0
+        lv, li = pv[: S * n * k].view(S, n, k), pi[: S * n * k].view(S, n, k)
+        qc, ic = queries[c0:c1], None if query_ids is None else query_ids[c0:c1]
+        if index.group is None:
+            for s, shard in enumerate(index.shards):
+                v, i = search(qc, shard, k, cosine=cosine, query_ids=ic)
+                lv[s].copy_(v)
+                li[s].copy_(i)
+        else:
+            v, i = search(qc, index.shards[0], k, cosine=cosine, query_ids=ic)
+            dist.all_gather_into_tensor(lv.view(S * n, k), v.contiguous(), group=index.group)      # [W n, k]: rank-major, the merge's layout
+            dist.all_gather_into_tensor(li.view(S * n, k), i.int().contiguous(), group=index.group)
+        a, b = max(c0, own0), min(c1, own1)
+        if a < b:
+            ops.search_merge_lists(lv[:, a - c0: b - c0], li[:, a - c0: b - c0], index._starts, k, vals=vals[a - own0: b - own0],
+                                   idx=idx[a - own0: b - own0])
+    return vals, idx.long()
 
 
 # ------------------------------------------------------------------------------------------------ compact gallery search
