@@ -819,6 +819,35 @@ int sc_topk_rows_wide_f32(const float* scores, int64_t ld, int32_t rows, int32_t
 int sc_search_merge_lists_f32(const float* part_vals, const int32_t* part_idx, int64_t shard_stride, const int64_t* row0, int32_t nQ,
                               int32_t S, int32_t k, float* vals, int32_t* idx, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Retrieval ranks in parts: sc_rank_counts_bf16's two phases as two accumulating entries, with a removed-row mask on B
+ * (csrc/rank_parts.hip).  Additive in round 22; sc_abi_version() stays 7.
+ *   replaces: the gather of every rank's embeddings onto one device before the sort-and-look-up of avssl/module/retrieval.py:45-121
+ *             can run: every (A range, B range) pair - a shard of the gallery, on this device or on another rank - is scored on its
+ *             own and only keys and counts meet.
+ *   Operands are sc_rank_counts_bf16's (a_split / b_split rows padded to 128, K6 % 384 == 0, int64 ids), its scores to the bit, its
+ *   keys and its counting rule.  b_live: NULL, or uint8 [nB]; column j takes part iff b_live == NULL or b_live[j] != 0.  A dead column
+ *   is neither a candidate of any row nor a query of the column direction, whatever its data (NaN included), and nothing is written
+ *   to best_b[j] / ahead_b[j].
+ *   THE PROTOCOL.  The caller zeroes best_a [nA], best_b [nB], ahead_a [nA], ahead_b [nB] ONCE, calls sc_rank_best_bf16 for every
+ *   (A range, B range) pair with the ranges' slices of the four buffers, then - after every "best" call, and after a MAX-reduction of
+ *   the keys where the pairs ran in different places - sc_rank_ahead_bf16 for every pair.  The accumulated result is what
+ *   sc_rank_counts_bf16 gives on the whole of A against the live rows of the whole of B, bit for bit.
+ *   sc_rank_best_bf16   one launch: atomicMax of the largest key over correct (a_ids[i] == b_ids[j]), non-NaN, live pairs into
+ *                       best_a[i] / best_b[j]; key 0 = none.  Calling it twice changes nothing.
+ *   sc_rank_ahead_bf16  one launch: READS best_a / best_b; atomicAdd into ahead_a[i] of #{j live : s_ij > best_a[i]} + #{j live, not
+ *                       correct : s_ij == best_a[i] or s_ij is NaN}, and the mirror image into ahead_b[j] of the live columns.
+ *                       Calling it twice doubles the counts.
+ *   Both: only integer atomics, so the result does not depend on S, on the run or on the order of the calls; no address depends on
+ *   a score, a key, an id or a mask byte; nothing at or past nA / nB is read of ids, mask, keys or counts; nothing is allocated;
+ *   argument checks in front of the launch; S >= 1 as for sc_rank_counts_bf16; nA == 0 or nB == 0: no-op, returns 0.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_rank_best_bf16(const sc_bf16* a_split, const sc_bf16* b_split, const int64_t* a_ids, const int64_t* b_ids, const uint8_t* b_live,
+                      int32_t nA, int32_t nB, int32_t K6, int32_t S, uint32_t* best_a, uint32_t* best_b, void* stream);
+int sc_rank_ahead_bf16(const sc_bf16* a_split, const sc_bf16* b_split, const int64_t* a_ids, const int64_t* b_ids, const uint8_t* b_live,
+                       int32_t nA, int32_t nB, int32_t K6, int32_t S, const uint32_t* best_a, const uint32_t* best_b, int32_t* ahead_a,
+                       int32_t* ahead_b, void* stream);
+
 /* Keyword BatchNorm: nn.BatchNorm1d over the keyword positions (avssl/module/speechclip_c_modules/kw_bn.py:167-228).
  *   x [N, E] fp32 (N = batch x keyword slots), per-channel statistics.  training: batch statistics (biased variance for the
  *   normalisation, unbiased for the running estimate; run_mean / run_var updated in place with `momentum`), save_mean / save_rstd

@@ -527,17 +527,55 @@ class KWClip_GeneralTransformer(nn.Module):
         self.log_dict(result, on_step=True, on_epoch=True, prog_bar=True, logger=True, sync_dist=True)
         return {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in outputs["others"].items()}
 
-    def validation_epoch_end(self, outputs: list) -> dict:
+    def validation_epoch_end(self, outputs: list, group=None) -> dict:
         """kwClip.py:447-482: one image embedding per id (the last seen, as the reference's dict does), audio x image scores
         and recall@k in both directions - everything stays on the device (retrieval.mutualRetrieval).  ``outputs``: the
-        ``others`` dicts returned by validation_step_end (or validation_step's full dicts)."""
-        from .retrieval import mutualRetrieval
+        ``others`` dicts returned by validation_step_end (or validation_step's full dicts).
+
+        ``group``: a torch.distributed process group whose ranks each hold the outputs of their own validation batches; the call is
+        then COLLECTIVE, needs ``retrieval.fused_ranks: true`` and returns, on every rank, the recall of the WHOLE validation set -
+        what the single-process call returns on the ranks' outputs concatenated in rank order (``_sharded_recall``)."""
+        if group is not None and not self.config.retrieval.get("fused_ranks", False):
+            raise ValueError("validation_epoch_end(group=...) runs on the sharded ranks: set retrieval.fused_ranks: true")
         outputs = [o["others"] if "others" in o else o for o in outputs]
         src = self.config.retrieval.get("audio_feat_src", "parallel")
         key = "cascaded_audio_feat" if src == "cascaded" else "parallel_audio_feat"
         ids = torch.cat([o["id"] for o in outputs], dim=0)
         audio = torch.cat([o["audio_feat"] if "audio_feat" in o else o[key] for o in outputs], dim=0).float()
         imgs = torch.cat([o["image_feat"] for o in outputs], dim=0).float()
+        if group is not None:
+            result = self._sharded_recall(ids, audio, imgs, group)
+        else:
+            result = self._recall_on_one_device(ids, audio, imgs)
+        if self._detokenize_enabled() and outputs and outputs[0].get("keywords", None) is not None:
+            every = int(self.config.log_setting.get("log_detokenize_results_every_n_epoch", 1) or 1)
+            if int(getattr(self, "current_epoch", 0)) % every == 0:
+                self._log_detokenized(outputs)
+        return result
+
+    def _sharded_recall(self, ids: torch.Tensor, audio: torch.Tensor, imgs: torch.Tensor, group) -> tuple:
+        """``validation_epoch_end`` over the ranks of ``group``: this rank's ids [n], audio and image embeddings [n, E] -> the three
+        recall dictionaries of the whole set.  The global sample order is the ranks' samples in rank order.  The ids are all-gathered
+        (int64, small), every rank computes the same "last occurrence of every id" and keeps, as its shard of the gallery, the image
+        rows of its own range that are one; the embeddings stay where they were encoded (retrieval.mutual_recall_sharded).  Recall
+        does not depend on the order of the gallery's rows, so the result equals the single-process one key for key."""
+        import torch.distributed as dist
+        from .retrieval import ShardedGalleryIndex, _exchange_counts, _gather_rows, mutual_recall_sharded
+        ids = ids.long().contiguous()
+        n = ids.shape[0]
+        counts = [c[0] for c in _exchange_counts([n], ids.device, group)]
+        own0 = sum(counts[: dist.get_rank(group)])
+        every = _gather_rows(ids, counts, group) if sum(counts) else ids
+        uniq, inv = torch.unique(every, return_inverse=True)
+        pos = torch.arange(every.shape[0], device=ids.device)
+        last = torch.zeros(uniq.shape[0], dtype=torch.long, device=ids.device).scatter_reduce(0, inv, pos, "amax", include_self=False)
+        rows = torch.sort(last[(last >= own0) & (last < own0 + n)]).values - own0        # this rank's rows that are a global last occurrence
+        index = ShardedGalleryIndex(imgs[rows].contiguous(), ids=ids[rows].contiguous(), group=group)
+        return mutual_recall_sharded(audio, index, ids, self.recall_at)
+
+    def _recall_on_one_device(self, ids: torch.Tensor, audio: torch.Tensor, imgs: torch.Tensor) -> tuple:
+        """``validation_epoch_end`` without a group: all ids [n], audio and image embeddings [n, E] on this device"""
+        from .retrieval import mutualRetrieval
         # last occurrence of every id, ids kept in first-seen order (python dict semantics of the reference)
         uniq, inv = torch.unique(ids, return_inverse=True)
         n = ids.shape[0]
@@ -554,10 +592,6 @@ class KWClip_GeneralTransformer(nn.Module):
             score_per_audio = audio @ img_feats.t()
             result = mutualRetrieval(score_per_A=score_per_audio, score_per_B=score_per_audio.t(), AB_answers=ids, BA_answers=img_ids,
                                      recall_at=self.recall_at)
-        if self._detokenize_enabled() and outputs and outputs[0].get("keywords", None) is not None:
-            every = int(self.config.log_setting.get("log_detokenize_results_every_n_epoch", 1) or 1)
-            if int(getattr(self, "current_epoch", 0)) % every == 0:
-                self._log_detokenized(outputs)
         return result
 
     # --------------------------------------------------------------------------------------------- keyword detokenisation

@@ -1270,6 +1270,55 @@ def rank_counts(a_split: torch.Tensor, b_split: torch.Tensor, a_ids: torch.Tenso
     return _rank_key_value(key_a), ahead_a, _rank_key_value(key_b), ahead_b
 
 
+def _rank_part_operands(name: str, a_split, b_split, a_ids, b_ids, nA: int, nB: int, counts, b_live, slabs):
+    """``rank_counts``' checks for ``rank_best`` / ``rank_ahead`` (``name``), and those of the caller's accumulators ``counts`` (pairs of
+    (tensor, rows): int32, contiguous, on the device) and of ``b_live`` -> (K6, S, the mask as uint8 or None)"""
+    every = (a_split, b_split, a_ids, b_ids) + tuple(t for t, _ in counts) + (() if b_live is None else (b_live,))
+    if not all(t.is_cuda for t in every):
+        raise RuntimeError(f"{name} runs on the HIP kernels: no CPU path")
+    assert a_split.dtype == torch.bfloat16 and b_split.dtype == torch.bfloat16 and a_split.dim() == 2 and b_split.dim() == 2
+    assert a_split.is_contiguous() and b_split.is_contiguous()
+    K6 = a_split.shape[1]
+    assert b_split.shape[1] == K6, (a_split.shape, b_split.shape)
+    assert a_split.shape[0] >= -(-nA // 128) * 128 and b_split.shape[0] >= -(-nB // 128) * 128, (a_split.shape, nA, b_split.shape, nB)
+    assert a_ids.dtype == torch.int64 and b_ids.dtype == torch.int64 and a_ids.is_contiguous() and b_ids.is_contiguous()
+    assert tuple(a_ids.shape) == (nA,) and tuple(b_ids.shape) == (nB,), (a_ids.shape, nA, b_ids.shape, nB)
+    for t, rows in counts:
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (rows,), (name, t.dtype, t.shape, rows)
+    if b_live is not None:
+        assert b_live.dtype in (torch.bool, torch.uint8) and b_live.is_contiguous() and tuple(b_live.shape) == (nB,), (b_live.dtype, b_live.shape, nB)
+        b_live = b_live.view(torch.uint8)
+    return K6, (search_slabs(nA, nB, 1) if slabs is None else int(slabs)), b_live
+
+
+def rank_best(a_split: torch.Tensor, b_split: torch.Tensor, a_ids: torch.Tensor, b_ids: torch.Tensor, nA: int, nB: int,
+              key_a: torch.Tensor, key_b: torch.Tensor, *, b_live: Optional[torch.Tensor] = None, slabs: Optional[int] = None) -> None:
+    """The first phase of ``rank_counts`` for one (A range, B range) pair, ACCUMULATED (sc_rank_best_bf16, csrc/rank_parts.hip):
+    key_a [nA] / key_b [nB] int32 (the kernel's uint32 keys; ``_rank_key_value`` decodes them, 0 = none) take the maximum of what
+    they hold and the pair's largest key over correct, non-NaN candidates.  ``b_live`` [nB] bool / uint8 or None: a row of B with
+    b_live == 0 is no candidate and no query, and its slot of ``key_b`` is not touched.  The caller zeroes the keys once, calls this
+    for every pair, then ``rank_ahead`` for every pair; operands, scores and ``slabs`` are ``rank_counts``'."""
+    nA, nB = int(nA), int(nB)
+    K6, S, live = _rank_part_operands("rank_best", a_split, b_split, a_ids, b_ids, nA, nB, ((key_a, nA), (key_b, nB)), b_live, slabs)
+    if nA and nB:
+        check(lib().sc_rank_best_bf16(_p(a_split), _p(b_split), _p(a_ids), _p(b_ids), _p(live), nA, nB, K6, S, _p(key_a), _p(key_b),
+                                      _stream()), "sc_rank_best_bf16")
+
+
+def rank_ahead(a_split: torch.Tensor, b_split: torch.Tensor, a_ids: torch.Tensor, b_ids: torch.Tensor, nA: int, nB: int,
+               key_a: torch.Tensor, key_b: torch.Tensor, ahead_a: torch.Tensor, ahead_b: torch.Tensor, *,
+               b_live: Optional[torch.Tensor] = None, slabs: Optional[int] = None) -> None:
+    """The second phase of ``rank_counts`` for one pair, ACCUMULATED (sc_rank_ahead_bf16, csrc/rank_parts.hip): reads the final keys
+    ``key_a`` [nA] / ``key_b`` [nB] (``rank_best`` over EVERY pair) and adds to ahead_a [nA] / ahead_b [nB] int32 the pair's
+    candidates that rank ahead under ``rank_counts``' rule.  ``b_live`` as in ``rank_best``: a dead row's ``ahead_b`` is not touched."""
+    nA, nB = int(nA), int(nB)
+    K6, S, live = _rank_part_operands("rank_ahead", a_split, b_split, a_ids, b_ids, nA, nB,
+                                      ((key_a, nA), (key_b, nB), (ahead_a, nA), (ahead_b, nB)), b_live, slabs)
+    if nA and nB:
+        check(lib().sc_rank_ahead_bf16(_p(a_split), _p(b_split), _p(a_ids), _p(b_ids), _p(live), nA, nB, K6, S, _p(key_a), _p(key_b),
+                                       _p(ahead_a), _p(ahead_b), _stream()), "sc_rank_ahead_bf16")
+
+
 def topk_rescore_cos(kw: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, vals: torch.Tensor, eps: float = 1e-8) -> torch.Tensor:
     """vals[r, j] <- cos(kw[r], table[idx[r, j]]) accumulated in fp64 (sc_topk_rescore_cos_f32): kw [rows, E], table [V, E] fp32, idx /
     vals [rows, k] int32 / fp32 contiguous (idx as ops.topk_rows wrote it; -1 -> -inf)."""

@@ -848,3 +848,112 @@ def mutual_recall(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex], AB_answ
             del res["median_rank"], res["mean_rank"]
     results_mean = {key: 0.5 * (results_AB[key] + results_BA[key]) for key in results_AB}
     return results_AB, results_BA, results_mean
+
+
+# ------------------------------------------------------------------------------------------------ ranks over a sharded gallery
+# ``mutual_ranks`` wants all of A and all of B in one GalleryIndex.  csrc/rank_parts.hip runs its two phases as accumulating entries
+# per (A, shard) pair: every shard's "best" first - between ranks the row keys meet in an all-reduce(MAX) -, then every shard's
+# "ahead".  A score depends only on its row of A, its row of B and the fixed K order, so the ranks are those of the whole gallery,
+# exactly: integers, no tolerance.
+def _exchange_counts(mine: Sequence[int], dev, group) -> list:
+    """a few ints of every rank -> [W][len(mine)] on every rank (one all_gather_into_tensor)"""
+    import torch.distributed as dist
+    W = dist.get_world_size(group)
+    m = torch.tensor(list(mine), device=dev, dtype=torch.int64)
+    every = torch.empty(W * m.numel(), device=dev, dtype=torch.int64)
+    dist.all_gather_into_tensor(every, m, group=group)
+    return every.view(W, m.numel()).tolist()
+
+
+def mutual_ranks_sharded(A: torch.Tensor, index: ShardedGalleryIndex, a_ids: torch.Tensor, cosine: bool = False) -> dict:
+    """``mutual_ranks`` of A [nA, E] (ids ``a_ids`` [nA] int64) against a ShardedGalleryIndex built with ``ids=``: row j of the gallery
+    is a correct candidate of row i of A iff index.ids[j] == a_ids[i].  -> {"ahead_AB" [nA] int64, "best_AB" [nA] fp32, "ahead_BA" [N]
+    int64, "best_BA" [N] fp32, "n_A", "n_B_live"}: ``mutual_ranks``' vectors on the whole gallery for every partition into shards,
+    exactly.  Removed rows of the index are no candidates and no queries: they carry ahead_BA = -1 and best_BA = -inf.  A query
+    without a correct live candidate, or whose best is not finite, gets ``ahead`` = the number of candidates: ``n_B_live`` for
+    A -> B, ``n_A`` for B -> A.  ``cosine`` applies to A (the index carries its own choice).
+
+    A is split once; ops.rank_best runs over every shard with the shard's ids and ``live`` mask, then ops.rank_ahead over every
+    shard (csrc/rank_parts.hip).  No [nA, N] matrix exists.
+
+    Distributed index (``index.group``): the call is COLLECTIVE.  Every rank passes its OWN rows of A and their ids (the counts may
+    differ, 0 is legal); they are all-gathered, every rank runs "best" for all of A against its shard, the row keys are combined by
+    all_reduce(MAX) - as unsigned values in int64 -, "ahead" runs with the global keys and the row counts are combined by
+    all_reduce(SUM).  The column results are complete on the rank that holds the rows, because it saw all of A.  Every rank
+    returns the A -> B entries of its own queries and the B -> A entries of its own gallery rows; ``n_A`` is the global query count."""
+    from . import ops
+    if not isinstance(index, ShardedGalleryIndex):
+        raise ValueError("mutual_ranks_sharded: index must be a ShardedGalleryIndex (a tensor or a GalleryIndex goes to mutual_ranks)")
+    if index.ids is None:
+        raise ValueError("mutual_ranks_sharded: a ShardedGalleryIndex built without ids= (the ids say which row is correct)")
+    if not isinstance(A, torch.Tensor) or A.dim() != 2:
+        raise ValueError("mutual_ranks_sharded: A must be a [nA, E] tensor")
+    nA = A.shape[0]
+    ops.check_filter_tensor("mutual_ranks_sharded", "a_ids", a_ids, nA)
+    if not A.is_cuda or not a_ids.is_cuda:
+        raise RuntimeError("mutual_ranks_sharded runs on the HIP kernels: device tensors only")
+    assert A.shape[1] == index.E, (A.shape, index.E)
+    dev, group = A.device, index.group
+    own0 = 0
+    if group is not None:
+        import torch.distributed as dist
+        counts = [c[0] for c in _exchange_counts([nA], dev, group)]
+        own0 = sum(counts[: dist.get_rank(group)])
+        if sum(counts):                                               # the same on every rank: so are the collectives below
+            A = _gather_rows(_rows_f32(A), counts, group)
+            a_ids = _gather_rows(a_ids, counts, group)
+    nAll = A.shape[0]
+    a_split = _split_in_chunks(A, 0, cosine)
+    off = [0]
+    for shard in index.shards:
+        off.append(off[-1] + shard.N)
+    n_loc = off[-1]                                                   # gallery rows on this device
+    out = torch.zeros(2 * (nAll + n_loc), device=dev, dtype=torch.int32)      # keys and counts of the call, zeroed in one fill
+    key_a, ahead_a, key_b, ahead_b = out[:nAll], out[nAll: 2 * nAll], out[2 * nAll: 2 * nAll + n_loc], out[2 * nAll + n_loc:]
+    for shard, o in zip(index.shards, off):
+        ops.rank_best(a_split, shard.split, a_ids, shard.ids, nAll, shard.N, key_a, key_b[o: o + shard.N], b_live=shard.live)
+    if group is not None and nAll:
+        # uint32 keys in int32 storage: a signed MAX would put every key of a positive score (>= 2^31) below the others
+        wide = key_a.long() & 0xFFFFFFFF
+        dist.all_reduce(wide, op=dist.ReduceOp.MAX, group=group)
+        key_a.copy_(torch.where(wide >= 2 ** 31, wide - 2 ** 32, wide))
+    for shard, o in zip(index.shards, off):
+        ops.rank_ahead(a_split, shard.split, a_ids, shard.ids, nAll, shard.N, key_a, key_b[o: o + shard.N], ahead_a, ahead_b[o: o + shard.N],
+                       b_live=shard.live)
+    ahead_a = ahead_a.long()
+    if group is not None and nAll:
+        dist.all_reduce(ahead_a, op=dist.ReduceOp.SUM, group=group)
+    n_live = index.n_live
+    best_a, best_b = ops._rank_key_value(key_a), ops._rank_key_value(key_b)
+    # key 0 (no correct, non-NaN, live candidate) came back as -inf; +inf: an overflowed score
+    ahead_a = torch.where(torch.isfinite(best_a), ahead_a, torch.full((), n_live, dtype=torch.int64, device=dev))
+    ahead_b = torch.where(torch.isfinite(best_b), ahead_b.long(), torch.full((), nAll, dtype=torch.int64, device=dev))
+    if any(shard.live is not None for shard in index.shards):
+        live = torch.cat([torch.ones(shard.N, device=dev, dtype=torch.bool) if shard.live is None else shard.live for shard in index.shards])
+        ahead_b = torch.where(live, ahead_b, torch.full((), -1, dtype=torch.int64, device=dev))     # best_b is -inf there: its key was never written
+    return {"ahead_AB": ahead_a[own0: own0 + nA], "best_AB": best_a[own0: own0 + nA], "ahead_BA": ahead_b, "best_BA": best_b,
+            "n_A": nAll, "n_B_live": n_live}
+
+
+def mutual_recall_sharded(A: torch.Tensor, index: ShardedGalleryIndex, AB_answers: torch.Tensor, recall_at: list,
+                          modality_A_title: str = "audio", modality_B_title: str = "image", cosine: bool = False,
+                          rank_stats: bool = False) -> Tuple[dict, dict, dict]:
+    """``mutual_recall``'s three dictionaries over the whole set from ``mutual_ranks_sharded``: A -> B over all queries, B -> A over
+    the live rows of the gallery (``AB_answers`` [nA] int64: the ids of A's rows; the gallery's are ``index.ids``).  Distributed
+    index: COLLECTIVE; the two ``ahead`` vectors are all-gathered, so every rank returns the same dictionaries."""
+    ranks = mutual_ranks_sharded(A, index, AB_answers, cosine=cosine)
+    ahead_ab, ahead_ba = ranks["ahead_AB"], ranks["ahead_BA"]
+    if index.group is not None:
+        counts = _exchange_counts([ahead_ab.numel(), ahead_ba.numel()], ahead_ab.device, index.group)
+        if sum(c[0] for c in counts):
+            ahead_ab = _gather_rows(ahead_ab.contiguous(), [c[0] for c in counts], index.group)
+        if sum(c[1] for c in counts):
+            ahead_ba = _gather_rows(ahead_ba.contiguous(), [c[1] for c in counts], index.group)
+    ahead_ba = ahead_ba[ahead_ba >= 0]                                # a removed row is no query
+    results_AB = recall_from_ranks(ahead_ab, ranks["n_B_live"], recall_at, modality_B_title)
+    results_BA = recall_from_ranks(ahead_ba, ranks["n_A"], recall_at, modality_A_title)
+    if not rank_stats:
+        for res in (results_AB, results_BA):
+            del res["median_rank"], res["mean_rank"]
+    results_mean = {key: 0.5 * (results_AB[key] + results_BA[key]) for key in results_AB}
+    return results_AB, results_BA, results_mean
