@@ -969,6 +969,29 @@ int sc_infonce_grad(const float* logits, const int64_t* ids, const float* lse_ro
                     const float* gscale /*device scalar*/, const float* inv_temp /*device scalar*/, float margin, int32_t dcl,
                     int32_t a2b, int32_t b2a, float* G, float* dlogit_dot /*[Bg]*/, void* stream);
 
+/* Mined negatives beside the batch (csrc/infonce_neg.hip): the a2b denominator of the loss above (avssl/module/losses.py:185-245, whose
+ * negatives are the batch alone) extended by, per anchor, a list of rows of a constant bank.  bank [N, E] fp32 with row stride
+ * bank_stride (floats, % 4), bank_ids [N] int64 or NULL (with ids, both or neither), neg_idx [Bg, M] int64 in the form hard_negatives
+ * returns, 1 <= M <= 1024, N < 2^31.  Slot (i, n), r = neg_idx[i, n], TAKES PART iff 0 <= r < N and (ids given) bank_ids[r] equals the id
+ * of no row of the batch (Bg <= 8192 with ids); other slots contribute through selects: their rows are never read.
+ *   sc_infonce_neg_fwd : reads the plain call's lse_row / lse_col / logits (the diagonal) and writes x [Bg, M] = inv_temp <A_i, bank[r]>
+ *                        (-inf where the slot takes no part), used [Bg] (slots that took part), lse_row_ext[i] = log(e^{lse_row_i} +
+ *                        sum_n e^{x_in}) and loss[0] recomputed from lse_row_ext, lse_col and the diagonal in sc_infonce_fwd's order (no
+ *                        slot taking part: the plain call's bits).  a2b must be set.  workspace: sc_infonce_neg_workspace_floats(Bg, M)
+ *                        floats, no initial contents needed.  Two launches; no atomics.
+ *   sc_infonce_neg_grad: dA [Bg, E] (holding G . B) += gscale / (Bg n_dir) inv_temp sum_n p_in bank[r_in], and dlogit_dot[i] += gscale /
+ *                        (Bg n_dir) sum_n p_in x_in / inv_temp, p_in = e^{x_in - lse_row_ext_i}; x = -inf marks the empty slots.  The in-batch
+ *                        gradient is sc_infonce_grad handed lse_row_ext.  The bank gets no gradient.
+ * Bg == 0: no launch.  Deterministic: the same operands give the same bits on every call. */
+int sc_infonce_neg_workspace_floats(int32_t Bg, int32_t M);   /* the count itself (0: no anchor or no legal M), -1: too many */
+int sc_infonce_neg_fwd(const float* A, const float* bank, int64_t bank_stride, const int64_t* neg_idx, const int64_t* ids,
+                       const int64_t* bank_ids, const float* inv_temp /*device scalar*/, const float* lse_row, const float* lse_col,
+                       const float* logits, int32_t Bg, int32_t E, int64_t N, int32_t M, int32_t a2b, int32_t b2a, float* x,
+                       int32_t* used, float* lse_row_ext, float* loss, float* workspace, void* stream);
+int sc_infonce_neg_grad(const float* bank, int64_t bank_stride, const int64_t* neg_idx, const float* x, const float* lse_row_ext,
+                        const float* gscale /*device scalar*/, const float* inv_temp /*device scalar*/, int32_t Bg, int32_t E, int64_t N,
+                        int32_t M, int32_t a2b, int32_t b2a, float* dA, float* dlogit_dot /*[Bg]*/, void* stream);
+
 /* CIF weight head (avssl/module/cif.py:106-129: ... Conv1d -> Dropout(0.5) -> ReLU -> Dropout(0.5) -> Linear(C, 1) -> Sigmoid): everything
  * behind the conv GEMM in one row kernel, forward and backward.  y [rows, C] fp32 = the conv output (bias included), w [C], bias [1]:
  *   alpha[row] = sigmoid(bias + sum_c w[c] m2 relu(m1 y[row, c]))     m1 / m2: dropout multipliers (p1 / p2, 0 in eval), keep bits =

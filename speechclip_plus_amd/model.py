@@ -443,8 +443,32 @@ class KWClip_GeneralTransformer(nn.Module):
                  "cascaded_audio_feat": cascaded_audio_feat, "vq_results": vq_results, "keywords": keywords,
                  "dsample_results": dsample_results, "keywords_len": keywords_len})
 
+    def set_negative_bank(self, embeddings: torch.Tensor, ids: torch.Tensor, k: int):
+        """Mined negatives for the contrastive loss: ``embeddings`` [N, E] are image embeddings of the training set (the image tower is
+        frozen, so they are constants: computed once, never stale, no gradient), ``ids`` [N] int64 their ids in the batch's id space.
+        The rows are normalised (``unit_rows``), kept, and indexed (``GalleryIndex(rows, ids=ids)``).  From then on ``compute_loss`` in
+        TRAIN mode mines, per branch term, ``hard_negatives(feat.detach(), index, id, None, k)`` and hands the criterion the bank, its
+        ids and the lists; eval mode and ``clear_negative_bank()`` give the plain loss.  ``search``'s own limits (1 <= k <= 1024, at most
+        262 144 rows at k > 32) raise as they do there.  ``compute_loss`` runs on the gathered batch on every rank, so data parallelism
+        needs no new collective."""
+        from .retrieval import WIDE_MAX_K, GalleryIndex
+        k = int(k)
+        if not 1 <= k <= WIDE_MAX_K:
+            raise ValueError(f"set_negative_bank: 1 <= k <= {WIDE_MAX_K} (k {k})")
+        if not isinstance(embeddings, torch.Tensor) or embeddings.dim() != 2:
+            raise ValueError("set_negative_bank: embeddings must be a [N, E] tensor")
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.shape != (embeddings.shape[0],):
+            raise ValueError(f"set_negative_bank: ids must be torch.int64 of shape ({embeddings.shape[0]},)")
+        rows = unit_rows(embeddings.detach().float()).detach()
+        ids = ids.detach().to(rows.device).contiguous()
+        self._neg_bank = (rows, ids, GalleryIndex(rows, ids=ids), k)
+
+    def clear_negative_bank(self):
+        self._neg_bank = None
+
     def compute_loss(self, inputDict: dict):
-        """kwClip.py:999-1040."""
+        """kwClip.py:999-1040.  With a negative bank set (``set_negative_bank``) and the model in train mode, every branch term takes
+        the bank rows mined for its anchors beside the batch."""
         assert isinstance(inputDict, dict)
         required_keys = {"id", "image_feat"}
         assert required_keys.issubset(set(inputDict.keys())), f"required: {required_keys}, input: {inputDict.keys()}"
@@ -457,8 +481,15 @@ class KWClip_GeneralTransformer(nn.Module):
             if loss_weight > 0.0:
                 feats_key = f"{branchType}_audio_feat"
                 assert feats_key in inputDict, f"{inputDict.keys()}"
+                mined = {}                          # train mode with a bank set: the bank, its ids and this term's mined lists
+                neg_bank = getattr(self, "_neg_bank", None) if self.training else None
+                if neg_bank is not None:
+                    from .retrieval import hard_negatives
+                    rows, bank_ids, index, k = neg_bank
+                    lists = hard_negatives(inputDict[feats_key].float().detach(), index, id, None, k)[1]
+                    mined = {"bank": rows, "bank_ids": bank_ids, "neg_idx": lists}
                 losses_[f"{branchType[0]}_cl_loss"] = self.criterion(feat_A=inputDict[feats_key].float(),
-                                                                     feat_B=image_feat, index=id)
+                                                                     feat_B=image_feat, index=id, **mined)
                 terms.append((float(loss_weight), losses_[f"{branchType[0]}_cl_loss"]))
         if "cif_quantity_out" in inputDict and "cif_target_len" in inputDict and hasattr(self, "quantity_loss_criteria"):
             losses_["quantity_loss"] = self.quantity_loss_criteria(inputDict["cif_quantity_out"], inputDict["cif_target_len"])

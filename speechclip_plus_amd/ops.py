@@ -1815,6 +1815,106 @@ def infonce_grad(logits: torch.Tensor, ids: Optional[torch.Tensor], lse_row: tor
     return G, dot
 
 
+NEG_MAX_M = 1024                   # the longest list per anchor (hard_negatives' own limit)
+
+
+def neg_operands(name: str, A, bank, neg_idx, ids, bank_ids, a2b: bool = True) -> None:
+    """The operands of the loss with a negative bank, checked before any launch, in ``search``'s order - format errors first, "device
+    tensors only" last: ids on one side only; dtypes and shapes (A [Bg, E] / bank [N, E] fp32 with E % 4 == 0, neg_idx [Bg, M] int64,
+    ids [Bg] / bank_ids [N] int64 contiguous); 1 <= M <= 1024; a2b; a bank that requires grad; the device."""
+    if (ids is None) != (bank_ids is None):
+        raise ValueError(f"{name}: ids on one side only - give the batch's ids and bank_ids, or neither")
+    for what, t in (("A", A), ("bank", bank)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{name}: {what} must be a 2-D tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: {what} must be torch.float32, not {t.dtype}")
+    Bg, E = A.shape
+    N = bank.shape[0]
+    if bank.shape[1] != E or E % 4 != 0 or E == 0:
+        raise ValueError(f"{name}: A {tuple(A.shape)} and bank {tuple(bank.shape)} must share E, a multiple of 4")
+    if N >= 2 ** 31:
+        raise ValueError(f"{name}: the bank has {N} rows, at most 2^31 - 1 are served")
+    if not isinstance(neg_idx, torch.Tensor):
+        raise ValueError(f"{name}: neg_idx must be a tensor")
+    if neg_idx.dtype != torch.int64:
+        raise ValueError(f"{name}: neg_idx must be torch.int64, not {neg_idx.dtype}")
+    if neg_idx.dim() != 2 or neg_idx.shape[0] != Bg:
+        raise ValueError(f"{name}: neg_idx has shape {tuple(neg_idx.shape)}, expected ({Bg}, M)")
+    if ids is not None:
+        check_filter_tensor(name, "ids", ids, Bg)
+        check_filter_tensor(name, "bank_ids", bank_ids, N)
+    M = neg_idx.shape[1]
+    if not 1 <= M <= NEG_MAX_M:
+        raise ValueError(f"{name}: 1 <= M <= {NEG_MAX_M} (neg_idx has M = {M} slots per anchor)")
+    if not a2b:
+        raise ValueError(f"{name}: the extra negatives enter the a2b denominator - with a2b=False they have none to enter")
+    if bank.requires_grad:
+        raise ValueError(f"{name}: the bank is constant - it gets no gradient (bank.requires_grad is set)")
+    given = [("A", A), ("bank", bank), ("neg_idx", neg_idx)] + ([("ids", ids), ("bank_ids", bank_ids)] if ids is not None else [])
+    for what, t in given:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} runs on the HIP kernels: device tensors only ({what})")
+    for what, t in given:
+        if t.device != A.device:
+            raise ValueError(f"{name}: {what} is on {t.device}, A on {A.device}")
+
+
+def bank_rows(bank: torch.Tensor) -> torch.Tensor:
+    """``bank`` as the kernels read it: rows of unit element stride at a row stride that is a multiple of 4 floats, 16-byte aligned (a
+    row-strided view is read in place; anything else is copied once)"""
+    N, E = bank.shape
+    if not (bank.stride(1) == 1 and (N <= 1 or (bank.stride(0) % 4 == 0 and bank.stride(0) >= E))):
+        bank = bank.contiguous()
+    return aligned16(bank)
+
+
+def infonce_neg_fwd(A: torch.Tensor, bank: torch.Tensor, neg_idx: torch.Tensor, ids: Optional[torch.Tensor], bank_ids: Optional[torch.Tensor],
+                    inv_temp: torch.Tensor, lse_row: torch.Tensor, lse_col: torch.Tensor, logits: torch.Tensor, a2b: bool = True,
+                    b2a: bool = True):
+    """The plain call's a2b denominator extended by the bank rows ``neg_idx`` [Bg, M] names (sc_infonce_neg_fwd, csrc/infonce_neg.hip):
+    ``lse_row`` / ``lse_col`` / ``logits`` are ``infonce_fwd``'s outputs for the same A, B, ids and options -> (loss [1], lse_row_ext [Bg],
+    x [Bg, M] = inv_temp <A_i, bank[r]> with -inf where the slot takes no part, used [Bg] int32).  A slot takes part iff 0 <= r < N and,
+    with ids, bank_ids[r] is the id of no batch row.  ``bank`` may be a row-strided view (read in place); a non-contiguous ``neg_idx`` is
+    copied."""
+    neg_operands("infonce_neg_fwd", A, bank, neg_idx, ids, bank_ids, a2b)
+    Bg, E = A.shape
+    N, M = bank.shape[0], neg_idx.shape[1]
+    assert A.is_contiguous() and inv_temp.dtype == torch.float32 and inv_temp.is_cuda and inv_temp.numel() == 1
+    assert logits.shape == (Bg, Bg) and logits.is_contiguous() and lse_row.shape == (Bg,) and lse_col.shape == (Bg,)
+    assert logits.dtype == lse_row.dtype == lse_col.dtype == torch.float32 and lse_row.is_contiguous() and lse_col.is_contiguous()
+    A, bank, neg_idx = aligned16(A), bank_rows(bank), neg_idx.contiguous()
+    dev = A.device
+    x = torch.empty(Bg, M, device=dev, dtype=torch.float32)
+    used = torch.empty(Bg, device=dev, dtype=torch.int32)
+    lse_ext = torch.empty(Bg, device=dev, dtype=torch.float32)
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    ws_floats = int(lib().sc_infonce_neg_workspace_floats(Bg, M))
+    if ws_floats < 0:
+        check(ws_floats, "sc_infonce_neg_workspace_floats")
+    ws = torch.empty(ws_floats, device=dev, dtype=torch.float32)
+    check(lib().sc_infonce_neg_fwd(_p(A), _p(bank), bank.stride(0) if N > 1 else E, _p(neg_idx), _p(ids), _p(bank_ids), _p(inv_temp),
+                                   _p(lse_row), _p(lse_col), _p(logits), Bg, E, N, M, int(a2b), int(b2a), _p(x), _p(used), _p(lse_ext),
+                                   _p(loss), _p(ws), _stream()), "sc_infonce_neg_fwd")
+    return loss, lse_ext, x, used
+
+
+def infonce_neg_grad(A: torch.Tensor, bank: torch.Tensor, neg_idx: torch.Tensor, x: torch.Tensor, lse_row_ext: torch.Tensor,
+                     gscale: torch.Tensor, inv_temp: torch.Tensor, a2b: bool, b2a: bool, dA: torch.Tensor, dot: torch.Tensor):
+    """The extras' share of the gradient, accumulated IN PLACE (sc_infonce_neg_grad): ``dA`` [Bg, E] (holding G . B of ``infonce_grad``
+    run on ``lse_row_ext``) += c inv_temp sum_n p_in bank[r_in] and ``dot`` [Bg] += c sum_n p_in x_in / inv_temp, p_in = e^{x_in -
+    lse_row_ext_i}, c = gscale / (Bg n_dir).  ``x`` is ``infonce_neg_fwd``'s (its -inf entries are the empty slots).  -> (dA, dot)"""
+    neg_operands("infonce_neg_grad", A, bank, neg_idx, None, None, a2b)
+    Bg, E = A.shape
+    N, M = bank.shape[0], neg_idx.shape[1]
+    assert x.shape == (Bg, M) and x.dtype == torch.float32 and x.is_contiguous() and lse_row_ext.shape == (Bg,)
+    assert dA.shape == (Bg, E) and dA.dtype == torch.float32 and dA.is_contiguous() and dot.shape == (Bg,) and dot.is_contiguous()
+    bank, neg_idx = bank_rows(bank), neg_idx.contiguous()
+    check(lib().sc_infonce_neg_grad(_p(bank), bank.stride(0) if N > 1 else E, _p(neg_idx), _p(x), _p(lse_row_ext), _p(gscale),
+                                    _p(inv_temp), Bg, E, N, M, int(a2b), int(b2a), _p(dA), _p(dot), _stream()), "sc_infonce_neg_grad")
+    return dA, dot
+
+
 def sumsq(x: torch.Tensor, nblk: int = 1024) -> torch.Tensor:
     part = torch.empty(nblk, device=x.device, dtype=torch.float32)
     check(lib().sc_sumsq_f32(_p(x), x.numel(), _p(part), nblk, _stream()), "sc_sumsq_f32")
