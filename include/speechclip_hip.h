@@ -645,7 +645,7 @@ int sc_search_topk_bf16(const sc_bf16* q_split, const sc_bf16* g_split, int32_t 
  *   sc_rank_counts_bf16  a_split [roundup(nA, 128), K6] / b_split [roundup(nB, 128), K6]: sc_search_topk_bf16's operands (side 0 / side 1
  *                        of sc_split3_bf16, K6 = 6 Ep, Ep % 64 == 0, padding rows zero) and its scores, to the bit.  a_ids [nA] /
  *                        b_ids [nB] int64: the pair (i, j) is correct iff a_ids[i] == b_ids[j].  Two launches of one kernel on
- *                        ``stream``: (1) best_a[i] = the largest key over the correct, non-NaN scores of row i, best_b[j] the same of
+ *                        ``stream`` - those of sc_rank_best_bf16 and sc_rank_ahead_bf16 (below) without a mask -: (1) best_a[i] = the largest key over the correct, non-NaN scores of row i, best_b[j] the same of
  *                        column j (atomicMax; key = sc_topk_rows_f32's order as a uint32: float order, -0 == +0; 0 = no such
  *                        candidate); (2) ahead_a[i] = #{j : s_ij > best_i} + #{j not correct : s_ij == best_i or s_ij is NaN} and
  *                        ahead_b[j] its mirror image over rows (int32 atomicAdd).  Rows >= nA / columns >= nB never enter.  All four
@@ -821,7 +821,7 @@ int sc_search_merge_lists_f32(const float* part_vals, const int32_t* part_idx, i
 
 /* ------------------------------------------------------------------------------------------------
  * Retrieval ranks in parts: sc_rank_counts_bf16's two phases as two accumulating entries, with a removed-row mask on B
- * (csrc/rank_parts.hip).  Additive in round 22; sc_abi_version() stays 7.
+ * (csrc/rank.hip: the same kernel, the same argument checks).  Additive in round 22; sc_abi_version() stays 7.
  *   replaces: the gather of every rank's embeddings onto one device before the sort-and-look-up of avssl/module/retrieval.py:45-121
  *             can run: every (A range, B range) pair - a shard of the gallery, on this device or on another rank - is scored on its
  *             own and only keys and counts meet.

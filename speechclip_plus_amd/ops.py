@@ -1250,19 +1250,9 @@ def rank_counts(a_split: torch.Tensor, b_split: torch.Tensor, a_ids: torch.Tenso
     ``a_split`` = split3_bf16(A, 0) [>= roundup(nA, 128), 6 Ep], ``b_split`` = split3_bf16(B, 1) [>= roundup(nB, 128), 6 Ep]; the scores are
     those of ``search_topk`` / ``cosine_scores_split`` and no [nA, nB] matrix is written.  ``slabs``: how many slabs B's rows are cut
     into (None: sc_search_slabs(nA, nB, 1)); the result does not depend on it, nor on the run."""
-    if not (a_split.is_cuda and b_split.is_cuda and a_ids.is_cuda and b_ids.is_cuda):
-        raise RuntimeError("rank_counts runs on the HIP kernels: no CPU path")
-    assert a_split.dtype == torch.bfloat16 and b_split.dtype == torch.bfloat16 and a_split.dim() == 2 and b_split.dim() == 2
-    assert a_split.is_contiguous() and b_split.is_contiguous()
-    K6 = a_split.shape[1]
-    assert b_split.shape[1] == K6, (a_split.shape, b_split.shape)
     nA, nB = int(nA), int(nB)
-    assert a_split.shape[0] >= -(-nA // 128) * 128 and b_split.shape[0] >= -(-nB // 128) * 128, (a_split.shape, nA, b_split.shape, nB)
-    assert a_ids.dtype == torch.int64 and b_ids.dtype == torch.int64 and a_ids.is_contiguous() and b_ids.is_contiguous()
-    assert tuple(a_ids.shape) == (nA,) and tuple(b_ids.shape) == (nB,), (a_ids.shape, nA, b_ids.shape, nB)
-    dev = a_split.device
-    S = search_slabs(nA, nB, 1) if slabs is None else int(slabs)
-    out = torch.zeros(2 * (nA + nB), device=dev, dtype=torch.int32)    # the kernel's four outputs, zeroed in one fill
+    K6, S, _ = _rank_part_operands("rank_counts", a_split, b_split, a_ids, b_ids, nA, nB, (), None, slabs)
+    out = torch.zeros(2 * (nA + nB), device=a_split.device, dtype=torch.int32)    # the kernel's four outputs, zeroed in one fill
     key_a, key_b, ahead_a, ahead_b = out[:nA], out[nA: nA + nB], out[nA + nB: 2 * nA + nB], out[2 * nA + nB:]
     if nA and nB:
         check(lib().sc_rank_counts_bf16(_p(a_split), _p(b_split), _p(a_ids), _p(b_ids), nA, nB, K6, S, _p(key_a), _p(key_b), _p(ahead_a),
@@ -1271,8 +1261,8 @@ def rank_counts(a_split: torch.Tensor, b_split: torch.Tensor, a_ids: torch.Tenso
 
 
 def _rank_part_operands(name: str, a_split, b_split, a_ids, b_ids, nA: int, nB: int, counts, b_live, slabs):
-    """``rank_counts``' checks for ``rank_best`` / ``rank_ahead`` (``name``), and those of the caller's accumulators ``counts`` (pairs of
-    (tensor, rows): int32, contiguous, on the device) and of ``b_live`` -> (K6, S, the mask as uint8 or None)"""
+    """The operand checks of ``rank_counts`` / ``rank_best`` / ``rank_ahead`` (``name``), those of the caller's accumulators ``counts``
+    (pairs of (tensor, rows): int32, contiguous, on the device) and of ``b_live`` -> (K6, S, the mask as uint8 or None)"""
     every = (a_split, b_split, a_ids, b_ids) + tuple(t for t, _ in counts) + (() if b_live is None else (b_live,))
     if not all(t.is_cuda for t in every):
         raise RuntimeError(f"{name} runs on the HIP kernels: no CPU path")
@@ -1293,7 +1283,7 @@ def _rank_part_operands(name: str, a_split, b_split, a_ids, b_ids, nA: int, nB: 
 
 def rank_best(a_split: torch.Tensor, b_split: torch.Tensor, a_ids: torch.Tensor, b_ids: torch.Tensor, nA: int, nB: int,
               key_a: torch.Tensor, key_b: torch.Tensor, *, b_live: Optional[torch.Tensor] = None, slabs: Optional[int] = None) -> None:
-    """The first phase of ``rank_counts`` for one (A range, B range) pair, ACCUMULATED (sc_rank_best_bf16, csrc/rank_parts.hip):
+    """The first phase of ``rank_counts`` for one (A range, B range) pair, ACCUMULATED (sc_rank_best_bf16, csrc/rank.hip):
     key_a [nA] / key_b [nB] int32 (the kernel's uint32 keys; ``_rank_key_value`` decodes them, 0 = none) take the maximum of what
     they hold and the pair's largest key over correct, non-NaN candidates.  ``b_live`` [nB] bool / uint8 or None: a row of B with
     b_live == 0 is no candidate and no query, and its slot of ``key_b`` is not touched.  The caller zeroes the keys once, calls this
@@ -1308,7 +1298,7 @@ def rank_best(a_split: torch.Tensor, b_split: torch.Tensor, a_ids: torch.Tensor,
 def rank_ahead(a_split: torch.Tensor, b_split: torch.Tensor, a_ids: torch.Tensor, b_ids: torch.Tensor, nA: int, nB: int,
                key_a: torch.Tensor, key_b: torch.Tensor, ahead_a: torch.Tensor, ahead_b: torch.Tensor, *,
                b_live: Optional[torch.Tensor] = None, slabs: Optional[int] = None) -> None:
-    """The second phase of ``rank_counts`` for one pair, ACCUMULATED (sc_rank_ahead_bf16, csrc/rank_parts.hip): reads the final keys
+    """The second phase of ``rank_counts`` for one pair, ACCUMULATED (sc_rank_ahead_bf16, csrc/rank.hip): reads the final keys
     ``key_a`` [nA] / ``key_b`` [nB] (``rank_best`` over EVERY pair) and adds to ahead_a [nA] / ahead_b [nB] int32 the pair's
     candidates that rank ahead under ``rank_counts``' rule.  ``b_live`` as in ``rank_best``: a dead row's ``ahead_b`` is not touched."""
     nA, nB = int(nA), int(nB)

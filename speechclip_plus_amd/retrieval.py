@@ -37,6 +37,11 @@ def _recall(score: torch.Tensor, query_ids: torch.Tensor, cand_ids: torch.Tensor
     return out
 
 
+def _mean_results(results_AB: dict, results_BA: dict) -> dict:
+    """the third dictionary of every result triple: the mean of the two directions, key by key"""
+    return {key: 0.5 * (results_AB[key] + results_BA[key]) for key in results_AB}
+
+
 def mutualRetrieval(score_per_A: torch.Tensor, score_per_B: torch.Tensor, AB_answers: torch.Tensor,
                     BA_answers: torch.Tensor, recall_at: list, modality_A_title: str = "audio",
                     modality_B_title: str = "image") -> Tuple[dict, dict, dict]:
@@ -49,8 +54,7 @@ def mutualRetrieval(score_per_A: torch.Tensor, score_per_B: torch.Tensor, AB_ans
     b_ids = BA_answers.to(score_per_A.device)
     results_AB = _recall(score_per_A, a_ids, b_ids, recall_at, modality_B_title)
     results_BA = _recall(score_per_B.to(score_per_A.device), b_ids, a_ids, recall_at, modality_A_title)
-    results_mean = {key: 0.5 * (results_AB[key] + results_BA[key]) for key in results_AB}
-    return results_AB, results_BA, results_mean
+    return results_AB, results_BA, _mean_results(results_AB, results_BA)
 
 
 # ------------------------------------------------------------------------------------------------ gallery search
@@ -358,6 +362,16 @@ def hard_negatives(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex, "Compac
 SHARD_LISTS_BYTES = 256 << 20      # the partial lists of one chunk of queries, S * chunk * k * 8 bytes, stay under this
 
 
+def _exchange_counts(mine: Sequence[int], dev, group) -> list:
+    """a few ints of every rank -> [W][len(mine)] on every rank (one all_gather_into_tensor)"""
+    import torch.distributed as dist
+    W = dist.get_world_size(group)
+    m = torch.tensor(list(mine), device=dev, dtype=torch.int64)
+    every = torch.empty(W * m.numel(), device=dev, dtype=torch.int64)
+    dist.all_gather_into_tensor(every, m, group=group)
+    return every.view(W, m.numel()).tolist()
+
+
 class ShardedGalleryIndex(_LiveRows):
     """Consecutive row ranges of one gallery [N, E], each a GalleryIndex, for ``search_sharded``.
 
@@ -401,10 +415,7 @@ class ShardedGalleryIndex(_LiveRows):
             if shard_rows is not None:
                 raise ValueError("ShardedGalleryIndex: shard_rows applies to the local form; with group= every rank's rows are one shard")
             W, rank = dist.get_world_size(group), dist.get_rank(group)
-            mine = torch.tensor([n, self.E, int(ids is not None)], device=gallery.device, dtype=torch.int64)
-            every = torch.empty(W * 3, device=gallery.device, dtype=torch.int64)
-            dist.all_gather_into_tensor(every, mine, group=group)
-            counts, Es, has = (every.view(W, 3)[:, j].tolist() for j in range(3))
+            counts, Es, has = (list(col) for col in zip(*_exchange_counts([n, self.E, int(ids is not None)], gallery.device, group)))
             if len(set(Es)) != 1:
                 raise ValueError(f"ShardedGalleryIndex: E differs between the ranks ({Es})")
             if len(set(has)) != 1:
@@ -508,14 +519,10 @@ def search_sharded(queries: torch.Tensor, index: ShardedGalleryIndex, k: int, co
     own0, own1 = 0, nQ                                                # this rank's queries among all of them
     if index.group is not None:
         import torch.distributed as dist
-        W, rank = dist.get_world_size(index.group), dist.get_rank(index.group)
-        mine = torch.tensor([nQ, int(query_ids is not None)], device=dev, dtype=torch.int64)
-        every = torch.empty(W * 2, device=dev, dtype=torch.int64)
-        dist.all_gather_into_tensor(every, mine, group=index.group)
-        counts, has = every.view(W, 2)[:, 0].tolist(), every.view(W, 2)[:, 1].tolist()
+        counts, has = (list(col) for col in zip(*_exchange_counts([nQ, int(query_ids is not None)], dev, index.group)))
         if len(set(has)) != 1:
             raise ValueError(f"search_sharded: query_ids on some ranks only ({has})")
-        own0 = sum(counts[:rank])
+        own0 = sum(counts[: dist.get_rank(index.group)])
         own1 = own0 + nQ
         queries = _gather_rows(_rows_f32(queries), counts, index.group)
         if query_ids is not None:
@@ -773,6 +780,12 @@ def search_compact(queries: torch.Tensor, gallery: Union[torch.Tensor, CompactGa
 # produces that integer for every row AND every column in the epilogue of the score GEMM ``search`` runs, so recall at any k, median
 # and mean rank in both directions come from two integer vectors and no [nA, nB] array exists (avssl/module/retrieval.py:45-121 on
 # the scores of avssl/model/kwClip.py:447-482).
+def _never_hits(ahead: torch.Tensor, best: torch.Tensor, n_candidates: int) -> torch.Tensor:
+    """the finishing rule of the rank kernel's counts: a query whose ``best`` is not finite - key 0 (no correct, non-NaN, live
+    candidate) came back as -inf; +inf: an overflowed score - gets ``ahead`` = the number of candidates.  -> int64"""
+    return torch.where(torch.isfinite(best), ahead.long(), torch.full((), n_candidates, dtype=torch.int64, device=ahead.device))
+
+
 def mutual_ranks(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex], a_ids: torch.Tensor, b_ids: torch.Tensor, cosine: bool = False,
                  slabs: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """A [nA, E], B [nB, E] (or a GalleryIndex of it), a_ids [nA], b_ids [nB] integer ids; row j of B is a correct candidate for row i
@@ -804,10 +817,7 @@ def mutual_ranks(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex], a_ids: t
     b_ids = b_ids.to(device=dev, dtype=torch.int64).contiguous()
     a_split = _split_in_chunks(A, 0, cosine)
     best_a, ahead_a, best_b, ahead_b = ops.rank_counts(a_split, index.split, a_ids, b_ids, nA, nB, slabs=slabs)
-    # key 0 (no correct, non-NaN candidate) came back as -inf; +inf: an overflowed score
-    ahead_a = torch.where(torch.isfinite(best_a), ahead_a.long(), torch.full((), nB, dtype=torch.int64, device=dev))
-    ahead_b = torch.where(torch.isfinite(best_b), ahead_b.long(), torch.full((), nA, dtype=torch.int64, device=dev))
-    return {"ahead_AB": ahead_a, "ahead_BA": ahead_b, "best_AB": best_a, "best_BA": best_b}
+    return {"ahead_AB": _never_hits(ahead_a, best_a, nB), "ahead_BA": _never_hits(ahead_b, best_b, nA), "best_AB": best_a, "best_BA": best_b}
 
 
 def recall_from_ranks(ahead: torch.Tensor, n_candidates: int, ks: Sequence[int], cand_title: str = "") -> Dict[str, float]:
@@ -829,6 +839,18 @@ def recall_from_ranks(ahead: torch.Tensor, n_candidates: int, ks: Sequence[int],
     return out
 
 
+def _recall_triple(ahead_ab: torch.Tensor, ahead_ba: torch.Tensor, n_b: int, n_a: int, recall_at: list, title_b: str, title_a: str,
+                   rank_stats: bool) -> Tuple[dict, dict, dict]:
+    """the two directions' ``ahead`` vectors, candidate counts and candidate titles -> ``mutualRetrieval``'s (A -> B, B -> A, mean)
+    dictionaries, with ``median_rank`` and ``mean_rank`` in each under ``rank_stats``"""
+    results_AB = recall_from_ranks(ahead_ab, n_b, recall_at, title_b)
+    results_BA = recall_from_ranks(ahead_ba, n_a, recall_at, title_a)
+    if not rank_stats:
+        for res in (results_AB, results_BA):
+            del res["median_rank"], res["mean_rank"]
+    return results_AB, results_BA, _mean_results(results_AB, results_BA)
+
+
 def mutual_recall(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex], AB_answers: torch.Tensor, BA_answers: torch.Tensor,
                   recall_at: list, modality_A_title: str = "audio", modality_B_title: str = "image", cosine: bool = False,
                   slabs: Optional[int] = None, rank_stats: bool = False) -> Tuple[dict, dict, dict]:
@@ -840,31 +862,15 @@ def mutual_recall(A: torch.Tensor, B: Union[torch.Tensor, GalleryIndex], AB_answ
     if AB_answers.dim() != 1 or BA_answers.dim() != 1:
         raise AssertionError("answers must be 1-d id vectors")
     ranks = mutual_ranks(A, B, AB_answers, BA_answers, cosine=cosine, slabs=slabs)
-    nA, nB = AB_answers.numel(), BA_answers.numel()
-    results_AB = recall_from_ranks(ranks["ahead_AB"], nB, recall_at, modality_B_title)
-    results_BA = recall_from_ranks(ranks["ahead_BA"], nA, recall_at, modality_A_title)
-    if not rank_stats:
-        for res in (results_AB, results_BA):
-            del res["median_rank"], res["mean_rank"]
-    results_mean = {key: 0.5 * (results_AB[key] + results_BA[key]) for key in results_AB}
-    return results_AB, results_BA, results_mean
+    return _recall_triple(ranks["ahead_AB"], ranks["ahead_BA"], BA_answers.numel(), AB_answers.numel(), recall_at, modality_B_title,
+                          modality_A_title, rank_stats)
 
 
 # ------------------------------------------------------------------------------------------------ ranks over a sharded gallery
-# ``mutual_ranks`` wants all of A and all of B in one GalleryIndex.  csrc/rank_parts.hip runs its two phases as accumulating entries
+# ``mutual_ranks`` wants all of A and all of B in one GalleryIndex.  csrc/rank.hip also runs its two phases as accumulating entries
 # per (A, shard) pair: every shard's "best" first - between ranks the row keys meet in an all-reduce(MAX) -, then every shard's
 # "ahead".  A score depends only on its row of A, its row of B and the fixed K order, so the ranks are those of the whole gallery,
 # exactly: integers, no tolerance.
-def _exchange_counts(mine: Sequence[int], dev, group) -> list:
-    """a few ints of every rank -> [W][len(mine)] on every rank (one all_gather_into_tensor)"""
-    import torch.distributed as dist
-    W = dist.get_world_size(group)
-    m = torch.tensor(list(mine), device=dev, dtype=torch.int64)
-    every = torch.empty(W * m.numel(), device=dev, dtype=torch.int64)
-    dist.all_gather_into_tensor(every, m, group=group)
-    return every.view(W, m.numel()).tolist()
-
-
 def mutual_ranks_sharded(A: torch.Tensor, index: ShardedGalleryIndex, a_ids: torch.Tensor, cosine: bool = False) -> dict:
     """``mutual_ranks`` of A [nA, E] (ids ``a_ids`` [nA] int64) against a ShardedGalleryIndex built with ``ids=``: row j of the gallery
     is a correct candidate of row i of A iff index.ids[j] == a_ids[i].  -> {"ahead_AB" [nA] int64, "best_AB" [nA] fp32, "ahead_BA" [N]
@@ -874,7 +880,7 @@ def mutual_ranks_sharded(A: torch.Tensor, index: ShardedGalleryIndex, a_ids: tor
     A -> B, ``n_A`` for B -> A.  ``cosine`` applies to A (the index carries its own choice).
 
     A is split once; ops.rank_best runs over every shard with the shard's ids and ``live`` mask, then ops.rank_ahead over every
-    shard (csrc/rank_parts.hip).  No [nA, N] matrix exists.
+    shard (csrc/rank.hip).  No [nA, N] matrix exists.
 
     Distributed index (``index.group``): the call is COLLECTIVE.  Every rank passes its OWN rows of A and their ids (the counts may
     differ, 0 is legal); they are all-gathered, every rank runs "best" for all of A against its shard, the row keys are combined by
@@ -925,9 +931,7 @@ def mutual_ranks_sharded(A: torch.Tensor, index: ShardedGalleryIndex, a_ids: tor
         dist.all_reduce(ahead_a, op=dist.ReduceOp.SUM, group=group)
     n_live = index.n_live
     best_a, best_b = ops._rank_key_value(key_a), ops._rank_key_value(key_b)
-    # key 0 (no correct, non-NaN, live candidate) came back as -inf; +inf: an overflowed score
-    ahead_a = torch.where(torch.isfinite(best_a), ahead_a, torch.full((), n_live, dtype=torch.int64, device=dev))
-    ahead_b = torch.where(torch.isfinite(best_b), ahead_b.long(), torch.full((), nAll, dtype=torch.int64, device=dev))
+    ahead_a, ahead_b = _never_hits(ahead_a, best_a, n_live), _never_hits(ahead_b, best_b, nAll)
     if any(shard.live is not None for shard in index.shards):
         live = torch.cat([torch.ones(shard.N, device=dev, dtype=torch.bool) if shard.live is None else shard.live for shard in index.shards])
         ahead_b = torch.where(live, ahead_b, torch.full((), -1, dtype=torch.int64, device=dev))     # best_b is -inf there: its key was never written
@@ -950,10 +954,4 @@ def mutual_recall_sharded(A: torch.Tensor, index: ShardedGalleryIndex, AB_answer
         if sum(c[1] for c in counts):
             ahead_ba = _gather_rows(ahead_ba.contiguous(), [c[1] for c in counts], index.group)
     ahead_ba = ahead_ba[ahead_ba >= 0]                                # a removed row is no query
-    results_AB = recall_from_ranks(ahead_ab, ranks["n_B_live"], recall_at, modality_B_title)
-    results_BA = recall_from_ranks(ahead_ba, ranks["n_A"], recall_at, modality_A_title)
-    if not rank_stats:
-        for res in (results_AB, results_BA):
-            del res["median_rank"], res["mean_rank"]
-    results_mean = {key: 0.5 * (results_AB[key] + results_BA[key]) for key in results_AB}
-    return results_AB, results_BA, results_mean
+    return _recall_triple(ahead_ab, ahead_ba, ranks["n_B_live"], ranks["n_A"], recall_at, modality_B_title, modality_A_title, rank_stats)

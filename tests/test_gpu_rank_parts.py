@@ -1,9 +1,16 @@
-"""GPU: ops.rank_best / ops.rank_ahead (csrc/rank_parts.hip) alone - the accumulate contract, the ranges and the removed-row mask.
+"""GPU: ops.rank_best / ops.rank_ahead (csrc/rank.hip) alone - the accumulate contract, the ranges and the removed-row mask.
 
 THE INVARIANT: a split-bf16 score depends only on its row of A, its row of B and the fixed K order.  So "best" over every (A range,
 B range) pair followed by "ahead" over every pair gives, bit for bit, the keys and counts ``ops.rank_counts`` gives on the whole of A
-against the whole of B - and with a mask, on the gallery with the dead rows physically deleted.  Every expectation is exact: Gaussian
-data against ``rank_counts`` (csrc/rank.hip, not edited), integer data (exact scores) against tests/rank_cases.py's rule on the CPU.
+against the whole of B - and with a mask, on the gallery with the dead rows physically deleted.  Every expectation is exact.
+
+THE ORACLE.  ``rank_best`` / ``rank_ahead`` and ``rank_counts`` are three entries of ONE kernel, so holding one against another is
+the code under test compared with itself.  On Gaussian data the expectation therefore comes from no rank kernel: ``_oracle`` takes
+the [nA, nB] fp32 score matrix from ``ops.cosine_scores_split`` on the same rows - the GEMM, another kernel, whose bits are the
+tile's (tests/test_gpu_wide_search.py: "both routes agree bit for bit") -, copies it to the CPU, cuts it to [:nA, :nB] and applies
+tests/rank_cases.py's rule: exact integers for ``ahead``, the fp32 maximum as fp64 for ``best``.  Both ``_parts(...)`` and
+``ops.rank_counts(...)`` are held against it with no tolerance, and against each other bit for bit.  Integer data (exact scores)
+is held against the same rule on an int64 product the CPU computes.
 
 Shapes: E = 64 and E = 100 (pads to 128); nA in {1, 127, 128, 129, 300}, nB in {1, 129, 257, 300}: one tile and several, 1-row and
 1-column tails; B cut into ranges of 100 rows (tile tails inside the gallery) and 1 + 256 + 43 rows, each range split on its own."""
@@ -61,6 +68,15 @@ def _parts(A, B, a_ids, b_ids, a_ranges=None, b_ranges=None, live=None, slabs=No
     return {k: v.cpu() for k, v in buf.items()}
 
 
+def _oracle(A, B, a_ids, b_ids):
+    """the rule of tests/rank_cases.py on the fp32 scores the GEMM writes for the same rows (no rank kernel runs) -> its dict"""
+    from speechclip_plus_amd import ops
+    b_split = ops.split3_bf16(B.to(DEV), 1)
+    scores = ops.cosine_scores_split(A.to(DEV), None, b_split, b_split.shape[0])
+    torch.cuda.synchronize()
+    return rk.both_directions(scores.cpu()[: A.shape[0], : B.shape[0]].double(), a_ids, b_ids)
+
+
 def _whole(A, B, a_ids, b_ids, slabs=None):
     """``ops.rank_counts`` on one (A, B) pair -> (best_a fp32, ahead_a int32, best_b, ahead_b) on the CPU"""
     from speechclip_plus_amd import ops
@@ -83,10 +99,14 @@ def _same_bits(got, want, cols=None):
 
 
 def _finished(got, n_b, n_a, cols=None):
-    """mutual_ranks' convention on the raw vectors: a query whose best is not finite never hits -> tests/rank_cases.py's dict"""
-    best_a, best_b = _value(got["key_a"]), _value(got["key_b"])
-    ahead_a = torch.where(torch.isfinite(best_a), got["ahead_a"].long(), torch.full((), n_b, dtype=torch.int64))
-    ahead_b = torch.where(torch.isfinite(best_b), got["ahead_b"].long(), torch.full((), n_a, dtype=torch.int64))
+    """mutual_ranks' convention on the raw vectors of ``_parts`` (or on ``_whole``'s tuple): a query whose best is not finite never
+    hits -> tests/rank_cases.py's dict"""
+    if isinstance(got, tuple):
+        best_a, ahead_a, best_b, ahead_b = got
+    else:
+        best_a, ahead_a, best_b, ahead_b = _value(got["key_a"]), got["ahead_a"], _value(got["key_b"]), got["ahead_b"]
+    ahead_a = torch.where(torch.isfinite(best_a), ahead_a.long(), torch.full((), n_b, dtype=torch.int64))
+    ahead_b = torch.where(torch.isfinite(best_b), ahead_b.long(), torch.full((), n_a, dtype=torch.int64))
     if cols is not None:
         ahead_b, best_b = ahead_b[cols], best_b[cols]
     return {"ahead_AB": ahead_a, "best_AB": best_a, "ahead_BA": ahead_b, "best_BA": best_b}
@@ -98,6 +118,14 @@ def _assert_equals_reference(got, ref):
         assert torch.equal(got[key], ref[key]), (key, bad.tolist(), got[key][bad].tolist(), ref[key][bad].tolist())
     for key in ("best_AB", "best_BA"):
         assert torch.equal(got[key].double(), ref[key]), key             # exact integers (or -inf): the fp32 value IS the reference
+
+
+def _assert_both_equal_the_oracle(got, want, ref, n_b, n_a, cols=None):
+    """``_parts``' vectors and ``_whole``'s tuple (computed on the live columns ``cols``) each equal the oracle ``ref`` exactly, and
+    each other bit for bit"""
+    _assert_equals_reference(_finished(got, n_b, n_a, cols), ref)
+    _assert_equals_reference(_finished(want, n_b, n_a), ref)
+    assert _same_bits(got, want, cols)
 
 
 @functools.lru_cache(maxsize=None)
@@ -120,9 +148,9 @@ def _ints(nA, nB, E):
 @pytest.mark.parametrize("nA", NAS)
 def test_one_pair_without_a_mask_is_rank_counts_bit_for_bit(nA, nB, E):
     A, B, a_ids, b_ids = _gauss(nA, nB, E)
-    want = _whole(A, B, a_ids, b_ids, 1)
+    want, ref = _whole(A, B, a_ids, b_ids, 1), _oracle(A, B, a_ids, b_ids)
     for S in (1, 2, 3, None, None):                                   # the default twice: a second run gives the same bits
-        assert _same_bits(_parts(A, B, a_ids, b_ids, slabs=S), want), S
+        _assert_both_equal_the_oracle(_parts(A, B, a_ids, b_ids, slabs=S), want, ref, nB, nA)
 
 
 # ---------------------------------------------------------------------------------------------------- 2. B in ranges
@@ -132,7 +160,8 @@ def test_one_pair_without_a_mask_is_rank_counts_bit_for_bit(nA, nB, E):
 def test_ranges_of_b_accumulate_to_the_whole_gallery(nA, sizes, E):
     nB = 300
     A, B, a_ids, b_ids = _gauss(nA, nB, E)
-    assert _same_bits(_parts(A, B, a_ids, b_ids, b_ranges=_ranges(nB, sizes)), _whole(A, B, a_ids, b_ids))
+    _assert_both_equal_the_oracle(_parts(A, B, a_ids, b_ids, b_ranges=_ranges(nB, sizes)), _whole(A, B, a_ids, b_ids),
+                                  _oracle(A, B, a_ids, b_ids), nB, nA)
     q, gal, a_ids, b_ids = _ints(nA, nB, E)
     got = _parts(q.float(), gal.float(), a_ids, b_ids, b_ranges=_ranges(nB, sizes))
     _assert_equals_reference(_finished(got, nB, nA), rk.both_directions(q.long() @ gal.long().t(), a_ids, b_ids))
@@ -145,9 +174,9 @@ def test_ranges_of_b_accumulate_to_the_whole_gallery(nA, sizes, E):
 def test_two_halves_of_a_accumulate_in_the_b_side_buffers(nA, nB, E):
     A, B, a_ids, b_ids = _gauss(nA, nB, E)
     halves = _ranges(nA, (nA // 2, nA - nA // 2))
-    want = _whole(A, B, a_ids, b_ids)
-    assert _same_bits(_parts(A, B, a_ids, b_ids, a_ranges=halves), want)
-    assert _same_bits(_parts(A, B, a_ids, b_ids, a_ranges=halves, b_ranges=_ranges(nB, 100)), want)
+    want, ref = _whole(A, B, a_ids, b_ids), _oracle(A, B, a_ids, b_ids)
+    _assert_both_equal_the_oracle(_parts(A, B, a_ids, b_ids, a_ranges=halves), want, ref, nB, nA)
+    _assert_both_equal_the_oracle(_parts(A, B, a_ids, b_ids, a_ranges=halves, b_ranges=_ranges(nB, 100)), want, ref, nB, nA)
 
 
 # ---------------------------------------------------------------------------------------------------- 4. placement across ranges
@@ -224,21 +253,22 @@ def test_a_mask_equals_the_gallery_without_the_dead_rows(E):
     A, B, a_ids, b_ids = _gauss(300, 300, E)
     live = torch.rand(300, generator=torch.Generator().manual_seed(E)) > 0.3
     live[100:200] = False                                             # a fully dead range
-    want = _whole(A, B[live], a_ids, b_ids[live])
+    want, ref, n_live = _whole(A, B[live], a_ids, b_ids[live]), _oracle(A, B[live], a_ids, b_ids[live]), int(live.sum())
     poisoned = B.clone()
     poisoned[~live] = float("nan")
     for sizes in (300, 100, (1, 256, 43)):
         for gallery in (B, poisoned):
-            assert _same_bits(_parts(A, gallery, a_ids, b_ids, b_ranges=_ranges(300, sizes), live=live), want, cols=live), sizes
+            _assert_both_equal_the_oracle(_parts(A, gallery, a_ids, b_ids, b_ranges=_ranges(300, sizes), live=live), want, ref, n_live, 300,
+                                          cols=live)
 
 
 @pytest.mark.parametrize("nA,nB", ((129, 257), (300, 300)))
 def test_a_mask_of_ones_equals_no_mask(nA, nB):
     A, B, a_ids, b_ids = _gauss(nA, nB, 100)
     ones = torch.ones(nB, dtype=torch.bool)
-    want = _whole(A, B, a_ids, b_ids)
+    want, ref = _whole(A, B, a_ids, b_ids), _oracle(A, B, a_ids, b_ids)
     for sizes in (nB, 100):
-        assert _same_bits(_parts(A, B, a_ids, b_ids, b_ranges=_ranges(nB, sizes), live=ones), want)
+        _assert_both_equal_the_oracle(_parts(A, B, a_ids, b_ids, b_ranges=_ranges(nB, sizes), live=ones), want, ref, nB, nA)
 
 
 # ---------------------------------------------------------------------------------------------------- 6. the accumulate contract

@@ -26,8 +26,10 @@ def test_symbols_declared_bound_and_exported():
     for name in NAMES:
         assert name in declared and name in _lib.SIGNATURES and hasattr(lib, name), name
     assert lib.sc_abi_version() == 7
-    assert "rank_parts.hip" in build.SOURCES and "rank.hip" in build.SOURCES
-    assert os.path.exists(os.path.join(build.CSRC, "rank_parts.hip"))
+    assert "rank.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "rank.hip"))
+    assert "rank_parts.hip" not in build.SOURCES and not os.path.exists(os.path.join(build.CSRC, "rank_parts.hip"))
+    for name in NAMES + ("sc_rank_counts_bf16",):                     # one file, three entries
+        assert name in declared and name in _lib.SIGNATURES and hasattr(lib, name), name
     assert callable(ops.rank_best) and callable(ops.rank_ahead)
     assert callable(sc.mutual_ranks_sharded) and callable(sc.mutual_recall_sharded)
     assert "mutual_ranks_sharded" in sc.__all__ and "mutual_recall_sharded" in sc.__all__

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sharded ranks (retrieval.mutual_ranks_sharded, csrc/rank_parts.hip) against ``mutual_ranks`` on the whole gallery, on
+"""Sharded ranks (retrieval.mutual_ranks_sharded, csrc/rank.hip's two accumulating entries) against ``mutual_ranks`` on the whole gallery, on
 tools/bench_search_sharded.py's protocol: ONE process, the two sides alternating in blocks after a warm-up at every switch (and
 alternating who goes first), device events around every block, ms per call, the median of five blocks.  One JSON line per run with
 the median and every block of each side and the spread of the blocks.
