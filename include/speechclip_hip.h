@@ -1170,6 +1170,27 @@ int sc_image_resample_v_norm(const uint8_t* mid, int64_t mid_bytes, const int64_
                              sc_bf16* A, int32_t Kp, const sc_segments* seg, int32_t P, int32_t B, int32_t S, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Raw-audio input of the speech encoder: PCM of any rate to 16 kHz mono fp32 on the device - the work of the reference's
+ * librosa.load(path, sr=16_000) behind the decoder (avssl/data/base_dataset.py:81, example.py:21): to float, to mono, resample.  The
+ * resampler is the project's own, in closed form.  g = gcd(sr, 16000), P = sr / g, Q = 16000 / g, c = 0.99 min(P, Q), W = 6,
+ * x[j] = 0 outside 0 <= j < n_in, u = c (j - m P / Q) / P:
+ *     y[m] = sum_j x[j] (c / P) sinc(u) cos^2(pi u / (2 W))   over |u| < W,      n_out = ceil(n_in Q / P)
+ * a Hann-windowed sinc, six zero crossings, roll-off 0.99 (the default filter of torchaudio's resample; NOT the reference's soxr_hq -
+ * no bit parity with it is claimed).  int16 samples are x / 32768; channels are averaged in fp32, (x0 + x1 + ...) / ch in channel order.
+ * Additive in round 25; sc_abi_version() stays 7.
+ *   sc_audio_resample: one launch for n_utt utterances of ONE source rate.  src: the packed PCM (interleaved frames), int16 if is_i16
+ *       else fp32; desc [n_utt][5] int64: byte offset into src, n_in (frames), ch (1 .. 8), n_out, output row.  table [Q][taps] fp32 and
+ *       first [Q] int32 (speechclip_plus_amd/audio_prep.py: resample_table): output m = q Q + i reads x[q P + first[i] + t] with
+ *       coefficient table[i][t], t ascending, one fmaf each; P = Q = 1 (16 kHz) converts and down-mixes only, table / first unused.
+ *       out [out_rows][ld_out] fp32: row desc.row gets its n_out samples and zeros up to Lout - every element of the rows named is
+ *       written.  tile: outputs per workgroup, a multiple of 256 (audio_prep.tile_outputs).  q P is formed in 64 bits.  A sample outside
+ *       [0, n_in) of its utterance is never loaded; an utterance that does not fit src_bytes reads nothing and yields zeros.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_audio_resample(const void* src, int64_t src_bytes, int32_t is_i16, const int64_t* desc, int32_t n_utt, const float* table,
+                      const int32_t* first, int32_t P, int32_t Q, int32_t taps, int32_t tile, float* out, int64_t ld_out,
+                      int32_t out_rows, int32_t Lout, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser step on a flat fp32 parameter buffer: torch.optim.Adam semantics (L2 weight decay added to
  * the gradient), gradient clipping by global norm folded in (avssl/model/kwClip.py:646-674 +
  * trainer.gradient_clip_val).  sumsq: partial sums of squares for the global norm.

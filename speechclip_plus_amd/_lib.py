@@ -245,6 +245,8 @@ SIGNATURES = {
     "sc_image_resample_h_u8": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p],
     "sc_image_resample_v_norm": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(Segments), c_int, c_int,
                                  c_int, c_void_p],
+    "sc_audio_resample": [c_void_p, c_i64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_int, c_int,
+                          c_void_p],
     "sc_rows_scatter_bf16": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "sc_cif_head_fwd": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, ctypes.c_uint32, c_float, ctypes.c_uint32, c_void_p],
     "sc_cif_head_bwd": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_float,

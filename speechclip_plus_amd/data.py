@@ -5,6 +5,9 @@ Semantics kept: a ``wav_len`` key is derived from the un-padded waveforms, ``wav
 utterance of the batch (batch first), other tensors are stacked, non-tensor fields (ids, lengths) become int64 tensors.  One
 addition: an ``image`` column of raw ``uint8 [H, W, 3]`` tensors of UNEQUAL sizes (which the reference's stack refuses) is packed into
 ``image`` (1-D uint8) + ``image_hw`` (int64 [B, 2], with a host twin) for the device-side CLIP preprocessing (image_prep.py).
+Likewise a batch whose rows carry a ``wav_sr`` key holds raw PCM (any rate, ``int16`` / ``float32``, ``[frames]`` or ``[frames, ch]``): its
+``wav`` column is packed into one 1-D buffer + ``wav_frames`` / ``wav_ch`` / ``wav_sr`` (int64 [B], with host twins) for the device-side
+down-mix and resampling to 16 kHz (audio_prep.py); such a batch has no ``wav_len`` - ``model.forward`` derives it.
 
 Round 5 - the way a batch reaches the device (avssl/model/kwClip.py:145-147 receives what Lightning's transfer produced):
 ``transfer_batch_to_device`` is the body of the LightningModule hook of the same name.  It keeps what a plain ``.to(device)`` of
@@ -31,6 +34,9 @@ def attach_host_lengths(wav_len: torch.Tensor, host: Optional[Sequence[int]] = N
     return wav_len
 
 
+_HOST_TWINS = ("wav_len", "wav_frames", "wav_ch", "wav_sr")      # int64 [B] columns whose values stay readable on the host
+
+
 def transfer_batch_to_device(batch: dict, device, copy_stream: Optional["torch.cuda.Stream"] = None) -> dict:
     """Body of ``LightningModule.transfer_batch_to_device(batch, device, dataloader_idx)`` for the batch dict of ``collate_general``.
     Every tensor goes to ``device``; ``wav_len`` keeps a host twin; EVERY host -> device copy runs on ``copy_stream`` (default: the
@@ -48,10 +54,11 @@ def transfer_batch_to_device(batch: dict, device, copy_stream: Optional["torch.c
         out = {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
         if isinstance(batch.get("image_hw"), torch.Tensor):
             _keep_sizes(out["image_hw"], batch["image_hw"])
-        if isinstance(batch.get("wav_len"), torch.Tensor):
-            host = getattr(batch["wav_len"], "_sc_host", None) or (batch["wav_len"].tolist() if not batch["wav_len"].is_cuda else None)
-            if host is not None:
-                attach_host_lengths(out["wav_len"], host)
+        for k in _HOST_TWINS:
+            if isinstance(batch.get(k), torch.Tensor):
+                host = getattr(batch[k], "_sc_host", None) or (batch[k].tolist() if not batch[k].is_cuda else None)
+                if host is not None:
+                    attach_host_lengths(out[k], host)
         return out
     from . import ops
     cs = copy_stream if copy_stream is not None else ops.shared_stream("h2d", device, priority=-1)
@@ -65,14 +72,14 @@ def transfer_batch_to_device(batch: dict, device, copy_stream: Optional["torch.c
             if v.is_cuda:                      # device -> device (another GPU): ordered on the CALLER's stream like any torch op - its
                 with torch.cuda.stream(main):  # producer may still be queued there, and the copy-stream event must not stand in for it
                     out[k] = v.to(device, non_blocking=True)
-                if k == "wav_len" and getattr(v, "_sc_host", None) is not None:
+                if k in _HOST_TWINS and getattr(v, "_sc_host", None) is not None:
                     attach_host_lengths(out[k], v._sc_host)
                 if k == "image_hw":
                     _keep_sizes(out[k], v)
                 continue
             src = v if v.is_pinned() else v.pin_memory()
             d = src.to(device, non_blocking=True)
-            if k == "wav_len":
+            if k in _HOST_TWINS:
                 attach_host_lengths(d, getattr(v, "_sc_host", None) or v.tolist())
             if k == "image_hw":
                 _keep_sizes(d, v)
@@ -112,11 +119,22 @@ def collate_general(batch: Sequence[dict], pin_memory: bool = False) -> Dict[str
     # does not survive the worker -> main hand-over anyway: there, leave it to DataLoader(pin_memory=True) + transfer_batch_to_device
     in_worker = torch.utils.data.get_worker_info() is not None
     pin = lambda t: bool(pin_memory) and not in_worker and torch.cuda.is_available() and (t is None or not t.is_cuda)     # every tensor
-    derive_len = "wav" in keys and isinstance(batch[0]["wav"], torch.Tensor)
+    raw_audio = "wav_sr" in keys and "wav" in keys
+    derive_len = "wav" in keys and isinstance(batch[0]["wav"], torch.Tensor) and not raw_audio
     out: Dict[str, torch.Tensor] = {}
     for k in keys:
         vals = [row[k] for row in batch]
-        if isinstance(vals[0], torch.Tensor):
+        if raw_audio and k == "wav":
+            # raw PCM of any rate, int16 / fp32, [frames] or [frames, ch]: packed samples + frame counts, channels and rates;
+            # model.forward down-mixes and resamples them on the device (audio_prep) into the padded batch and wav_len
+            from .audio_prep import as_entries, pack
+            raw = pack(as_entries(vals, [row["wav_sr"] for row in batch]), pin_memory=pin(None))       # every limit, here
+            out[k] = raw.packed
+            for name, host in (("wav_frames", raw.frames), ("wav_ch", raw.ch), ("wav_sr", raw.sr)):
+                out[name] = attach_host_lengths(torch.tensor(host, dtype=torch.long, pin_memory=pin(None)))
+        elif raw_audio and k == "wav_sr":
+            pass                                                   # written with "wav"
+        elif isinstance(vals[0], torch.Tensor):
             if k == "wav":
                 L = max(int(v.shape[0]) for v in vals)
                 padded = torch.zeros((len(vals), L) + tuple(vals[0].shape[1:]), dtype=vals[0].dtype, pin_memory=pin(vals[0]),

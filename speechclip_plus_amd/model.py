@@ -385,14 +385,27 @@ class KWClip_GeneralTransformer(nn.Module):
         self.log_dict(logged, sync_dist=True)
         return recall_AB, recall_BA, recall_mean
 
-    def processWavs(self, wav):
+    def processWavs(self, wav, sample_rate=None):
+        """``sample_rate`` None: ``wav`` is 16 kHz mono fp32 and goes on as it is.  Otherwise (one int, or one per item) ``wav`` is raw
+        PCM - a list of int16 / fp32 arrays or tensors, 1-D or [frames, channels], or paths of 16-bit WAV files - and is down-mixed and
+        resampled to 16 kHz on the device first (audio_prep.prep_audio): a padded fp32 batch and its lengths."""
+        if sample_rate is not None:
+            from .audio_prep import prep_audio
+            if not isinstance(wav, (list, tuple)):
+                wav = [wav]                                    # one utterance
+            return prep_audio(list(wav), sample_rate, self._device)
         wav_len = [len(x) for x in wav]
         return wav, wav_len
 
     # ---------------------------------------------------------------------------------------------
     def forward(self, batch: dict) -> tuple:
         """kwClip.py:839-963."""
-        wav, wav_len, image, id = batch["wav"], batch["wav_len"], batch["image"], batch["id"]
+        if batch.get("wav_sr") is not None:                    # raw PCM (data.collate_general): packed samples + host frame counts, channels, rates
+            from .audio_prep import RawAudioBatch, prep_audio
+            wav, wav_len = prep_audio(RawAudioBatch(batch["wav"], batch["wav_frames"], batch["wav_ch"], batch["wav_sr"]), None, self._device)
+        else:
+            wav, wav_len = batch["wav"], batch["wav_len"]
+        image, id = batch["image"], batch["id"]
         audio_feat, audio_feat_len = self.forward_audio(wav, wav_len, return_hidden_states=False)
         if batch.get("image_hw") is not None:                  # ragged raw images (data.collate_general): packed bytes + host sizes
             image = (image, batch["image_hw"])
@@ -816,9 +829,9 @@ class KWClip_GeneralTransformer(nn.Module):
         return cls.from_reference_checkpoint(config, ckpt["state_dict"], **kw)
 
     # ---------------------------------------------------------------------------------------------
-    def encode_speech(self, wav) -> dict:
-        """kwClip.py:1042-1091 (un-normalised branch output)."""
-        wav, wav_len = self.processWavs(wav)
+    def encode_speech(self, wav, sample_rate=None) -> dict:
+        """kwClip.py:1042-1091 (un-normalised branch output).  ``sample_rate``: ``wav`` is raw PCM at that rate (processWavs)."""
+        wav, wav_len = self.processWavs(wav, sample_rate)
         audio_feat, audio_feat_len = self.forward_audio(wav, wav_len)
         if self.cascaded_branch is not None:
             output = self.cascaded_branch(audio_feat=audio_feat, audio_feat_len=audio_feat_len)
@@ -881,16 +894,16 @@ class KWClip_GeneralTransformer(nn.Module):
             return search_compact(queries, gallery, k, query_ids=query_ids, gallery_ids=gallery_ids)[:2]
         return search(queries, gallery, k, query_ids=query_ids, gallery_ids=gallery_ids)
 
-    def extract_keywords(self, wav) -> dict:
+    def extract_keywords(self, wav, sample_rate=None) -> dict:
         """kwClip.py:1093-1103, the inference entry of the keyword recipes: ``wav`` one 1-D waveform (or a list of them) ->
         ``{"vq_results", "dsample_results"}`` with ``vq_results["targets"]`` flattened to a list of ORIGINAL CLIP token ids
         (``clip.reducedl2Original`` when the vocabulary is reduced; slots past an utterance's ``dsample_feats_length`` included, as
-        in the reference)."""
+        in the reference).  ``sample_rate``: ``wav`` is raw PCM at that rate (processWavs)."""
         if self.cascaded_branch is None:
             raise RuntimeError("extract_keywords needs a keyword branch (cascaded+ / hybrid+ recipe)")
         if isinstance(wav, torch.Tensor) and wav.dim() == 1:
             wav = [wav]
-        wav, wav_len = self.processWavs(wav)
+        wav, wav_len = self.processWavs(wav, sample_rate)
         with torch.no_grad():
             audio_feat, audio_feat_len = self.forward_audio(wav, wav_len)
             output = self.cascaded_branch(audio_feat=audio_feat, audio_feat_len=audio_feat_len, otherInputs={})
@@ -901,10 +914,10 @@ class KWClip_GeneralTransformer(nn.Module):
         vq_results["targets"] = targets
         return {"vq_results": vq_results, "dsample_results": dsample_results}
 
-    def feature_extractor_s3prl(self, wav) -> Tuple[torch.Tensor, Tuple]:
+    def feature_extractor_s3prl(self, wav, sample_rate=None) -> Tuple[torch.Tensor, Tuple]:
         """kwClip.py:965-997: the HuBERT states (fresh tensors: the encoder clones what it hands out) followed by the branch
-        layer's hidden states (full-sequence layer on the library's kernels)."""
-        wav, wav_len = self.processWavs(wav)
+        layer's hidden states (full-sequence layer on the library's kernels).  ``sample_rate``: ``wav`` is raw PCM at that rate."""
+        wav, wav_len = self.processWavs(wav, sample_rate)
         audio_feat, audio_len, hidden_states = self.forward_audio(wav, wav_len, return_hidden_states=True)
         assert isinstance(hidden_states, tuple)
         with torch.no_grad():

@@ -2294,6 +2294,24 @@ def image_resample_v_norm(mid: torch.Tensor, tab: torch.Tensor, lut: torch.Tenso
     return out, A
 
 
+def audio_resample(src: torch.Tensor, desc: torch.Tensor, table: Optional[torch.Tensor], first: Optional[torch.Tensor], P: int, Q: int,
+                   taps: int, tile: int, out: torch.Tensor) -> torch.Tensor:
+    """out [rows, Lout] fp32 <- the utterances of ONE source rate that ``desc`` (int64 [n, 5]: byte offset, frames, channels, n_out,
+    output row) names in the packed PCM ``src`` (1-D int16 or fp32), converted, down-mixed and resampled to 16 kHz; zeros behind each
+    n_out (sc_audio_resample).  ``table`` [Q, taps] fp32 / ``first`` [Q] int32: audio_prep.resample_table; None at P = Q = 1."""
+    assert src.dim() == 1 and src.is_contiguous() and src.dtype in (torch.int16, torch.float32) and src.numel() > 0
+    assert desc.dtype == torch.int64 and desc.dim() == 2 and desc.shape[1] == 5 and desc.is_contiguous() and desc.shape[0] >= 1
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[1] >= 1 and out.stride(0) >= out.shape[1]
+    if P == 1 and Q == 1:
+        table = first = None
+    else:
+        assert table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (Q, taps)
+        assert first.dtype == torch.int32 and first.is_contiguous() and tuple(first.shape) == (Q,)
+    check(lib().sc_audio_resample(_p(src), src.numel() * src.element_size(), int(src.dtype == torch.int16), _p(desc), desc.shape[0], _p(table),
+                                  _p(first), P, Q, taps, tile, _p(out), out.stride(0), out.shape[0], out.shape[1], _stream()), "sc_audio_resample")
+    return out
+
+
 def rows_scatter(d: torch.Tensor, row: torch.Tensor, M: int, SEG: int) -> torch.Tensor:
     """dX [M, W] bf16: zero except dX[row[b]] = bf16(d[b]) (row[b] inside segment b of SEG rows)"""
     B, W = d.shape
