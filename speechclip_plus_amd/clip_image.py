@@ -22,13 +22,14 @@ csrc/image_prep.hip) and writes the patch GEMM's operand directly; ``prep_image`
 import torch
 from torch import nn
 
+from ._lib import DEFINES
 from .clip_text import ResidualAttentionBlock
 
 CLIP_IMAGE_ARCHS = {"ViT-B/32": dict(width=768, layers=12, heads=12, patch=32, resolution=224, embed_dim=512),
                     "ViT-L/14": dict(width=1024, layers=24, heads=16, patch=14, resolution=224, embed_dim=768)}
 CLIP_IMAGE_MEAN = (0.48145466, 0.4578275, 0.40821073)       # the normalisation of CLIP's published preprocessing
 CLIP_IMAGE_STD = (0.26862954, 0.26130258, 0.27577711)
-SEG_ROWS = 8                                                 # SC_SEG_ROWS: an image's row pitch is a multiple of this
+SEG_ROWS = DEFINES["SC_SEG_ROWS"]                            # 8: an image's row pitch is a multiple of this
 
 
 def patch_k(patch: int) -> int:

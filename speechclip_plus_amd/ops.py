@@ -8,7 +8,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import RtGemmArgs, RtLnArgs, RtLnBwdArgs, GemmArgs, HubertLayerArgs, Segments, check, diag_lib, lib
+from ._lib import DEFINES, RtGemmArgs, RtLnArgs, RtLnBwdArgs, GemmArgs, HubertLayerArgs, Segments, check, diag_lib, lib
 
 
 def _p(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
@@ -41,7 +41,7 @@ class RowSegments:
 
     ``pitch`` [B] rows per utterance; ``keys`` [B] the key count that sorts the attention work list (longest first)."""
 
-    GRAN = 8             # SC_SEG_ROWS: pitches are multiples of this; one chunk-table entry per GRAN rows
+    GRAN = DEFINES["SC_SEG_ROWS"]      # 8: pitches are multiples of this; one chunk-table entry per GRAN rows
 
     def __init__(self, pitch, keys, device, storage: Optional[torch.Tensor] = None, keys_known: bool = True):
         host, self.row0_host, self.n_work = self.host_tables(pitch, keys, keys_known)
@@ -251,7 +251,7 @@ def hubert_layer_fwd(x: torch.Tensor, out: torch.Tensor, valid_len: torch.Tensor
     check(L.sc_hubert_layer_fwd(ctypes.byref(a), _stream()), "sc_hubert_layer_fwd", L)
 
 
-ATTN_SLACK = 64     # SC_ATTN_SLACK: rows behind qk / elements behind vt that a 64-key attention tile may read past the last utterance
+ATTN_SLACK = DEFINES["SC_ATTN_SLACK"]     # 64: rows behind qk / elements behind vt that a 64-key attention tile may read past the last utterance
 
 
 def hubert_layer_workspace(rows: int, D: int, F_: int, device):
@@ -261,7 +261,7 @@ def hubert_layer_workspace(rows: int, D: int, F_: int, device):
     zeroed here, once (0 x NaN in the P.V product is NaN); everything else is left as the allocator hands it out - the layer writes
     it before it reads it.  -> namespace(qk, vt, ctx, pre, x1, ffn) of [rows, .] views for the ``pl`` argument."""
     from types import SimpleNamespace
-    n = int(lib().sc_workspace_bytes(1, rows, D, F_)) // 2
+    n = int(lib().sc_workspace_bytes(DEFINES["SC_WS_HUBERT_LAYER"], rows, D, F_)) // 2
     ws = torch.empty(n, device=device, dtype=torch.bfloat16)
     pl, off = {}, 0
     for name, cols, slack in (("qk", 2 * D, ATTN_SLACK * 2 * D), ("vt", D, ATTN_SLACK), ("ctx", D, 0), ("pre", D, 0), ("x1", D, 0), ("ffn", F_, 0)):
@@ -1519,7 +1519,7 @@ def _conv0_groupnorm_gelu(stats_wav: torch.Tensor, wav_len: Optional[torch.Tenso
     """stats -> finalize -> gn_gelu of both row layouts: the GroupNorm statistics of stats_wav over t < T0 (wav_len None: the prepared
     batch; else the caller's, masked by wav_len / wav_off), then the activation of the prepared waveform x (seg None: [B, ldw] rows)"""
     B, C = stats_wav.shape[0], w0.shape[0]
-    partial = torch.empty(B * nchunk * 66, device=stats_wav.device, dtype=torch.float64)
+    partial = torch.empty(B * nchunk * DEFINES["SC_CONV0_NSTAT"], device=stats_wav.device, dtype=torch.float64)
     scale = torch.empty(B, C, device=stats_wav.device, dtype=torch.float32)
     shift = torch.empty_like(scale)
     L = lib()
