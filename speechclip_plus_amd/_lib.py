@@ -30,6 +30,14 @@ DEFINES = HEADER.defines            # the header's integer #defines: SC_SEG_ROWS
 # name -> argtypes of the functions that return int / int32_t (a status, or a small count); the others (sc_last_error, sc_sizeof,
 # sc_workspace_bytes, sc_infonce_workspace_floats, sc_hash32) are bound from HEADER.functions like these, with their own restype
 SIGNATURES = {name: argtypes for name, (restype, argtypes) in HEADER.functions.items() if restype is ctypes.c_int32}
+# The supervised contrastive loss (csrc/supcon.hip) is declared in a header of its own, read by the same reader into tables of its own:
+# the main header's function set, structs, defines and ABI version stay what they were.  Every library build exports these too.
+SUPCON_HEADER_PATH = os.path.join(INCLUDE, "speechclip_hip_supcon.h")
+SUPCON_HEADER = _header.read(SUPCON_HEADER_PATH)
+if SUPCON_HEADER.structs or set(SUPCON_HEADER.functions) & set(HEADER.functions):
+    raise RuntimeError(f"{SUPCON_HEADER_PATH} declares a struct, or a function of {HEADER_PATH} a second time")
+SUPCON_DEFINES = SUPCON_HEADER.defines            # SC_SUPCON_MAX_LOGIT_BYTES
+SUPCON_SIGNATURES = {name: argtypes for name, (restype, argtypes) in SUPCON_HEADER.functions.items() if restype is ctypes.c_int32}
 
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libspeechclip_hip_diag.so")
 GELU_EXACT_LIB_PATH = os.path.join(_HERE, "csrc", "libspeechclip_hip_gelu_exact.so")   # checker build (build.py), tests only
@@ -78,7 +86,7 @@ def _load(path: str) -> ctypes.CDLL:
             f"{path} not found: the HIP extension is not built (python -m speechclip_plus_amd.build). "
             "speechclip_plus_amd has no CPU / eager fallback.")
     cdll = ctypes.CDLL(path)
-    for name, (restype, argtypes) in HEADER.functions.items():
+    for name, (restype, argtypes) in list(HEADER.functions.items()) + list(SUPCON_HEADER.functions.items()):
         fn = getattr(cdll, name)            # AttributeError if the symbol is missing: loud
         fn.argtypes = argtypes
         fn.restype = restype

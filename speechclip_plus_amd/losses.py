@@ -6,6 +6,8 @@ index=None) -> scalar`` (keywords ``bank`` / ``bank_ids`` / ``neg_idx``: mined n
 otherwise).  No MAX_EYE = 256 cap (losses.py:126: the reference cannot run B > 256; the masks are computed in-kernel from
 ``index``).  Forward = one launch (csrc/loss_optim.hip: sc_infonce_fwd); the temperature reaches the kernels as a DEVICE scalar,
 so a trainable temperature costs no host synchronisation in the step.
+
+SupConLoss (avssl/module/losses.py:8-123), the module's other class, follows below on csrc/supcon.hip: same-id pairs as positives.
 """
 import numpy as np
 import torch
@@ -141,3 +143,135 @@ class MaskedContrastiveLoss(nn.Module):
             return _InfoNCENegFn.apply(feat_A, feat_B, inv_temp, index, max(self.margin, 0.0), self.dcl, self.a2b, self.b2a, bank, bank_ids,
                                        neg_idx, self)
         return _InfoNCEFn.apply(feat_A, feat_B, inv_temp, index, max(self.margin, 0.0), self.dcl, self.a2b, self.b2a)
+
+
+class _SupConFn(torch.autograd.Function):
+    """The whole of SupConLoss as ONE node.  ``views``: either ``features`` [bsz, V, E] alone or V tensors [bsz, E] (view v = rows v bsz ..
+    of the contrast matrix); forward = sc_supcon_fwd, backward = sc_supcon_grad and the two feature products on the exact-fp32 GEMM."""
+
+    @staticmethod
+    def forward(ctx, inv_temp, labels, mask, anchor_views, base_temperature, *views):
+        if len(views) == 1 and views[0].dim() == 3:                            # cat(unbind(features, 1), 0): row r = features[r % bsz, r // bsz]
+            bsz, V, E = views[0].shape
+            C = views[0].detach().float().transpose(0, 1).reshape(V * bsz, E)
+        else:
+            bsz, V = views[0].shape[0], len(views)
+            C = torch.cat([v.detach().float() for v in views], 0)
+        it = inv_temp.detach().float().reshape(1).contiguous()
+        Na = anchor_views * bsz
+        loss, logits, lse, _, poscnt = ops.supcon_fwd(C, Na, bsz, labels, mask, it, base_temperature)
+        none = torch.empty(0)
+        ctx.save_for_backward(C, logits, lse, poscnt, it, labels if labels is not None else none, mask if mask is not None else none)
+        ctx.has = (labels is not None, mask is not None)
+        ctx.it_shape = inv_temp.shape
+        ctx.geom = (bsz, V, Na, base_temperature, [(v.dim(), v.dtype) for v in views])
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        C, logits, lse, poscnt, it, labels, mask = ctx.saved_tensors
+        bsz, V, Na, base_temperature, views = ctx.geom
+        labels, mask = labels if ctx.has[0] else None, mask if ctx.has[1] else None
+        G, dot = ops.supcon_grad(logits, lse, poscnt, bsz, labels, mask, g.float().reshape(1).contiguous(), it, base_temperature)
+        dT = dot.sum().reshape(ctx.it_shape) if ctx.needs_input_grad[0] else None   # d loss / d inv_temp (device scalar)
+        dviews = [None] * len(views)
+        if any(ctx.needs_input_grad[5:]):
+            dC = ops.sgemm_mfma(G, C[:Na], a_kmajor=True, b_kmajor=True)       # G^T . C[:Na]  [N, E]   (G already carries inv_temp)
+            dC[:Na] += ops.sgemm_mfma(G, C, b_kmajor=True)                     # G . C         [Na, E]: the anchors' own rows
+            if len(views) == 1 and views[0][0] == 3:
+                dviews = [dC.view(V, bsz, -1).transpose(0, 1).to(views[0][1])]
+            else:
+                dviews = [dC[v * bsz: (v + 1) * bsz].to(dt) if need else None
+                          for v, ((_, dt), need) in enumerate(zip(views, ctx.needs_input_grad[5:]))]
+        return (dT, None, None, None, None) + tuple(dviews)
+
+
+class SupConLoss(nn.Module):
+    """Supervised contrastive loss (Khosla et al., https://arxiv.org/abs/2004.11362; avssl/module/losses.py:8-123) on the HIP kernels of
+    csrc/supcon.hip: samples that share a label are POSITIVES of one another - speech-image, speech-speech and image-image - where
+    MaskedContrastiveLoss only takes them out of the negatives.  Without labels and mask it is the SimCLR loss.
+
+    The reference's constructor and state: ``temperature`` is an ``nn.Parameter`` of shape [1] holding T itself when
+    ``learnable_temperature`` (its state-dict key and shape), the python float otherwise; ``current_temperature`` as there.  The loss's
+    factor is 1 / base_temperature (not T / base_temperature), as in the reference's text.  An anchor without a positive (one view and a
+    label nobody shares, or a zero row of ``mask``) gives 0 / 0: a NaN loss, as the reference's - there is no host check and no
+    synchronisation.  1 / T is formed by torch on the device, the node returns its gradient and autograd does the rest."""
+
+    def __init__(self, temperature=0.07, contrast_mode="all", base_temperature=0.07, learnable_temperature=True):
+        super().__init__()
+        self.learnable_temperature = learnable_temperature
+        if learnable_temperature:
+            self.temperature = nn.Parameter(torch.FloatTensor([temperature]))
+        else:
+            self.temperature = temperature
+        self.contrast_mode = contrast_mode
+        self.base_temperature = base_temperature
+        self._inv_temp_dev = {}
+
+    @property
+    def current_temperature(self):
+        if self.learnable_temperature:
+            return self.temperature.item()
+        return self.temperature
+
+    @property
+    def temperature_for_logging(self):
+        """``current_temperature`` without the device -> host synchronisation of ``.item()``: a 0-dim device tensor when the temperature
+        is learnable (loggers accept tensors), the python float otherwise."""
+        if self.learnable_temperature:
+            return self.temperature.detach().float().reshape(())
+        return float(self.temperature)
+
+    def forward(self, features=None, labels=None, mask=None, *, feat_A=None, feat_B=None, index=None, bank=None, bank_ids=None,
+                neg_idx=None):
+        """With ``features`` [bsz, n_views, ...] (trailing dimensions flattened), ``labels`` [bsz] or ``mask`` [bsz, bsz] (float, may be
+        asymmetric, any weights; no gradient) it is the reference's call, with the reference's ValueErrors.
+
+        With ``feat_A`` / ``feat_B`` [bsz, E] and ``index`` it is the call ``compute_loss`` makes of every criterion: ``features =
+        stack((feat_A, feat_B), 1)``, ``labels = index``.  Speech (feat_A) is view 0, so ``contrast_mode="one"`` anchors on speech only.
+        This adapter is this project's decision: the reference's compute_loss passes ``feat_A=, feat_B=, index=`` to whatever criterion
+        the yaml names, which its own SupConLoss.forward(features, labels, mask) answers with a TypeError - the reference cannot train
+        with the class it ships.  Mined negatives (``bank`` / ``bank_ids`` / ``neg_idx``) stay MaskedContrastiveLoss's: a ValueError."""
+        if bank is not None or bank_ids is not None or neg_idx is not None:
+            raise ValueError("SupConLoss takes no negative bank (bank / bank_ids / neg_idx): mined negatives are MaskedContrastiveLoss's")
+        if features is None:
+            if feat_A is None or feat_B is None:
+                raise ValueError("SupConLoss: give `features` [bsz, n_views, ...], or feat_A and feat_B")
+            if labels is not None or mask is not None:
+                raise ValueError("SupConLoss: with feat_A / feat_B the labels come as `index`")
+            if feat_A.dim() != 2 or feat_A.shape != feat_B.shape:
+                raise ValueError(f"SupConLoss: feat_A {tuple(feat_A.shape)} and feat_B {tuple(feat_B.shape)} must be one shape [bsz, E]")
+            views, labels = (feat_A, feat_B), index
+            batch_size, n_views = feat_A.shape[0], 2
+        else:
+            if feat_A is not None or feat_B is not None or index is not None:
+                raise ValueError("SupConLoss: give `features` or feat_A / feat_B / index, not both")
+            if len(features.shape) < 3:
+                raise ValueError("`features` needs to be [bsz, n_views, ...],at least 3 dimensions are required")
+            if len(features.shape) > 3:
+                features = features.reshape(features.shape[0], features.shape[1], -1)
+            views = (features,)
+            batch_size, n_views = features.shape[0], features.shape[1]
+        if labels is not None and mask is not None:
+            raise ValueError("Cannot define both `labels` and `mask`")
+        if labels is not None:
+            labels = labels.contiguous().view(-1)
+            if labels.shape[0] != batch_size:
+                raise ValueError("Num of labels does not match num of features")
+            labels = labels.to(torch.int64)
+        elif mask is not None:
+            mask = mask.detach().float().contiguous()
+        if self.contrast_mode == "one":
+            anchor_views = 1
+        elif self.contrast_mode == "all":
+            anchor_views = n_views
+        else:
+            raise ValueError("Unknown mode: {}".format(self.contrast_mode))
+        dev = views[0].device
+        if self.learnable_temperature:
+            inv_temp = self.temperature.reciprocal()
+        else:                                              # constant: one device scalar per device, built once
+            inv_temp = self._inv_temp_dev.get(dev)
+            if inv_temp is None:
+                inv_temp = self._inv_temp_dev[dev] = torch.full((1,), 1.0 / float(self.temperature), device=dev)
+        return _SupConFn.apply(inv_temp, labels, mask, anchor_views, float(self.base_temperature), *views)

@@ -8,7 +8,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import DEFINES, RtGemmArgs, RtLnArgs, RtLnBwdArgs, GemmArgs, HubertLayerArgs, Segments, check, diag_lib, lib
+from ._lib import DEFINES, SUPCON_DEFINES, RtGemmArgs, RtLnArgs, RtLnBwdArgs, GemmArgs, HubertLayerArgs, Segments, check, diag_lib, lib
 
 
 def _p(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
@@ -1903,6 +1903,118 @@ def infonce_neg_grad(A: torch.Tensor, bank: torch.Tensor, neg_idx: torch.Tensor,
     check(lib().sc_infonce_neg_grad(_p(bank), bank.stride(0) if N > 1 else E, _p(neg_idx), _p(x), _p(lse_row_ext), _p(gscale),
                                     _p(inv_temp), Bg, E, N, M, int(a2b), int(b2a), _p(dA), _p(dot), _stream()), "sc_infonce_neg_grad")
     return dA, dot
+
+
+_SUPCON_WS = {}
+SUPCON_MAX_LOGIT_BYTES = SUPCON_DEFINES["SC_SUPCON_MAX_LOGIT_BYTES"]      # 1 GiB of logits [Na, N] fp32
+
+
+def supcon_operands(name: str, C, Na: int, bsz: int, labels, mask, inv_temp=None) -> None:
+    """The operands of the supervised contrastive loss, checked before any launch - format errors first, "device tensors only" last:
+    C [N, E] fp32 with E % 4 == 0 and N a whole number of views of bsz samples; 0 <= Na <= N; labels [bsz] int64 or mask [bsz, bsz]
+    fp32 (one of them or neither), contiguous; Na N 4 bytes of logits within SUPCON_MAX_LOGIT_BYTES; inv_temp a one-element fp32 tensor."""
+    if not isinstance(C, torch.Tensor) or C.dim() != 2:
+        raise ValueError(f"{name}: C must be a 2-D tensor")
+    if C.dtype != torch.float32:
+        raise ValueError(f"{name}: C must be torch.float32, not {C.dtype}")
+    N, E = C.shape
+    if E == 0 or E % 4 != 0:
+        raise ValueError(f"{name}: C {tuple(C.shape)} must have E > 0, a multiple of 4")
+    if not C.is_contiguous():
+        raise ValueError(f"{name}: C must be contiguous")
+    if bsz <= 0 or N % bsz != 0:
+        raise ValueError(f"{name}: bsz {bsz} must be positive and divide the {N} rows of C (N = views x bsz)")
+    if not 0 <= Na <= N:
+        raise ValueError(f"{name}: Na {Na} must lie in 0 .. N = {N}")
+    if labels is not None and mask is not None:
+        raise ValueError(f"{name}: labels and mask are both given - one of them or neither")
+    if labels is not None:
+        check_filter_tensor(name, "labels", labels, bsz)
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.float32:
+            raise ValueError(f"{name}: mask must be a torch.float32 tensor")
+        if tuple(mask.shape) != (bsz, bsz) or not mask.is_contiguous():
+            raise ValueError(f"{name}: mask has shape {tuple(mask.shape)}, expected a contiguous ({bsz}, {bsz})")
+    if Na * N * 4 > SUPCON_MAX_LOGIT_BYTES:
+        raise ValueError(f"{name}: the logits [{Na}, {N}] fp32 take {Na * N * 4} bytes, above the limit of {SUPCON_MAX_LOGIT_BYTES} (1 GiB)")
+    if inv_temp is not None and (not isinstance(inv_temp, torch.Tensor) or inv_temp.dtype != torch.float32 or inv_temp.numel() != 1):
+        raise ValueError(f"{name}: inv_temp must be a one-element torch.float32 tensor (a device scalar)")
+    given = [("C", C)] + [(w, t) for w, t in (("labels", labels), ("mask", mask), ("inv_temp", inv_temp)) if t is not None]
+    for what, t in given:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} runs on the HIP kernels: device tensors only ({what})")
+    for what, t in given:
+        if t.device != C.device:
+            raise ValueError(f"{name}: {what} is on {t.device}, C on {C.device}")
+
+
+def _supcon_workspace(Na: int, N: int, device) -> torch.Tensor:
+    """Per (device, stream, Na, N) workspace of sc_supcon_fwd; zeroed once HERE (it ends in the ticket word, which every launch resets)."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream, Na, N)
+    ws = _SUPCON_WS.get(key)
+    if ws is None:
+        ws = _SUPCON_WS[key] = torch.zeros(int(lib().sc_supcon_workspace_floats(Na, N)), device=device, dtype=torch.float32)
+    return ws
+
+
+def supcon_fwd(C: torch.Tensor, Na: int, bsz: int, labels: Optional[torch.Tensor], mask: Optional[torch.Tensor], inv_temp: torch.Tensor,
+               base_temperature: float = 0.07):
+    """Supervised contrastive loss on the contrast rows C [N, E] = cat(unbind(features, 1), 0), anchors = rows 0 .. Na - 1 (sc_supcon_fwd,
+    csrc/supcon.hip) -> (loss [1], logits [Na, N], lse [Na], possum [Na] = sum_j w_ij l_ij, poscnt [Na] = sum_j w_ij).  ``labels``
+    [bsz] int64 or ``mask`` [bsz, bsz] fp32 or neither (the identity); ``inv_temp`` a device scalar tensor.  N = 0 or Na = 0 launches
+    nothing (the loss of no anchor is NaN, as the mean of nothing)."""
+    Na, bsz = int(Na), int(bsz)
+    if float(base_temperature) == 0.0:
+        raise ValueError("supcon_fwd: base_temperature is 0")
+    supcon_operands("supcon_fwd", C, Na, bsz, labels, mask, inv_temp)
+    C = aligned16(C)
+    N, E = C.shape
+    dev = C.device
+    logits = torch.empty(Na, N, device=dev, dtype=torch.float32)
+    lse, possum, poscnt = (torch.empty(Na, device=dev, dtype=torch.float32) for _ in range(3))
+    if N == 0 or Na == 0:
+        return torch.full((1,), float("nan"), device=dev), logits, lse, possum, poscnt
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    ws = _supcon_workspace(Na, N, dev)
+    check(lib().sc_supcon_fwd(_p(C), N, Na, bsz, E, _p(labels), _p(mask), _p(inv_temp), float(base_temperature), _p(logits), _p(lse),
+                              _p(possum), _p(poscnt), _p(loss), _p(ws), _stream()), "sc_supcon_fwd")
+    return loss, logits, lse, possum, poscnt
+
+
+def supcon_grad(logits: torch.Tensor, lse: torch.Tensor, poscnt: torch.Tensor, bsz: int, labels: Optional[torch.Tensor],
+                mask: Optional[torch.Tensor], gscale: torch.Tensor, inv_temp: torch.Tensor, base_temperature: float = 0.07):
+    """-> (G [Na, N] = inv_temp * gscale * dloss/dlogits, dot [Na] with sum(dot) = gscale * d loss / d inv_temp) from ``supcon_fwd``'s
+    logits, lse and poscnt (sc_supcon_grad).  dC = [G . C ; 0] + G^T . C[:Na] on ``sgemm_mfma``."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("supcon_grad: logits must be a contiguous 2-D torch.float32 tensor")
+    Na, N = logits.shape
+    bsz = int(bsz)
+    if bsz <= 0 or N % bsz != 0 or Na > N:
+        raise ValueError(f"supcon_grad: logits {tuple(logits.shape)} must be [Na <= N, N] with bsz {bsz} > 0 dividing N")
+    for what, t in (("lse", lse), ("poscnt", poscnt)):
+        check_filter_tensor("supcon_grad", what, t, Na, (torch.float32,))
+    for what, t in (("gscale", gscale), ("inv_temp", inv_temp)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1:
+            raise ValueError(f"supcon_grad: {what} must be a one-element torch.float32 tensor (a device scalar)")
+    if labels is not None and mask is not None:
+        raise ValueError("supcon_grad: labels and mask are both given - one of them or neither")
+    if labels is not None:
+        check_filter_tensor("supcon_grad", "labels", labels, bsz)
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.float32 or tuple(mask.shape) != (bsz, bsz)
+                             or not mask.is_contiguous()):
+        raise ValueError(f"supcon_grad: mask must be a contiguous torch.float32 tensor of shape ({bsz}, {bsz})")
+    if float(base_temperature) == 0.0:
+        raise ValueError("supcon_grad: base_temperature is 0")
+    for what, t in (("logits", logits), ("lse", lse), ("poscnt", poscnt), ("gscale", gscale), ("inv_temp", inv_temp), ("labels", labels),
+                    ("mask", mask)):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"supcon_grad runs on the HIP kernels: device tensors only ({what})")
+    G = torch.empty_like(logits)
+    dot = torch.empty(Na, device=logits.device, dtype=torch.float32)
+    if N > 0 and Na > 0:
+        check(lib().sc_supcon_grad(_p(logits), _p(lse), _p(poscnt), N, Na, bsz, _p(labels), _p(mask), _p(gscale), _p(inv_temp),
+                                   float(base_temperature), _p(G), _p(dot), _stream()), "sc_supcon_grad")
+    return G, dot
 
 
 def sumsq(x: torch.Tensor, nblk: int = 1024) -> torch.Tensor:
