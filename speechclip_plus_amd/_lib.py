@@ -39,6 +39,14 @@ if SUPCON_HEADER.structs or set(SUPCON_HEADER.functions) & set(HEADER.functions)
 SUPCON_DEFINES = SUPCON_HEADER.defines            # SC_SUPCON_MAX_LOGIT_BYTES
 SUPCON_SIGNATURES = {name: argtypes for name, (restype, argtypes) in SUPCON_HEADER.functions.items() if restype is ctypes.c_int32}
 
+# The quantiser's soft / Gumbel / learnable-temperature modes (csrc/vq_modes.hip): a third header, handled exactly like the second.
+VQ_HEADER_PATH = os.path.join(INCLUDE, "speechclip_hip_vq.h")
+VQ_HEADER = _header.read(VQ_HEADER_PATH)
+if VQ_HEADER.structs or set(VQ_HEADER.functions) & (set(HEADER.functions) | set(SUPCON_HEADER.functions)):
+    raise RuntimeError(f"{VQ_HEADER_PATH} declares a struct, or a function of {HEADER_PATH} or {SUPCON_HEADER_PATH} a second time")
+VQ_DEFINES = VQ_HEADER.defines                    # none
+VQ_SIGNATURES = {name: argtypes for name, (restype, argtypes) in VQ_HEADER.functions.items() if restype is ctypes.c_int32}
+
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libspeechclip_hip_diag.so")
 GELU_EXACT_LIB_PATH = os.path.join(_HERE, "csrc", "libspeechclip_hip_gelu_exact.so")   # checker build (build.py), tests only
 _LIB = None
@@ -86,7 +94,7 @@ def _load(path: str) -> ctypes.CDLL:
             f"{path} not found: the HIP extension is not built (python -m speechclip_plus_amd.build). "
             "speechclip_plus_amd has no CPU / eager fallback.")
     cdll = ctypes.CDLL(path)
-    for name, (restype, argtypes) in list(HEADER.functions.items()) + list(SUPCON_HEADER.functions.items()):
+    for name, (restype, argtypes) in list(HEADER.functions.items()) + list(SUPCON_HEADER.functions.items()) + list(VQ_HEADER.functions.items()):
         fn = getattr(cdll, name)            # AttributeError if the symbol is missing: loud
         fn.argtypes = argtypes
         fn.restype = restype

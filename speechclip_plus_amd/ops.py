@@ -1383,6 +1383,144 @@ def vq_norm_bwd(kw: torch.Tensor, rnorm: torch.Tensor, dy: torch.Tensor, eps: fl
     return dx
 
 
+def vq_mode_operands(name: str, x, V: int, temp, stats=None, mats=()) -> None:
+    """The operands of the quantiser's soft / Gumbel kernels (csrc/vq_modes.hip), checked before any launch - format errors first,
+    "device tensors only" last: x [Nk, >= V] fp32 with unit column stride and Nk V < 2^32 (the noise index is 32 bits wide), temp a
+    positive float, ``stats`` the contiguous [2, Nk] fp32 row statistics of vq_noisy_rowstats, ``mats`` = (name, tensor) pairs of
+    [Nk, >= V] fp32 matrices."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError(f"{name}: x must be a 2-D tensor")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{name}: x must be torch.float32, not {x.dtype}")
+    Nk, V = x.shape[0], int(V)
+    if Nk == 0 or V <= 0 or x.shape[1] < V or x.stride(1) != 1:
+        raise ValueError(f"{name}: x {tuple(x.shape)} must have rows, at least V = {V} > 0 columns and unit column stride")
+    if Nk * V >= 1 << 32:
+        raise ValueError(f"{name}: x has {Nk} rows of V = {V} scores: Nk * V must stay below 2^32 (the noise index is 32 bits wide)")
+    if not float(temp) > 0.0:
+        raise ValueError(f"{name}: temp must be positive, not {temp}")
+    if stats is not None and (not isinstance(stats, torch.Tensor) or stats.dtype != torch.float32 or tuple(stats.shape) != (2, Nk)
+                              or not stats.is_contiguous()):
+        raise ValueError(f"{name}: stats must be a contiguous torch.float32 tensor of shape (2, {Nk}) (vq_noisy_rowstats)")
+    for what, t in mats:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != Nk or t.shape[1] < V or t.stride(1) != 1:
+            raise ValueError(f"{name}: {what} must be a torch.float32 matrix [{Nk}, >= {V}] with unit column stride")
+    given = [("x", x)] + ([("stats", stats)] if stats is not None else []) + list(mats)
+    for what, t in given:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} runs on the HIP kernels: device tensors only ({what})")
+    for what, t in given:
+        if t.device != x.device:
+            raise ValueError(f"{name}: {what} is on {t.device}, x on {x.device}")
+
+
+def vq_gumbel(Nk: int, V: int, seed: int, device) -> torch.Tensor:
+    """g [Nk, V] fp32 = -log(-log u), u from sc_hash32((n V + v) ^ seed): the noise the Gumbel kernels evaluate in place, materialised
+    (sc_vq_gumbel_f32) for host twins and torch yardsticks."""
+    Nk, V = int(Nk), int(V)
+    if Nk <= 0 or V <= 0 or Nk * V >= 1 << 32:
+        raise ValueError(f"vq_gumbel: Nk = {Nk} and V = {V} must be positive with Nk * V below 2^32")
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("vq_gumbel runs on the HIP kernels: device tensors only")
+    g = torch.empty(Nk, V, device=device, dtype=torch.float32)
+    check(lib().sc_vq_gumbel_f32(_p(g), V, Nk, V, int(seed) & 0xffffffff, _stream()), "sc_vq_gumbel_f32")
+    return g
+
+
+def vq_noisy_rowstats(x: torch.Tensor, V: int, temp: float, seed: int = 0, noise: bool = True):
+    """x [Nk, >= V] fp32, masked (vq_rowstats ran) -> idx [Nk] int64 = first argmax(x + g), stats [2, Nk] fp32 = (max (x + g),
+    log sum exp((x + g - max) / temp)): LSE((x + g) / temp) = stats[0] / temp + stats[1], kept apart for the soft kernels.
+    ``noise`` false: the same statistics of x itself."""
+    vq_mode_operands("vq_noisy_rowstats", x, V, temp)
+    Nk = x.shape[0]
+    idx = torch.empty(Nk, device=x.device, dtype=torch.int64)
+    stats = torch.empty(2, Nk, device=x.device, dtype=torch.float32)
+    check(lib().sc_vq_noisy_rowstats(_p(x), x.stride(0), Nk, V, float(temp), int(seed) & 0xffffffff, int(bool(noise)), _p(idx),
+                                     _p(stats[0]), _p(stats[1]), _stream()), "sc_vq_noisy_rowstats")
+    return idx, stats
+
+
+def vq_soft_prob(x: torch.Tensor, stats: torch.Tensor, V: int, temp: float, seed: int = 0, noise: bool = False) -> torch.Tensor:
+    """s [Nk, V] fp32 = softmax((x + g) / temp) (g = 0 without ``noise``), exactly 0 in masked columns; ``stats`` [2, Nk] =
+    vq_noisy_rowstats' for the same (temp, seed, noise)."""
+    if isinstance(x, torch.Tensor) and x.shape[0] > 65535:
+        raise ValueError(f"vq_soft_prob: x has {x.shape[0]} rows, at most 65535")
+    vq_mode_operands("vq_soft_prob", x, V, temp, stats=stats)
+    Nk = x.shape[0]
+    s = torch.empty(Nk, V, device=x.device, dtype=torch.float32)
+    check(lib().sc_vq_soft_prob_f32(_p(x), x.stride(0), _p(stats[0]), _p(stats[1]), Nk, V, float(temp), int(seed) & 0xffffffff, int(bool(noise)), _p(s), V,
+                                    _stream()), "sc_vq_soft_prob_f32")
+    return s
+
+
+def vq_soft_split(x: torch.Tensor, stats: torch.Tensor, V: int, temp: float, Vp: int, seed: int = 0, noise: bool = False,
+                  rows_pad: int = 128) -> torch.Tensor:
+    """The same s as bf16 hi + lo in the three K-blocks [hi | hi | lo] of the soft product: [Nkp, 3 Vp] bf16, zero outside [Nk, V]."""
+    Vp = int(Vp)
+    if Vp < V or Vp % 64 != 0:
+        raise ValueError(f"vq_soft_split: Vp = {Vp} must be a multiple of 64 at or above V = {V}")
+    vq_mode_operands("vq_soft_split", x, V, temp, stats=stats)
+    Nk = x.shape[0]
+    Nkp = -(-Nk // rows_pad) * rows_pad
+    out = torch.empty(Nkp, 3 * Vp, device=x.device, dtype=torch.bfloat16)
+    check(lib().sc_vq_soft_split_bf16(_p(x), x.stride(0), _p(stats[0]), _p(stats[1]), Nk, V, float(temp), int(seed) & 0xffffffff, int(bool(noise)), _p(out),
+                                      Nkp, Vp, _stream()), "sc_vq_soft_split_bf16")
+    return out
+
+
+def vq_soft_table(table: torch.Tensor, Vp: int) -> torch.Tensor:
+    """table [V, Et] fp32 -> its transposed bf16 split [Et, 3 Vp] = [hi | lo | hi] (hi = bf16(table), lo = bf16(table - hi); zero in the
+    columns V .. Vp - 1 of every block): the W operand of ``vq_soft_product``.  Built once per table, off the step's path."""
+    V, Et = table.shape
+    tT = table.detach().float().t()
+    hi = tT.to(torch.bfloat16)
+    lo = (tT - hi.float()).to(torch.bfloat16)
+    W = torch.zeros(Et, 3, Vp, device=table.device, dtype=torch.bfloat16)
+    W[:, 0, :V], W[:, 1, :V], W[:, 2, :V] = hi, lo, hi
+    return W.view(Et, 3 * Vp)
+
+
+def vq_soft_slices(Vp: int) -> int:
+    """Equal slices (multiples of 64, at most 16) of the soft product's contraction of 3 Vp."""
+    units = 3 * Vp // 64
+    return max(s for s in range(1, 17) if units % s == 0)
+
+
+def vq_soft_product(s_split: torch.Tensor, w_split: torch.Tensor, Et: int) -> torch.Tensor:
+    """keywords [Nkp, Et] fp32 = s . table over the K-blocks [hi | hi | lo] x [hi | lo | hi]: hi hi + hi lo + lo hi, every bf16 product
+    exact in fp32, as ONE batched bf16 GEMM cut along the contraction into fp32 partials that sc_colsum_f32 adds in slice order."""
+    assert s_split.dtype == torch.bfloat16 and w_split.dtype == torch.bfloat16 and s_split.is_contiguous() and w_split.is_contiguous()
+    Nkp, K3 = s_split.shape
+    assert w_split.shape == (Et, K3) and K3 % 192 == 0, (tuple(w_split.shape), Et, K3)
+    S = vq_soft_slices(K3 // 3)
+    Kc = K3 // S
+    part = torch.empty(S, Nkp, Et, device=s_split.device, dtype=torch.float32)
+    gemm_raw(s_split, K3, w_split, K3, part, Et, Nkp, Et, Kc, out_f32=True, nb1=S, sA=(Kc, 0), sW=(Kc, 0), sC=(Nkp * Et, 0))
+    out = torch.empty(Nkp, Et, device=s_split.device, dtype=torch.float32)
+    colsum(part, Nkp * Et, S, Nkp * Et, out)
+    return out
+
+
+def vq_soft_bwd2(x: torch.Tensor, stats: torch.Tensor, t: torch.Tensor, V: int, temp: float, out_bf16: bool, Vpad: Optional[int] = None,
+                 seed: int = 0, noise: bool = False, want_dtemp: bool = False):
+    """-> (dx [Nk, Vpad] = s (t - <s, t>) / temp with s = softmax((x + g) / temp), dtemp [1] = -(1 / temp) sum dz z or None): the row
+    terms of d temp are added in index order by sc_colsum_f32."""
+    Vpad = V if Vpad is None else int(Vpad)
+    if Vpad < V:
+        raise ValueError(f"vq_soft_bwd2: Vpad = {Vpad} is below V = {V}")
+    vq_mode_operands("vq_soft_bwd2", x, V, temp, stats=stats, mats=(("t", t),))
+    Nk = x.shape[0]
+    dx = torch.empty(Nk, Vpad, device=x.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
+    rows = torch.empty(Nk, device=x.device, dtype=torch.float32) if want_dtemp else None
+    check(lib().sc_vq_soft_bwd2(_p(x), x.stride(0), _p(stats[0]), _p(stats[1]), _p(t), t.stride(0), Nk, V, Vpad, float(temp), int(seed) & 0xffffffff,
+                                int(bool(noise)), _p(dx), Vpad, int(out_bf16), _p(rows), _stream()), "sc_vq_soft_bwd2")
+    dtemp = None
+    if want_dtemp:
+        dtemp = torch.empty(1, device=x.device, dtype=torch.float32)
+        colsum(rows, 1, Nk, 1, dtemp)
+    return dx, dtemp
+
+
 def bn_rows_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, run_mean: torch.Tensor, run_var: torch.Tensor,
                 training: bool, momentum: float, eps: float):
     """BatchNorm over the rows of x [N, E] fp32 -> (y, save_mean, save_rstd); running estimates updated in place when training."""

@@ -17,6 +17,13 @@ How it runs here (``SimpleVectorQuantizer.quantize_keywords``, called by General
               (sc_vq_norm_bwd_f32).  The reference trains under precision-16 autocast; gradients here are bf16 operands with
               fp32 accumulation.
 
+The other training modes (csrc/vq_modes.hip, include/speechclip_hip_vq.h; ``_KeywordVQModeFn`` / ``_VQDenseModeFn``):
+``use_gumbel`` perturbs the scores with g = -log(-log u), a stateless hash of (seed, row, column) that every kernel evaluates again
+(targets and the one-hot from argmax(x + g), soft = softmax((x + g) / temp)); ``hard = False`` makes ``subword_prob`` the softmax
+itself, keywords = soft . table as one bf16 GEMM over the K-blocks [hi | hi | lo] x [hi | lo | hi] (every product exact in fp32, fp32
+partials along the vocabulary added in slice order); ``temp = "learnable=..."`` returns d temp = -(1 / temp) sum dz z to ``curr_temp``.
+Eval mode of every configuration, and training with use_gumbel false, hard true and no temperature gradient, issue the calls above.
+
 ``SimpleVectorQuantizer.forward(x)`` keeps the reference's module-level signature on a given score tensor (dense
 ``subword_prob`` with the same straight-through gradient, same kernels).  Same constructor keywords and result-dict keys.
 There is no CPU path: these modules take device tensors only (the CPU restatement of this maths is oracle/cascaded_ref.py).
@@ -66,6 +73,14 @@ class VocabTables:
         assert self.norm_split.shape[0] == self.Vp
         units = self.Vp // 64
         self.splits = max(s for s in range(1, 17) if units % s == 0)                # equal vocabulary slices, multiples of 64
+        self._soft_T = None
+
+    def soft_table(self) -> torch.Tensor:
+        """The table transposed and split, [Et, 3 Vp] bf16 = [hi | lo | hi]: the W operand of the soft product ``s . table``
+        (ops.vq_soft_product).  Built on the first soft call: a hard-mode model never allocates it."""
+        if self._soft_T is None:
+            self._soft_T = ops.vq_soft_table(self.table, self.Vp)
+        return self._soft_T
 
     @staticmethod
     def of(weight: torch.Tensor, cache: dict) -> "VocabTables":
@@ -79,10 +94,16 @@ class VQResult(dict):
     """Result dict of the fused path: ``subword_prob`` (a dense (B, N, V) one-hot nobody on the path reads - the keywords are
     gathered) is materialised on first access only."""
 
+    _soft = None        # soft modes: (scores, row statistics, temp, seed, noise) - subword_prob is then softmax((x + g) / temp), not the one-hot
+
     def __missing__(self, key):
         if key == "subword_prob":
             bsz, tsz, V = self._shape
-            self[key] = ops.vq_onehot(self["targets"].reshape(-1), V).view(bsz, tsz, V)
+            if self._soft is not None:
+                x, stats, temp, seed, noise = self._soft
+                self[key] = ops.vq_soft_prob(x, stats, V, temp, seed, noise).view(bsz, tsz, V)
+            else:
+                self[key] = ops.vq_onehot(self["targets"].reshape(-1), V).view(bsz, tsz, V)
             return self[key]
         raise KeyError(key)
 
@@ -114,26 +135,97 @@ class _KeywordVQFn(torch.autograd.Function):
             return None, None, None, None
         kw, rnorm, cos, lse_t = ctx.saved_tensors
         tb, temp = ctx.tb, ctx.temp
+        dkw, _ = _keyword_backward(kw, rnorm, cos, tb, g,
+                                   lambda x, t, Vp: (ops.vq_soft_bwd(x, lse_t, t, tb.V, temp, out_bf16=True, Vpad=Vp), None))
+        return dkw, None, None, None
+
+
+def _keyword_backward(kw, rnorm, cos, tb: VocabTables, g, soft_bwd):
+    """The gradient chain of ``quantize_keywords`` in every training mode: t = g . table^T -> (dx, d temp) = soft_bwd(scores, t, Vp) ->
+    dx . normalised table, cut along the vocabulary -> through the normalisation.  -> (d kw, d temp)"""
+    Nk, Et = kw.shape
+    Nkp, Vp = cos.shape
+    dev = kw.device
+    gb = torch.zeros(Nkp, tb.Etp, device=dev, dtype=torch.bfloat16)
+    gb[:Nk, :Et] = g
+    t = torch.empty(Nkp, Vp, device=dev, dtype=torch.float32)
+    ops.gemm_raw(gb, tb.Etp, tb.table_bf16, tb.Etp, t, Vp, Nkp, Vp, tb.Etp, out_f32=True)     # d subword_prob = g . table^T
+    dx = torch.zeros(Nkp, Vp, device=dev, dtype=torch.bfloat16) if Nkp != Nk else None
+    dxv, dtemp = soft_bwd(cos[:Nk], t[:Nk], Vp)
+    if dx is None:
+        dx = dxv
+    else:
+        dx[:Nk] = dxv
+    S = tb.splits
+    Kc = Vp // S
+    part = torch.empty(S, Nkp, Et, device=dev, dtype=torch.float32)
+    ops.gemm_raw(dx, Vp, tb.norm_T_bf16, Vp, part, Et, Nkp, Et, Kc, out_f32=True, nb1=S, sA=(Kc, 0), sW=(Kc, 0), sC=(Nkp * Et, 0))
+    dkwn = torch.empty(Nkp, Et, device=dev, dtype=torch.float32)
+    ops.colsum(part, Nkp * Et, S, Nkp * Et, dkwn)
+    return ops.vq_norm_bwd(kw, rnorm, dkwn[:Nk]), dtemp
+
+
+class _KeywordVQModeFn(torch.autograd.Function):
+    """The training modes beside the default one (use_gumbel, hard = false, a learnable temperature), one node for all of them:
+    kw [Nk, Et] fp32, temp_t = the temperature parameter [1] (learnable) or None -> (keywords [Nk, Et], idx [Nk] = the targets, ent [Nk],
+    ppl [2], scores [Nkp, Vp], stats [2, Nk]); gradients to kw and, as a [1] tensor, to temp_t.
+    hard: keywords = table[idx] (the exact one-hot's product; the straight-through term is value-neutral); soft: keywords = s . table on
+    the split-bf16 product (ops.vq_soft_product).  Statistics (ent, ppl) come from the unperturbed scores in every mode."""
+
+    @staticmethod
+    def forward(ctx, kw, temp_t, tb: VocabTables, temp: float, use_gumbel: bool, hard: bool, seed: int):
         Nk, Et = kw.shape
-        Nkp, Vp = cos.shape
-        dev = kw.device
-        gb = torch.zeros(Nkp, tb.Etp, device=dev, dtype=torch.bfloat16)
-        gb[:Nk, :Et] = g
-        t = torch.empty(Nkp, Vp, device=dev, dtype=torch.float32)
-        ops.gemm_raw(gb, tb.Etp, tb.table_bf16, tb.Etp, t, Vp, Nkp, Vp, tb.Etp, out_f32=True)     # d subword_prob = g . table^T
-        dx = torch.zeros(Nkp, Vp, device=dev, dtype=torch.bfloat16) if Nkp != Nk else None
-        dxv = ops.vq_soft_bwd(cos[:Nk], lse_t, t[:Nk], tb.V, temp, out_bf16=True, Vpad=Vp)
-        if dx is None:
-            dx = dxv
+        kw = kw.detach().float().contiguous()
+        kwn_T, rnorm = ops.vq_prep(kw)
+        if EXACT_FP32_SCORES:
+            cos = ops.sgemm_mfma(kwn_T, tb.norm_T, a_kmajor=True, b_kmajor=True)
         else:
-            dx[:Nk] = dxv
-        S = tb.splits
-        Kc = Vp // S
-        part = torch.empty(S, Nkp, Et, device=dev, dtype=torch.float32)
-        ops.gemm_raw(dx, Vp, tb.norm_T_bf16, Vp, part, Et, Nkp, Et, Kc, out_f32=True, nb1=S, sA=(Kc, 0), sW=(Kc, 0), sC=(Nkp * Et, 0))
-        dkwn = torch.empty(Nkp, Et, device=dev, dtype=torch.float32)
-        ops.colsum(part, Nkp * Et, S, Nkp * Et, dkwn)
-        return ops.vq_norm_bwd(kw, rnorm, dkwn[:Nk]), None, None, None
+            cos = ops.cosine_scores_split(kw, rnorm, tb.norm_split, tb.Vp)
+        x = cos[:Nk]
+        idx, _, lse_1, ent = ops.vq_rowstats(x, tb.V, temp, SPECIAL_TOKENS)
+        ppl = ops.vq_perplexity(x, tb.V, idx, lse_1)
+        idx, stats = ops.vq_noisy_rowstats(x, tb.V, temp, seed, use_gumbel)            # (max, log sum) of the scores this mode softmaxes
+        if hard:
+            out = ops.vq_gather(tb.table, idx)
+        else:
+            out = ops.vq_soft_product(ops.vq_soft_split(x, stats, tb.V, temp, tb.Vp, seed, use_gumbel), tb.soft_table(), Et)[:Nk]
+        ctx.tb, ctx.temp, ctx.seed, ctx.noise = tb, temp, seed, use_gumbel
+        ctx.want_dtemp = temp_t is not None
+        ctx.save_for_backward(kw, rnorm, cos, stats)
+        ctx.mark_non_differentiable(idx, ent, ppl, cos, stats)
+        return out, idx, ent, ppl, cos, stats
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        kw, rnorm, cos, stats = ctx.saved_tensors
+        tb = ctx.tb
+        dkw, dtemp = _keyword_backward(kw, rnorm, cos, tb, g, lambda x, t, Vp: ops.vq_soft_bwd2(
+            x, stats, t, tb.V, ctx.temp, out_bf16=True, Vpad=Vp, seed=ctx.seed, noise=ctx.noise, want_dtemp=ctx.want_dtemp))
+        return dkw, dtemp, None, None, None, None, None
+
+
+class _VQDenseModeFn(torch.autograd.Function):
+    """The same modes at the module level, on a given score matrix x [Nk, V] (masked in place): dense subword_prob = the exact one-hot
+    of argmax(x + g) (hard) or s = softmax((x + g) / temp) (soft), gradient dx = s (t - <s, t>) / temp in both, d temp as a [1] tensor."""
+
+    @staticmethod
+    def forward(ctx, x, temp_t, temp: float, prob_msk, use_gumbel: bool, hard: bool, seed: int):
+        Nk, V = x.shape
+        idx, _, lse_1, ent = ops.vq_rowstats(x, V, temp, prob_msk)
+        ppl = ops.vq_perplexity(x, V, idx, lse_1)
+        idx, stats = ops.vq_noisy_rowstats(x, V, temp, seed, use_gumbel)
+        prob = ops.vq_onehot(idx, V) if hard else ops.vq_soft_prob(x, stats, V, temp, seed, use_gumbel)
+        ctx.temp, ctx.seed, ctx.noise, ctx.want_dtemp = temp, seed, use_gumbel, temp_t is not None
+        ctx.save_for_backward(x, stats)
+        ctx.mark_non_differentiable(idx, ent, ppl)
+        return prob, idx, ent, ppl
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        x, stats = ctx.saved_tensors
+        dx, dtemp = ops.vq_soft_bwd2(x, stats, g.float().contiguous(), x.shape[1], ctx.temp, out_bf16=False, seed=ctx.seed, noise=ctx.noise,
+                                     want_dtemp=ctx.want_dtemp)
+        return dx, dtemp, None, None, None, None, None
 
 
 class _VQDenseFn(torch.autograd.Function):
@@ -162,10 +254,7 @@ class _VQDenseFn(torch.autograd.Function):
 class SimpleVectorQuantizer(nn.Module):
     def __init__(self, temp, groundTruthPerplexity=None, time_first=True, use_gumbel=False, hard=True):
         super().__init__()
-        self.time_first, self.use_gumbel, self.hard = time_first, use_gumbel, hard
-        if use_gumbel or not hard:
-            raise NotImplementedError("only the shipped quantiser is built: use_gumbel false, hard true "
-                                      "(config/speechCLIP+/*: vq.args)")
+        self.time_first, self.use_gumbel, self.hard = time_first, bool(use_gumbel), bool(hard)
         if isinstance(temp, str):
             if temp.startswith("learnable="):
                 self.temp_type = "learnable"
@@ -189,13 +278,29 @@ class SimpleVectorQuantizer(nn.Module):
             self.curr_temp = max(self.max_temp * self.temp_decay ** num_updates, self.min_temp)
 
     def _temp(self) -> float:
+        """The temperature of this call as a host float, read ONCE per forward: a learnable temperature costs one ``.item()`` (a device
+        sync) here, the sync the reference has at my_vector_quantizer.py:123 (``result["temp"] = self.curr_temp.item()``).  A
+        temperature at or below zero is a ValueError before any launch."""
         if self.temp_type == "fixed":
-            return self._fixed_temp
-        if self.temp_type == "learnable":
-            if self.training and torch.is_grad_enabled():
-                raise NotImplementedError("temp='learnable=...': the gradient to the temperature is not built (no shipped config)")
-            return float(self.curr_temp.item())
-        return float(self.curr_temp)
+            temp = self._fixed_temp
+        elif self.temp_type == "learnable":
+            temp = float(self.curr_temp.item())
+        else:
+            temp = float(self.curr_temp)
+        if not temp > 0.0:
+            raise ValueError(f"SimpleVectorQuantizer: the temperature is {temp}; it must be positive")
+        return temp
+
+    def _mode(self):
+        """-> (default, temp_t, seed).  ``default``: this call is the shipped quantiser's (eval mode of every configuration; training
+        with use_gumbel false, hard true and no gradient to a temperature) and issues exactly the calls it always has.  Otherwise
+        ``temp_t`` is the temperature parameter when it takes a gradient (else None) and ``seed`` the Gumbel seed: one
+        ``ops.next_mult_seed()`` per call, drawn only when training with use_gumbel, so no other mode moves the dropout seed stream."""
+        temp_t = self.curr_temp if (self.temp_type == "learnable" and self.training and torch.is_grad_enabled()
+                                    and self.curr_temp.requires_grad) else None
+        if not self.training or (self.hard and not self.use_gumbel and temp_t is None):
+            return True, None, 0
+        return False, temp_t, (ops.next_mult_seed() if self.use_gumbel else 0)
 
     def _result(self, bsz, tsz, V, idx, ent, ppl, temp) -> VQResult:
         r = VQResult(num_vars=V)
@@ -229,7 +334,11 @@ class SimpleVectorQuantizer(nn.Module):
         if x2.dtype != torch.float32 or x2.stride(1) != 1:
             x2 = x2.float().contiguous()
         temp = self._temp()
-        prob, idx, ent, ppl = _VQDenseFn.apply(x2, temp, self.training, tuple(prob_msk))
+        default, temp_t, seed = self._mode()
+        if default:
+            prob, idx, ent, ppl = _VQDenseFn.apply(x2, temp, self.training, tuple(prob_msk))
+        else:
+            prob, idx, ent, ppl = _VQDenseModeFn.apply(x2, temp_t, temp, tuple(prob_msk), self.use_gumbel, self.hard, seed)
         r = self._result(bsz, tsz, fsz, idx, ent, ppl, temp)
         r["subword_prob"] = prob.view(bsz, tsz, fsz)
         if not produce_targets:
@@ -245,8 +354,17 @@ class SimpleVectorQuantizer(nn.Module):
         tb = VocabTables.of(token_table, self._tables)
         bsz, tsz, Et = keywords.shape
         temp = self._temp()
-        out, idx, ent, ppl = _KeywordVQFn.apply(keywords.reshape(bsz * tsz, Et), tb, temp, self.training)
-        return self._result(bsz, tsz, tb.V, idx, ent, ppl, temp), out.view(bsz, tsz, Et).to(keywords.dtype)
+        default, temp_t, seed = self._mode()
+        if default:
+            out, idx, ent, ppl = _KeywordVQFn.apply(keywords.reshape(bsz * tsz, Et), tb, temp, self.training)
+            r = self._result(bsz, tsz, tb.V, idx, ent, ppl, temp)
+        else:
+            out, idx, ent, ppl, cos, stats = _KeywordVQModeFn.apply(keywords.reshape(bsz * tsz, Et), temp_t, tb, temp, self.use_gumbel,
+                                                                  self.hard, seed)
+            r = self._result(bsz, tsz, tb.V, idx, ent, ppl, temp)
+            if not self.hard:                      # subword_prob, if anybody asks, is the dense softmax of these scores
+                r._soft = (cos[:bsz * tsz], stats, temp, seed, self.use_gumbel)
+        return r, out.reshape(bsz, tsz, Et).to(keywords.dtype)
 
 
 class _KwBNFn(torch.autograd.Function):
