@@ -1233,6 +1233,79 @@ int sc_rows_scatter_bf16(const float* d, const int32_t* row, sc_bf16* dX, int32_
  * block's padded-pitch key mask from the lengths in one launch. */
 int sc_len_mask_u8(const int64_t* lens, int32_t add, uint8_t* mask, int32_t B, int32_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Supervised contrastive loss (Khosla et al.; csrc/supcon.hip).  Additive in round 27; sc_abi_version() stays 7.
+ *   replaces: SupConLoss.forward (avssl/module/losses.py:8-123), on the contrast rows C [N, E] = cat(unbind(features, 1), 0), N = V bsz:
+ *             row r is view r / bsz of sample r % bsz.  Anchors are rows 0 .. Na - 1 (Na = N: contrast_mode "all"; Na = bsz: "one").
+ *     l_ij   = inv_temp <C_i, C_j>                                   i < Na, j < N
+ *     keep_ij = [j != i]                                             an anchor never contrasts with itself
+ *     w_ij   = W[i % bsz, j % bsz] keep_ij                           W = [labels_a == labels_b] (all 64 bits) with labels, the float mask
+ *                                                                    [bsz, bsz] as given (asymmetric, any weights) with mask, identity with neither
+ *     lse_i  = log sum_j keep_ij e^{l_ij},   s_i = sum_j w_ij
+ *     loss   = -(1 / base_temperature) / Na sum_i [ sum_j w_ij l_ij / s_i - lse_i ]      (s_i = 0: 0 / 0, a NaN loss as the reference's)
+ *   sc_supcon_fwd : ONE launch - 64 x 64 logit tiles on the matrix pipe in exact fp32, per-tile (max, sum exp, sum w l, sum w) row
+ *                   partials over the kept columns, the last-arriving workgroup merges them in tile order (deterministic, no float
+ *                   atomics) into lse [Na], possum [Na] = sum_j w_ij l_ij, poscnt [Na] = s_i and loss[0]; the scaled logits [Na, N] are
+ *                   kept for the backward.  labels and mask: one of them or neither.  inv_temp is a DEVICE scalar, base_temperature a
+ *                   host float.  E % 4 == 0, C 16-byte aligned; rows of C at or behind N are never read.  N == 0 launches nothing.
+ *                   Na N 4 bytes of logits above 1 GiB (SC_SUPCON_MAX_LOGIT_BYTES) are refused.
+ *                   workspace: sc_supcon_workspace_floats(Na, N) floats, whose last word is the ticket - the CALLER zeroes the workspace
+ *                   once before its first launch; every launch leaves the ticket zero.  One workspace per stream.
+ *   sc_supcon_grad: with p_ij = keep_ij e^{l_ij - lse_i} and g_ij = -(w_ij / s_i - p_ij) / (base_temperature Na):
+ *                   G [Na, N] = inv_temp gscale g   (dC = [G . C ; 0] + G^T . C[:Na]: sc_sgemm_mfma_f32, no further scaling) and
+ *                   dlogit_dot [Na] = gscale sum_j g_ij l_ij / inv_temp, so that d loss / d inv_temp = sum_i dlogit_dot[i].
+ *                   gscale is the incoming gradient of the loss, a DEVICE scalar.  The mask gets no gradient.
+ * ---------------------------------------------------------------------------------------------- */
+#define SC_SUPCON_MAX_LOGIT_BYTES 1073741824   /* 1 GiB of logits [Na, N] fp32 */
+int64_t sc_supcon_workspace_floats(int32_t Na, int32_t N);   /* 0: nothing to launch; -1: refused (see sc_last_error) */
+int sc_supcon_fwd(const float* C, int32_t N, int32_t Na, int32_t bsz, int32_t E, const int64_t* labels, const float* mask,
+                  const float* inv_temp, float base_temperature, float* logits, float* lse, float* possum, float* poscnt, float* loss,
+                  float* workspace, void* stream);
+int sc_supcon_grad(const float* logits, const float* lse, const float* poscnt, int32_t N, int32_t Na, int32_t bsz, const int64_t* labels,
+                   const float* mask, const float* gscale, const float* inv_temp, float base_temperature, float* G, float* dlogit_dot,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training modes of SimpleVectorQuantizer: soft, Gumbel, learnable temperature (csrc/vq.hip, behind sc_vq_rowstats / sc_vq_soft_bwd).
+ * Additive in round 28; sc_abi_version() stays 7.
+ *   replaces: SimpleVectorQuantizer.forward in training (avssl/module/speechclip_c_modules/my_vector_quantizer.py:124-137) for
+ *             use_gumbel true / hard false, and the gradient to a learnable temperature.
+ *   x [Nk, ldx >= V] fp32 are the MASKED scores: sc_vq_rowstats has written -inf into the special columns.  tau = temp > 0.
+ *     z_nv = (x_nv + g_nv) / tau,  s = softmax(z) per row,  g = 0 without noise.
+ *   Noise (noise != 0): stateless, one hash word per element -
+ *     e = n V + v as uint32 (n the row, V the TRUE vocabulary, not a pitch; (int64) Nk V < 2^32 is an argument check),
+ *     w = sc_hash32(e ^ seed),  u = ((w >> 9) + 0.5) 2^-23 (exact in fp32, in [2^-24, 1 - 2^-24]),
+ *     g = -log(-log u) with the precise logf (1 ulp each): finite, in [-2.82, 16.64], |g - g_exact| <= 4 U (1 + |g|), U = 2^-24.
+ *   Every kernel that takes (seed, noise) evaluates the same g for the same (n, v): nothing but x and the seed is kept for the backward.
+ *   sc_vq_gumbel_f32     : g [Nk, ldg] materialised (columns < V), for host twins and yardsticks.
+ *   sc_vq_noisy_rowstats : per row (one workgroup each, sc_vq_rowstats' shape and tie rule: the lowest column among equal maxima)
+ *                          idx = first argmax_v (x + g), rowmax = max_v (x + g), logsum = log sum_v exp((x + g - rowmax) / tau).
+ *                          LSE((x + g) / tau) = rowmax / tau + logsum; the two stay APART, because their fp32 sum would put an
+ *                          absolute error of U |rowmax / tau| into every exponent (6e-5 at tau = 1e-3) where x + g - rowmax is exact at
+ *                          the maximum.  noise 0: the same statistics of x itself, with the precise expf / logf.
+ *   sc_vq_soft_prob_f32  : s [Nk, lds >= V] = exp((x + g - rowmax) / tau - logsum) dense, exactly 0 in masked columns; rowmax and
+ *                          logsum are sc_vq_noisy_rowstats' for the same (temp, seed, noise).
+ *   sc_vq_soft_split_bf16: the same s as the bf16 addends hi = bf16(s), lo = bf16(s - hi) in three K-blocks of Vp columns,
+ *                          out [Nkp, 3 Vp] = [hi | hi | lo]; against a table laid out [hi | lo | hi] ONE bf16 GEMM sums
+ *                          hi hi + hi lo + lo hi, each product exact in fp32.  Rows >= Nk and columns >= V of every block are
+ *                          written as zeros.  Vp % 4 == 0, out 8-byte aligned.
+ *   sc_vq_soft_bwd2      : with t = d subword_prob:  dz = s (t - <s, t>),  dx [Nk, ldd >= Vpad] = dz / tau (bf16 or fp32; columns
+ *                          V .. Vpad - 1 zero-filled; s == 0 gives exactly 0 and never meets t),  and, when dtemp_row [Nk] is given,
+ *                          dtemp_row[n] = -(1 / tau) sum_v dz_nv z_nv over s > 0: d tau = sum_n dtemp_row[n] (sc_colsum_f32, index order).
+ *                          sc_vq_soft_bwd is this formula with noise 0, no dtemp_row, on the fused LSE.
+ *   Fixed-order reductions, no float atomics: two calls on the same inputs give the same bits.
+ * ---------------------------------------------------------------------------------------------- */
+int sc_vq_gumbel_f32(float* g, int64_t ldg, int32_t Nk, int32_t V, uint32_t seed, void* stream);
+int sc_vq_noisy_rowstats(const float* x, int64_t ldx, int32_t Nk, int32_t V, float temp, uint32_t seed, int32_t noise, int64_t* idx,
+                         float* rowmax, float* logsum, void* stream);
+int sc_vq_soft_prob_f32(const float* x, int64_t ldx, const float* rowmax, const float* logsum, int32_t Nk, int32_t V, float temp,
+                        uint32_t seed, int32_t noise, float* s, int64_t lds, void* stream);
+int sc_vq_soft_split_bf16(const float* x, int64_t ldx, const float* rowmax, const float* logsum, int32_t Nk, int32_t V, float temp,
+                          uint32_t seed, int32_t noise, uint16_t* out, int32_t Nkp, int32_t Vp, void* stream);
+int sc_vq_soft_bwd2(const float* x, int64_t ldx, const float* rowmax, const float* logsum, const float* t, int64_t ldt, int32_t Nk,
+                    int32_t V, int32_t Vpad, float temp, uint32_t seed, int32_t noise, void* dx, int64_t ldd, int32_t out_bf16,
+                    float* dtemp_row, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

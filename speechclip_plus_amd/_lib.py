@@ -26,26 +26,11 @@ HEADER = _header.read(HEADER_PATH, STRUCT_NAMES)
 if set(HEADER.structs) != set(STRUCT_NAMES):
     raise RuntimeError(f"{HEADER_PATH} declares the structs {sorted(HEADER.structs)}, _lib.STRUCT_NAMES names {sorted(STRUCT_NAMES)}")
 GemmArgs, HubertLayerArgs, RtGemmArgs, RtLnArgs, RtLnBwdArgs, Segments = STRUCTS = tuple(HEADER.structs[c] for c in STRUCT_NAMES)
-DEFINES = HEADER.defines            # the header's integer #defines: SC_SEG_ROWS, SC_ATTN_SLACK, SC_CONV0_NSTAT, SC_WS_*
+DEFINES = HEADER.defines            # the header's integer #defines: SC_SEG_ROWS, SC_ATTN_SLACK, SC_CONV0_NSTAT, SC_WS_*, SC_SUPCON_MAX_LOGIT_BYTES
 # name -> argtypes of the functions that return int / int32_t (a status, or a small count); the others (sc_last_error, sc_sizeof,
-# sc_workspace_bytes, sc_infonce_workspace_floats, sc_hash32) are bound from HEADER.functions like these, with their own restype
+# sc_workspace_bytes, sc_infonce_workspace_floats, sc_supcon_workspace_floats, sc_hash32) are bound from HEADER.functions like these, with
+# their own restype
 SIGNATURES = {name: argtypes for name, (restype, argtypes) in HEADER.functions.items() if restype is ctypes.c_int32}
-# The supervised contrastive loss (csrc/supcon.hip) is declared in a header of its own, read by the same reader into tables of its own:
-# the main header's function set, structs, defines and ABI version stay what they were.  Every library build exports these too.
-SUPCON_HEADER_PATH = os.path.join(INCLUDE, "speechclip_hip_supcon.h")
-SUPCON_HEADER = _header.read(SUPCON_HEADER_PATH)
-if SUPCON_HEADER.structs or set(SUPCON_HEADER.functions) & set(HEADER.functions):
-    raise RuntimeError(f"{SUPCON_HEADER_PATH} declares a struct, or a function of {HEADER_PATH} a second time")
-SUPCON_DEFINES = SUPCON_HEADER.defines            # SC_SUPCON_MAX_LOGIT_BYTES
-SUPCON_SIGNATURES = {name: argtypes for name, (restype, argtypes) in SUPCON_HEADER.functions.items() if restype is ctypes.c_int32}
-
-# The quantiser's soft / Gumbel / learnable-temperature modes (csrc/vq_modes.hip): a third header, handled exactly like the second.
-VQ_HEADER_PATH = os.path.join(INCLUDE, "speechclip_hip_vq.h")
-VQ_HEADER = _header.read(VQ_HEADER_PATH)
-if VQ_HEADER.structs or set(VQ_HEADER.functions) & (set(HEADER.functions) | set(SUPCON_HEADER.functions)):
-    raise RuntimeError(f"{VQ_HEADER_PATH} declares a struct, or a function of {HEADER_PATH} or {SUPCON_HEADER_PATH} a second time")
-VQ_DEFINES = VQ_HEADER.defines                    # none
-VQ_SIGNATURES = {name: argtypes for name, (restype, argtypes) in VQ_HEADER.functions.items() if restype is ctypes.c_int32}
 
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libspeechclip_hip_diag.so")
 GELU_EXACT_LIB_PATH = os.path.join(_HERE, "csrc", "libspeechclip_hip_gelu_exact.so")   # checker build (build.py), tests only
@@ -94,7 +79,7 @@ def _load(path: str) -> ctypes.CDLL:
             f"{path} not found: the HIP extension is not built (python -m speechclip_plus_amd.build). "
             "speechclip_plus_amd has no CPU / eager fallback.")
     cdll = ctypes.CDLL(path)
-    for name, (restype, argtypes) in list(HEADER.functions.items()) + list(SUPCON_HEADER.functions.items()) + list(VQ_HEADER.functions.items()):
+    for name, (restype, argtypes) in HEADER.functions.items():
         fn = getattr(cdll, name)            # AttributeError if the symbol is missing: loud
         fn.argtypes = argtypes
         fn.restype = restype

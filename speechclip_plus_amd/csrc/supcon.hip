@@ -15,7 +15,6 @@
 // self column; the difference cancels).  s_i = 0 gives 0 / 0: a NaN loss, as the reference's.  Rows of C at or behind N (and behind Na on
 // the anchor side) are never loaded; K-tails are zero-filled by the loader (E % 4 == 0).
 #include "sc_common.h"
-#include "speechclip_hip_supcon.h"
 
 namespace {
 

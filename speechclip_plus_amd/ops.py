@@ -8,7 +8,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import DEFINES, SUPCON_DEFINES, RtGemmArgs, RtLnArgs, RtLnBwdArgs, GemmArgs, HubertLayerArgs, Segments, check, diag_lib, lib
+from ._lib import DEFINES, RtGemmArgs, RtLnArgs, RtLnBwdArgs, GemmArgs, HubertLayerArgs, Segments, check, diag_lib, lib
 
 
 def _p(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
@@ -1384,7 +1384,7 @@ def vq_norm_bwd(kw: torch.Tensor, rnorm: torch.Tensor, dy: torch.Tensor, eps: fl
 
 
 def vq_mode_operands(name: str, x, V: int, temp, stats=None, mats=()) -> None:
-    """The operands of the quantiser's soft / Gumbel kernels (csrc/vq_modes.hip), checked before any launch - format errors first,
+    """The operands of the quantiser's soft / Gumbel kernels (csrc/vq.hip, behind the row statistics), checked before any launch - format errors first,
     "device tensors only" last: x [Nk, >= V] fp32 with unit column stride and Nk V < 2^32 (the noise index is 32 bits wide), temp a
     positive float, ``stats`` the contiguous [2, Nk] fp32 row statistics of vq_noisy_rowstats, ``mats`` = (name, tensor) pairs of
     [Nk, >= V] fp32 matrices."""
@@ -2044,7 +2044,7 @@ def infonce_neg_grad(A: torch.Tensor, bank: torch.Tensor, neg_idx: torch.Tensor,
 
 
 _SUPCON_WS = {}
-SUPCON_MAX_LOGIT_BYTES = SUPCON_DEFINES["SC_SUPCON_MAX_LOGIT_BYTES"]      # 1 GiB of logits [Na, N] fp32
+SUPCON_MAX_LOGIT_BYTES = DEFINES["SC_SUPCON_MAX_LOGIT_BYTES"]      # 1 GiB of logits [Na, N] fp32
 
 
 def supcon_operands(name: str, C, Na: int, bsz: int, labels, mask, inv_temp=None) -> None:

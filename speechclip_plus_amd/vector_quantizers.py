@@ -17,7 +17,8 @@ How it runs here (``SimpleVectorQuantizer.quantize_keywords``, called by General
               (sc_vq_norm_bwd_f32).  The reference trains under precision-16 autocast; gradients here are bf16 operands with
               fp32 accumulation.
 
-The other training modes (csrc/vq_modes.hip, include/speechclip_hip_vq.h; ``_KeywordVQModeFn`` / ``_VQDenseModeFn``):
+The other training modes (the same two nodes, ``_KeywordVQFn`` / ``_VQDenseFn``, with a mode; kernels behind the row statistics in
+csrc/vq.hip, prototypes in include/speechclip_hip.h):
 ``use_gumbel`` perturbs the scores with g = -log(-log u), a stateless hash of (seed, row, column) that every kernel evaluates again
 (targets and the one-hot from argmax(x + g), soft = softmax((x + g) / temp)); ``hard = False`` makes ``subword_prob`` the softmax
 itself, keywords = soft . table as one bf16 GEMM over the K-blocks [hi | hi | lo] x [hi | lo | hi] (every product exact in fp32, fp32
@@ -108,11 +109,33 @@ class VQResult(dict):
         raise KeyError(key)
 
 
+# A call's ``mode``: None is the shipped default (argmax of the scores, hard one-hot, no gradient to a temperature: sc_vq_rowstats' fused
+# lse_t and sc_vq_soft_bwd); otherwise (use_gumbel, hard, seed), on sc_vq_noisy_rowstats' (max, log sum) and sc_vq_soft_bwd2.
+
+
+def _row_statistics(x, V: int, temp: float, mask):
+    """The front half every call shares, on scores x [Nk, >= V] (masked in place): -> (idx, lse_t, ent, ppl).  ent and ppl come from
+    the unperturbed scores in every mode."""
+    idx, lse_t, lse_1, ent = ops.vq_rowstats(x, V, temp, mask)
+    return idx, lse_t, ent, ops.vq_perplexity(x, V, idx, lse_1)
+
+
+def _soft_bwd(x, stat, t, V: int, temp: float, mode, want_dtemp: bool, out_bf16: bool, Vpad=None):
+    """-> (dx = soft (t - <soft, t>) / temp, d temp or None) on the statistics the forward of this mode saved."""
+    if mode is None:
+        return ops.vq_soft_bwd(x, stat, t, V, temp, out_bf16=out_bf16, Vpad=Vpad), None
+    use_gumbel, _, seed = mode
+    return ops.vq_soft_bwd2(x, stat, t, V, temp, out_bf16=out_bf16, Vpad=Vpad, seed=seed, noise=use_gumbel, want_dtemp=want_dtemp)
+
+
 class _KeywordVQFn(torch.autograd.Function):
-    """kw [Nk, Et] fp32 -> (keywords [Nk, Et] = table[argmax cos], idx [Nk], ent [Nk], ppl [2]); gradient to kw (training)."""
+    """kw [Nk, Et] fp32, temp_t = the temperature parameter [1] when it takes a gradient (else None) -> (keywords [Nk, Et], idx [Nk] =
+    the targets, ent [Nk], ppl [2], scores [Nkp, Vp], stats [2, Nk] or None in the default mode); gradients to kw and, as a [1]
+    tensor, to temp_t.  hard: keywords = table[idx] (the exact one-hot's product; the straight-through term is value-neutral, the dense
+    (Nk, V) one-hot is never built); soft: keywords = s . table on the split-bf16 product (ops.vq_soft_product)."""
 
     @staticmethod
-    def forward(ctx, kw, tb: VocabTables, temp: float, training: bool):
+    def forward(ctx, kw, temp_t, tb: VocabTables, temp: float, training: bool, mode):
         Nk, Et = kw.shape
         kw = kw.detach().float().contiguous()
         kwn_T, rnorm = ops.vq_prep(kw)
@@ -120,24 +143,32 @@ class _KeywordVQFn(torch.autograd.Function):
             cos = ops.sgemm_mfma(kwn_T, tb.norm_T, a_kmajor=True, b_kmajor=True)                               # [Nkp, Vp] fp32
         else:
             cos = ops.cosine_scores_split(kw, rnorm, tb.norm_split, tb.Vp)                                     # [Nkp, Vp] fp32, fp32-accurate
-        idx, lse_t, lse_1, ent = ops.vq_rowstats(cos[:Nk], tb.V, temp, SPECIAL_TOKENS)
-        ppl = ops.vq_perplexity(cos[:Nk], tb.V, idx, lse_1)
-        out = ops.vq_gather(tb.table, idx)
-        ctx.tb, ctx.temp, ctx.training = tb, temp, training
+        x = cos[:Nk]
+        idx, lse_t, ent, ppl = _row_statistics(x, tb.V, temp, SPECIAL_TOKENS)
+        use_gumbel, hard, seed = mode or (False, True, 0)
+        stat = lse_t
+        if mode is not None:               # the argmax and the (max, log sum) [2, Nk] of the scores this mode softmaxes
+            idx, stat = ops.vq_noisy_rowstats(x, tb.V, temp, seed, use_gumbel)
+        if hard:
+            out = ops.vq_gather(tb.table, idx)
+        else:
+            out = ops.vq_soft_product(ops.vq_soft_split(x, stat, tb.V, temp, tb.Vp, seed, use_gumbel), tb.soft_table(), Et)[:Nk]
+        ctx.tb, ctx.temp, ctx.training, ctx.mode, ctx.want_dtemp = tb, temp, training, mode, temp_t is not None
         if training:
-            ctx.save_for_backward(kw, rnorm, cos, lse_t)
-        ctx.mark_non_differentiable(idx, ent, ppl)
-        return out, idx, ent, ppl
+            ctx.save_for_backward(kw, rnorm, cos, stat)
+        stats = None if mode is None else stat
+        ctx.mark_non_differentiable(*(t for t in (idx, ent, ppl, cos, stats) if t is not None))
+        return out, idx, ent, ppl, cos, stats
 
     @staticmethod
     def backward(ctx, g, *_):
         if not ctx.training:               # inference: subword_prob is the hard one-hot, nothing flows back
-            return None, None, None, None
-        kw, rnorm, cos, lse_t = ctx.saved_tensors
-        tb, temp = ctx.tb, ctx.temp
-        dkw, _ = _keyword_backward(kw, rnorm, cos, tb, g,
-                                   lambda x, t, Vp: (ops.vq_soft_bwd(x, lse_t, t, tb.V, temp, out_bf16=True, Vpad=Vp), None))
-        return dkw, None, None, None
+            return None, None, None, None, None, None
+        kw, rnorm, cos, stat = ctx.saved_tensors
+        tb = ctx.tb
+        dkw, dtemp = _keyword_backward(kw, rnorm, cos, tb, g, lambda x, t, Vp: _soft_bwd(
+            x, stat, t, tb.V, ctx.temp, ctx.mode, ctx.want_dtemp, out_bf16=True, Vpad=Vp))
+        return dkw, dtemp, None, None, None, None
 
 
 def _keyword_backward(kw, rnorm, cos, tb: VocabTables, g, soft_bwd):
@@ -165,90 +196,32 @@ def _keyword_backward(kw, rnorm, cos, tb: VocabTables, g, soft_bwd):
     return ops.vq_norm_bwd(kw, rnorm, dkwn[:Nk]), dtemp
 
 
-class _KeywordVQModeFn(torch.autograd.Function):
-    """The training modes beside the default one (use_gumbel, hard = false, a learnable temperature), one node for all of them:
-    kw [Nk, Et] fp32, temp_t = the temperature parameter [1] (learnable) or None -> (keywords [Nk, Et], idx [Nk] = the targets, ent [Nk],
-    ppl [2], scores [Nkp, Vp], stats [2, Nk]); gradients to kw and, as a [1] tensor, to temp_t.
-    hard: keywords = table[idx] (the exact one-hot's product; the straight-through term is value-neutral); soft: keywords = s . table on
-    the split-bf16 product (ops.vq_soft_product).  Statistics (ent, ppl) come from the unperturbed scores in every mode."""
-
-    @staticmethod
-    def forward(ctx, kw, temp_t, tb: VocabTables, temp: float, use_gumbel: bool, hard: bool, seed: int):
-        Nk, Et = kw.shape
-        kw = kw.detach().float().contiguous()
-        kwn_T, rnorm = ops.vq_prep(kw)
-        if EXACT_FP32_SCORES:
-            cos = ops.sgemm_mfma(kwn_T, tb.norm_T, a_kmajor=True, b_kmajor=True)
-        else:
-            cos = ops.cosine_scores_split(kw, rnorm, tb.norm_split, tb.Vp)
-        x = cos[:Nk]
-        idx, _, lse_1, ent = ops.vq_rowstats(x, tb.V, temp, SPECIAL_TOKENS)
-        ppl = ops.vq_perplexity(x, tb.V, idx, lse_1)
-        idx, stats = ops.vq_noisy_rowstats(x, tb.V, temp, seed, use_gumbel)            # (max, log sum) of the scores this mode softmaxes
-        if hard:
-            out = ops.vq_gather(tb.table, idx)
-        else:
-            out = ops.vq_soft_product(ops.vq_soft_split(x, stats, tb.V, temp, tb.Vp, seed, use_gumbel), tb.soft_table(), Et)[:Nk]
-        ctx.tb, ctx.temp, ctx.seed, ctx.noise = tb, temp, seed, use_gumbel
-        ctx.want_dtemp = temp_t is not None
-        ctx.save_for_backward(kw, rnorm, cos, stats)
-        ctx.mark_non_differentiable(idx, ent, ppl, cos, stats)
-        return out, idx, ent, ppl, cos, stats
-
-    @staticmethod
-    def backward(ctx, g, *_):
-        kw, rnorm, cos, stats = ctx.saved_tensors
-        tb = ctx.tb
-        dkw, dtemp = _keyword_backward(kw, rnorm, cos, tb, g, lambda x, t, Vp: ops.vq_soft_bwd2(
-            x, stats, t, tb.V, ctx.temp, out_bf16=True, Vpad=Vp, seed=ctx.seed, noise=ctx.noise, want_dtemp=ctx.want_dtemp))
-        return dkw, dtemp, None, None, None, None, None
-
-
-class _VQDenseModeFn(torch.autograd.Function):
-    """The same modes at the module level, on a given score matrix x [Nk, V] (masked in place): dense subword_prob = the exact one-hot
-    of argmax(x + g) (hard) or s = softmax((x + g) / temp) (soft), gradient dx = s (t - <s, t>) / temp in both, d temp as a [1] tensor."""
-
-    @staticmethod
-    def forward(ctx, x, temp_t, temp: float, prob_msk, use_gumbel: bool, hard: bool, seed: int):
-        Nk, V = x.shape
-        idx, _, lse_1, ent = ops.vq_rowstats(x, V, temp, prob_msk)
-        ppl = ops.vq_perplexity(x, V, idx, lse_1)
-        idx, stats = ops.vq_noisy_rowstats(x, V, temp, seed, use_gumbel)
-        prob = ops.vq_onehot(idx, V) if hard else ops.vq_soft_prob(x, stats, V, temp, seed, use_gumbel)
-        ctx.temp, ctx.seed, ctx.noise, ctx.want_dtemp = temp, seed, use_gumbel, temp_t is not None
-        ctx.save_for_backward(x, stats)
-        ctx.mark_non_differentiable(idx, ent, ppl)
-        return prob, idx, ent, ppl
-
-    @staticmethod
-    def backward(ctx, g, *_):
-        x, stats = ctx.saved_tensors
-        dx, dtemp = ops.vq_soft_bwd2(x, stats, g.float().contiguous(), x.shape[1], ctx.temp, out_bf16=False, seed=ctx.seed, noise=ctx.noise,
-                                     want_dtemp=ctx.want_dtemp)
-        return dx, dtemp, None, None, None, None, None
-
-
 class _VQDenseFn(torch.autograd.Function):
-    """module-level API on a given score matrix x [Nk, V] (masked in place): dense hard one-hot with the straight-through gradient."""
+    """The module-level API on a given score matrix x [Nk, V] (masked in place): dense subword_prob = the exact one-hot of argmax(x + g)
+    (hard) or s = softmax((x + g) / temp) (soft), gradient dx = s (t - <s, t>) / temp in both, d temp as a [1] tensor to temp_t."""
 
     @staticmethod
-    def forward(ctx, x, temp: float, training: bool, prob_msk):
+    def forward(ctx, x, temp_t, temp: float, prob_msk, training: bool, mode):
         Nk, V = x.shape
-        idx, lse_t, lse_1, ent = ops.vq_rowstats(x, V, temp, prob_msk)
-        ppl = ops.vq_perplexity(x, V, idx, lse_1)
-        prob = ops.vq_onehot(idx, V)
-        ctx.temp, ctx.training = temp, training
+        idx, lse_t, ent, ppl = _row_statistics(x, V, temp, prob_msk)
+        use_gumbel, hard, seed = mode or (False, True, 0)
+        stat = lse_t
+        if mode is not None:               # the argmax and the (max, log sum) [2, Nk] of the scores this mode softmaxes
+            idx, stat = ops.vq_noisy_rowstats(x, V, temp, seed, use_gumbel)
+        prob = ops.vq_onehot(idx, V) if hard else ops.vq_soft_prob(x, stat, V, temp, seed, use_gumbel)
+        ctx.temp, ctx.training, ctx.mode, ctx.want_dtemp = temp, training, mode, temp_t is not None
         if training:
-            ctx.save_for_backward(x, lse_t)
+            ctx.save_for_backward(x, stat)
         ctx.mark_non_differentiable(idx, ent, ppl)
         return prob, idx, ent, ppl
 
     @staticmethod
     def backward(ctx, g, *_):
         if not ctx.training:
-            return None, None, None, None
-        x, lse_t = ctx.saved_tensors
-        return ops.vq_soft_bwd(x, lse_t, g.float().contiguous(), x.shape[1], ctx.temp, out_bf16=False), None, None, None
+            return None, None, None, None, None, None
+        x, stat = ctx.saved_tensors
+        dx, dtemp = _soft_bwd(x, stat, g.float().contiguous(), x.shape[1], ctx.temp, ctx.mode, ctx.want_dtemp, out_bf16=False)
+        return dx, dtemp, None, None, None, None
 
 
 class SimpleVectorQuantizer(nn.Module):
@@ -335,10 +308,8 @@ class SimpleVectorQuantizer(nn.Module):
             x2 = x2.float().contiguous()
         temp = self._temp()
         default, temp_t, seed = self._mode()
-        if default:
-            prob, idx, ent, ppl = _VQDenseFn.apply(x2, temp, self.training, tuple(prob_msk))
-        else:
-            prob, idx, ent, ppl = _VQDenseModeFn.apply(x2, temp_t, temp, tuple(prob_msk), self.use_gumbel, self.hard, seed)
+        mode = None if default else (self.use_gumbel, self.hard, seed)
+        prob, idx, ent, ppl = _VQDenseFn.apply(x2, temp_t, temp, tuple(prob_msk), self.training, mode)
         r = self._result(bsz, tsz, fsz, idx, ent, ppl, temp)
         r["subword_prob"] = prob.view(bsz, tsz, fsz)
         if not produce_targets:
@@ -355,15 +326,11 @@ class SimpleVectorQuantizer(nn.Module):
         bsz, tsz, Et = keywords.shape
         temp = self._temp()
         default, temp_t, seed = self._mode()
-        if default:
-            out, idx, ent, ppl = _KeywordVQFn.apply(keywords.reshape(bsz * tsz, Et), tb, temp, self.training)
-            r = self._result(bsz, tsz, tb.V, idx, ent, ppl, temp)
-        else:
-            out, idx, ent, ppl, cos, stats = _KeywordVQModeFn.apply(keywords.reshape(bsz * tsz, Et), temp_t, tb, temp, self.use_gumbel,
-                                                                  self.hard, seed)
-            r = self._result(bsz, tsz, tb.V, idx, ent, ppl, temp)
-            if not self.hard:                      # subword_prob, if anybody asks, is the dense softmax of these scores
-                r._soft = (cos[:bsz * tsz], stats, temp, seed, self.use_gumbel)
+        mode = None if default else (self.use_gumbel, self.hard, seed)
+        out, idx, ent, ppl, cos, stats = _KeywordVQFn.apply(keywords.reshape(bsz * tsz, Et), temp_t, tb, temp, self.training, mode)
+        r = self._result(bsz, tsz, tb.V, idx, ent, ppl, temp)
+        if mode is not None and not self.hard:     # subword_prob, if anybody asks, is the dense softmax of these scores
+            r._soft = (cos[:bsz * tsz], stats, temp, seed, self.use_gumbel)
         return r, out.reshape(bsz, tsz, Et).to(keywords.dtype)
 
 

@@ -1,6 +1,6 @@
 """Helpers of tests/test_gpu_supcon.py and the CPU tests of SupConLoss (not collected on their own): seeded inputs and an fp64 reference
 of the supervised contrastive loss (csrc/supcon.hip under losses.SupConLoss), written from the formulas of
-include/speechclip_hip_supcon.h - no autograd, no reference code.  Nothing here needs a GPU; tests/test_supcon_cases_cpu.py checks this
+include/speechclip_hip.h - no autograd, no reference code.  Nothing here needs a GPU; tests/test_supcon_cases_cpu.py checks this
 reference against the fixtures the reference implementation produced (tests/golden/supcon.npz)."""
 import os
 

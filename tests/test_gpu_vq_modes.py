@@ -1,4 +1,4 @@
-"""The quantiser's soft / Gumbel / learnable-temperature modes on the HIP kernels of csrc/vq_modes.hip (under ops.vq_* and
+"""The quantiser's soft / Gumbel / learnable-temperature modes on the HIP kernels of csrc/vq.hip (under ops.vq_* and
 vector_quantizers.SimpleVectorQuantizer) against the fp64 restatement of tests/vq_modes_cases.py.
 
 Bounds, fixed before the first run (U = 2^-24; every formula is a function in vq_modes_cases.py with its derivation):
@@ -428,6 +428,89 @@ def test_eval_mode_gives_the_defaults_bits_in_every_mode(temp):
         for k in ("targets", "code_perplexity", "prob_perplexity", "ent_per_t", "diversity_loss", "subword_prob"):
             assert torch.equal(r[k], r0[k]) and torch.equal(d[k], d0[k]), k
     assert ops._mult_calls[0] == c0
+
+
+# ---------------------------------------------------------------------------------------------------- the launch sequences
+RECORDED_OPS = ("vq_prep", "sgemm_mfma", "cosine_scores_split", "vq_rowstats", "vq_perplexity", "vq_noisy_rowstats", "vq_gather", "vq_onehot",
+                "vq_soft_prob", "vq_soft_split", "vq_soft_table", "vq_soft_product", "vq_soft_bwd", "vq_soft_bwd2", "gemm_raw", "colsum",
+                "vq_norm_bwd")
+CONFIGURATIONS = {"default": {}, "soft": {"hard": False}, "gumbel_hard": {"use_gumbel": True, "hard": True}, "learnable": {"temp": "learnable=0.1"}}
+MODE_ONLY = {"vq_noisy_rowstats", "vq_soft_bwd2", "vq_soft_split", "vq_soft_prob", "vq_soft_table"}
+KW_FRONT = ["vq_prep", "cosine_scores_split", "vq_rowstats", "vq_perplexity"]
+KW_BACK = ["gemm_raw", "colsum", "vq_norm_bwd"]
+# What the two nodes called before they took the mode as an argument (recorded with record_sequences on that code, one class per
+# entry point and mode family then): forward calls, "|", backward calls.
+KEYWORD_SEQUENCES = {
+    "default": KW_FRONT + ["vq_gather", "|", "gemm_raw", "vq_soft_bwd"] + KW_BACK,
+    "soft": KW_FRONT + ["vq_noisy_rowstats", "vq_soft_split", "vq_soft_table", "vq_soft_product", "|", "gemm_raw", "vq_soft_bwd2"] + KW_BACK,
+    "gumbel_hard": KW_FRONT + ["vq_noisy_rowstats", "vq_gather", "|", "gemm_raw", "vq_soft_bwd2"] + KW_BACK,
+    "learnable": KW_FRONT + ["vq_noisy_rowstats", "vq_gather", "|", "gemm_raw", "vq_soft_bwd2"] + KW_BACK,
+    "eval": KW_FRONT + ["vq_gather", "|"],
+}
+DENSE_SEQUENCES = {
+    "default": ["vq_rowstats", "vq_perplexity", "vq_onehot", "|", "vq_soft_bwd"],
+    "soft": ["vq_rowstats", "vq_perplexity", "vq_noisy_rowstats", "vq_soft_prob", "|", "vq_soft_bwd2"],
+    "gumbel_hard": ["vq_rowstats", "vq_perplexity", "vq_noisy_rowstats", "vq_onehot", "|", "vq_soft_bwd2"],
+    "learnable": ["vq_rowstats", "vq_perplexity", "vq_noisy_rowstats", "vq_onehot", "|", "vq_soft_bwd2"],
+    "eval": ["vq_rowstats", "vq_perplexity", "vq_onehot", "|"],
+}
+
+
+def record_sequences(setattr_):
+    """-> (keyword sequences, dense sequences): the ``ops`` functions quantize_keywords (V = 50 table, 6 keyword rows) and forward(x)
+    (a (2, 3, 50) score tensor) call, in order, per configuration; calls one recorded function makes to another are its own business
+    and are not recorded.  ``setattr_(ops, name, wrapper)`` installs the recorder (monkeypatch.setattr)."""
+    from speechclip_plus_amd import ops
+    from speechclip_plus_amd.vector_quantizers import SimpleVectorQuantizer
+    log, depth = [], [0]
+
+    def recorder(name, fn):
+        @functools.wraps(fn)
+        def wrapper(*args, **kwargs):
+            if depth[0] == 0:
+                log.append(name)
+            depth[0] += 1
+            try:
+                return fn(*args, **kwargs)
+            finally:
+                depth[0] -= 1
+        return wrapper
+    V, Et = 50, 8
+    table = torch.from_numpy(_table(V, Et)).cuda()
+    kw0 = torch.randn(2, 3, Et, generator=torch.Generator().manual_seed(11)).cuda()
+    x0 = torch.from_numpy(_scores(15, V)[:6].reshape(2, 3, V).copy()).cuda()
+    quantizers = {name: SimpleVectorQuantizer(**{"temp": "fixed=0.1", **args}).cuda().train() for name, args in CONFIGURATIONS.items()}
+    quantizers["eval"] = SimpleVectorQuantizer(temp="fixed=0.1").cuda().eval()
+    for name in RECORDED_OPS:
+        setattr_(ops, name, recorder(name, getattr(ops, name)))
+    keyword, dense = {}, {}
+    for name, vq in quantizers.items():
+        kw = kw0.clone().requires_grad_(vq.training)
+        _, out = vq.quantize_keywords(kw, table)
+        log.append("|")
+        if vq.training:
+            out.sum().backward()
+        keyword[name], log[:] = list(log), []
+        x = x0.clone().requires_grad_(vq.training)
+        r = vq(x * 1.0)
+        log.append("|")
+        if vq.training:
+            (r["subword_prob"] * x0).sum().backward()
+        dense[name], log[:] = list(log), []
+    return keyword, dense
+
+
+def test_the_launch_sequences_are_the_ones_before_the_nodes_were_folded(monkeypatch):
+    from speechclip_plus_amd import ops
+    c0 = ops._mult_calls[0]
+    try:
+        keyword, dense = record_sequences(monkeypatch.setattr)
+    finally:
+        ops._mult_calls[0] = c0
+    assert keyword == KEYWORD_SEQUENCES and dense == DENSE_SEQUENCES
+    for seq in (keyword["default"], keyword["eval"], dense["default"], dense["eval"]):
+        assert not MODE_ONLY & set(seq)
+    assert keyword["eval"][-1] == "|" and dense["eval"][-1] == "|"                       # eval records no backward call
 
 
 # ---------------------------------------------------------------------------------------------------- sampling

@@ -22,7 +22,8 @@ def test_library_exports_every_declared_symbol():
     lib = _lib.lib()                       # raises if the .so is missing (no fallback)
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/speechclip_hip.h but not exported"
-    assert set(_lib.SIGNATURES) | {"sc_last_error", "sc_hash32", "sc_infonce_workspace_floats", "sc_workspace_bytes", "sc_sizeof"} == declared
+    assert set(_lib.SIGNATURES) | {"sc_last_error", "sc_hash32", "sc_infonce_workspace_floats", "sc_workspace_bytes", "sc_sizeof",
+                                   "sc_supcon_workspace_floats"} == declared
     assert lib.sc_abi_version() == 7
     # the ctypes mirrors of the argument structs have the C structs' sizes (checked again at every load: _lib.lib())
     for what, cls in enumerate((_lib.GemmArgs, _lib.HubertLayerArgs, _lib.RtGemmArgs, _lib.RtLnArgs, _lib.RtLnBwdArgs)):

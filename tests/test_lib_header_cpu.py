@@ -130,13 +130,13 @@ def test_missing_header_names_the_path(tmp_path):
 # ---- the real header
 
 NOT_INT = {"sc_last_error": c_char_p, "sc_hash32": c_uint32, "sc_infonce_workspace_floats": c_int64, "sc_workspace_bytes": c_int64,
-           "sc_sizeof": c_int64}
+           "sc_sizeof": c_int64, "sc_supcon_workspace_floats": c_int64}
 
 
 def test_every_declared_function_is_bound_with_the_headers_types():
     from speechclip_plus_amd import _lib
     fns = _lib.HEADER.functions
-    assert len(fns) == 131 and set(_lib.SIGNATURES) | set(NOT_INT) == set(fns) and not set(_lib.SIGNATURES) & set(NOT_INT)
+    assert len(fns) == 139 and set(_lib.SIGNATURES) | set(NOT_INT) == set(fns) and not set(_lib.SIGNATURES) & set(NOT_INT)
     assert {n: r for n, (r, _) in fns.items() if r is not c_int32} == NOT_INT
     assert type(_lib.SIGNATURES) is dict and all(type(a) is list for a in _lib.SIGNATURES.values())
     lib = _lib.lib()
@@ -167,6 +167,7 @@ def test_the_six_structs_keep_their_names_and_the_sizeof_order():
 
 def test_the_defines_and_their_python_twins():
     from speechclip_plus_amd import _lib, clip_image, ops
-    assert _lib.DEFINES == {"SC_SEG_ROWS": 8, "SC_ATTN_SLACK": 64, "SC_CONV0_NSTAT": 66, "SC_WS_INFONCE": 0, "SC_WS_HUBERT_LAYER": 1}
+    assert _lib.DEFINES == {"SC_SEG_ROWS": 8, "SC_ATTN_SLACK": 64, "SC_CONV0_NSTAT": 66, "SC_WS_INFONCE": 0, "SC_WS_HUBERT_LAYER": 1,
+                            "SC_SUPCON_MAX_LOGIT_BYTES": 1 << 30}
     assert ops.RowSegments.GRAN == clip_image.SEG_ROWS == _lib.DEFINES["SC_SEG_ROWS"] == 8
     assert ops.ATTN_SLACK == _lib.DEFINES["SC_ATTN_SLACK"] == 64

@@ -1,5 +1,5 @@
-"""SupConLoss without a GPU: the C entry points of csrc/supcon.hip are declared in include/speechclip_hip_supcon.h, bound from it and
-exported by every library build, while the main header and the ABI version stay what they were; constructor and state dict are the
+"""SupConLoss without a GPU: the C entry points of csrc/supcon.hip are declared in include/speechclip_hip.h, bound from it and
+exported by every library build, additive to the functions the header had, at the same ABI version; constructor and state dict are the
 reference's; every refusal - the module's ValueErrors, ops' operand checks, the C argument checks - comes before any launch; the
 model builds with ``cl_loss.type: SupConLoss`` and trains its temperature."""
 import ctypes
@@ -15,23 +15,27 @@ GIB = 1 << 30
 
 
 # ---------------------------------------------------------------------------------------------------- declared, bound, exported
-def test_symbols_declared_in_the_second_header_bound_and_exported():
+def _declared(text):
+    return re.findall(r"\b(sc_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))
+
+
+def test_symbols_declared_in_the_header_bound_and_exported():
     import speechclip_plus_amd as sc
     from speechclip_plus_amd import _lib, build, losses, ops
-    text = open(os.path.join(ROOT, "include", "speechclip_hip_supcon.h")).read()
-    declared = set(re.findall(r"\b(sc_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", text, flags=re.S)))
-    assert declared == set(NEW_SYMBOLS) == set(_lib.SUPCON_HEADER.functions)
+    text = open(os.path.join(ROOT, "include", "speechclip_hip.h")).read()
+    assert set(NEW_SYMBOLS) <= set(_declared(text)) and set(NEW_SYMBOLS) <= set(_lib.HEADER.functions)
     assert "losses.py:8-123" in text and 'extern "C"' in text
-    assert set(_lib.SUPCON_SIGNATURES) == {"sc_supcon_fwd", "sc_supcon_grad"}
-    assert _lib.SUPCON_HEADER.functions["sc_supcon_workspace_floats"] == (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32])
-    assert _lib.SUPCON_HEADER.structs == {} and _lib.SUPCON_DEFINES == {"SC_SUPCON_MAX_LOGIT_BYTES": GIB} and ops.SUPCON_MAX_LOGIT_BYTES == GIB
+    assert {"sc_supcon_fwd", "sc_supcon_grad"} <= set(_lib.SIGNATURES) and "sc_supcon_workspace_floats" not in _lib.SIGNATURES
+    assert _lib.HEADER.functions["sc_supcon_workspace_floats"] == (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32])
+    assert _lib.DEFINES["SC_SUPCON_MAX_LOGIT_BYTES"] == GIB and ops.SUPCON_MAX_LOGIT_BYTES == GIB
     v, f = ctypes.c_void_p, ctypes.c_float
     i32 = ctypes.c_int32
-    assert _lib.SUPCON_SIGNATURES["sc_supcon_fwd"] == [v, i32, i32, i32, i32, v, v, v, f, v, v, v, v, v, v, v]
-    assert _lib.SUPCON_SIGNATURES["sc_supcon_grad"] == [v, v, v, i32, i32, i32, v, v, v, v, f, v, v, v]
+    assert _lib.SIGNATURES["sc_supcon_fwd"] == [v, i32, i32, i32, i32, v, v, v, f, v, v, v, v, v, v, v]
+    assert _lib.SIGNATURES["sc_supcon_grad"] == [v, v, v, i32, i32, i32, v, v, v, v, f, v, v, v]
     for path in (_lib.LIB_PATH, _lib.DIAG_LIB_PATH, _lib.GELU_EXACT_LIB_PATH):           # all three link the same objects
         cdll = _lib._load(path)
-        for name, (restype, argtypes) in _lib.SUPCON_HEADER.functions.items():
+        for name in NEW_SYMBOLS:
+            restype, argtypes = _lib.HEADER.functions[name]
             fn = getattr(cdll, name)
             assert fn.restype is restype and list(fn.argtypes) == argtypes, (path, name)
     assert "supcon.hip" in build.SOURCES
@@ -39,12 +43,22 @@ def test_symbols_declared_in_the_second_header_bound_and_exported():
     assert sc.SupConLoss is losses.SupConLoss and "SupConLoss" in sc.__all__ and "MaskedContrastiveLoss" in sc.__all__
 
 
-def test_the_main_header_and_the_abi_version_stay():
+def test_one_header_declares_them_once_and_the_abi_version_stays():
+    """The loss's three and the quantiser modes' five entry points are declared exactly once, in the one header, beside the 131
+    functions it had; no side header and no second table is left; the additions did not move the ABI version."""
     from speechclip_plus_amd import _lib
-    assert len(_lib.HEADER.functions) == 131 and not set(NEW_SYMBOLS) & set(_lib.HEADER.functions)
-    assert not set(NEW_SYMBOLS) & set(_lib.SIGNATURES)
-    assert _lib.DEFINES == {"SC_SEG_ROWS": 8, "SC_ATTN_SLACK": 64, "SC_CONV0_NSTAT": 66, "SC_WS_INFONCE": 0, "SC_WS_HUBERT_LAYER": 1}
-    assert _lib.HEADER_PATH.endswith("speechclip_hip.h") and _lib.SUPCON_HEADER_PATH.endswith("speechclip_hip_supcon.h")
+    eight = NEW_SYMBOLS + ("sc_vq_gumbel_f32", "sc_vq_noisy_rowstats", "sc_vq_soft_prob_f32", "sc_vq_soft_split_bf16", "sc_vq_soft_bwd2")
+    declared = _declared(open(_lib.HEADER_PATH).read())
+    assert all(declared.count(name) == 1 for name in eight)
+    fns = list(_lib.HEADER.functions)
+    assert len(fns) == 139 == len(set(declared)) and set(fns) == set(declared)
+    assert len(set(fns) - set(eight)) == 131 and sorted(fns[-8:]) == sorted(eight)           # the former 131, then the two blocks
+    assert _lib.DEFINES == {"SC_SEG_ROWS": 8, "SC_ATTN_SLACK": 64, "SC_CONV0_NSTAT": 66, "SC_WS_INFONCE": 0, "SC_WS_HUBERT_LAYER": 1,
+                            "SC_SUPCON_MAX_LOGIT_BYTES": GIB}
+    assert _lib.HEADER_PATH.endswith("speechclip_hip.h")
+    assert not hasattr(_lib, "SUPCON_HEADER") and not hasattr(_lib, "VQ_HEADER")
+    assert not os.path.exists(os.path.join(ROOT, "include", "speechclip_hip_supcon.h"))
+    assert not os.path.exists(os.path.join(ROOT, "include", "speechclip_hip_vq.h"))
     assert _lib.lib().sc_abi_version() == 7
 
 

@@ -1,6 +1,6 @@
-"""The quantiser's soft / Gumbel / learnable-temperature modes without a GPU: the C entry points of csrc/vq_modes.hip are declared in
-include/speechclip_hip_vq.h, bound from it and exported by every library build, while the main header, the supcon header and the ABI
-version stay what they were; the constructor takes every mode; every refusal - the module's, ops' operand checks, the C argument
+"""The quantiser's soft / Gumbel / learnable-temperature modes without a GPU: the C entry points (csrc/vq.hip) are declared in
+include/speechclip_hip.h, bound from it and exported by every library build, additive to the functions the header had, at the same ABI
+version; the constructor takes every mode; every refusal - the module's, ops' operand checks, the C argument
 checks - comes before any launch; a table holds no soft operand until a soft call asks for it."""
 import ctypes
 import os
@@ -13,36 +13,47 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("sc_vq_gumbel_f32", "sc_vq_noisy_rowstats", "sc_vq_soft_prob_f32", "sc_vq_soft_split_bf16", "sc_vq_soft_bwd2")
 
 
-def test_symbols_declared_in_the_third_header_bound_and_exported():
+def _declared(text):
+    return re.findall(r"\b(sc_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))
+
+
+def test_symbols_declared_in_the_header_bound_and_exported():
     from speechclip_plus_amd import _lib, build, ops
-    text = open(os.path.join(ROOT, "include", "speechclip_hip_vq.h")).read()
-    declared = set(re.findall(r"\b(sc_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", text, flags=re.S)))
-    assert declared == set(NEW_SYMBOLS) == set(_lib.VQ_HEADER.functions) == set(_lib.VQ_SIGNATURES)
+    text = open(os.path.join(ROOT, "include", "speechclip_hip.h")).read()
+    assert set(NEW_SYMBOLS) <= set(_declared(text)) and set(NEW_SYMBOLS) <= set(_lib.HEADER.functions) and set(NEW_SYMBOLS) <= set(_lib.SIGNATURES)
     assert "my_vector_quantizer.py:124-137" in text and 'extern "C"' in text
-    assert _lib.VQ_HEADER.structs == {} and _lib.VQ_DEFINES == {}
     v, f, i32, i64, u32 = ctypes.c_void_p, ctypes.c_float, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32
-    assert _lib.VQ_SIGNATURES["sc_vq_gumbel_f32"] == [v, i64, i32, i32, u32, v]
-    assert _lib.VQ_SIGNATURES["sc_vq_noisy_rowstats"] == [v, i64, i32, i32, f, u32, i32, v, v, v, v]
-    assert _lib.VQ_SIGNATURES["sc_vq_soft_prob_f32"] == [v, i64, v, v, i32, i32, f, u32, i32, v, i64, v]
-    assert _lib.VQ_SIGNATURES["sc_vq_soft_split_bf16"] == [v, i64, v, v, i32, i32, f, u32, i32, v, i32, i32, v]
-    assert _lib.VQ_SIGNATURES["sc_vq_soft_bwd2"] == [v, i64, v, v, v, i64, i32, i32, i32, f, u32, i32, v, i64, i32, v, v]
+    assert _lib.SIGNATURES["sc_vq_gumbel_f32"] == [v, i64, i32, i32, u32, v]
+    assert _lib.SIGNATURES["sc_vq_noisy_rowstats"] == [v, i64, i32, i32, f, u32, i32, v, v, v, v]
+    assert _lib.SIGNATURES["sc_vq_soft_prob_f32"] == [v, i64, v, v, i32, i32, f, u32, i32, v, i64, v]
+    assert _lib.SIGNATURES["sc_vq_soft_split_bf16"] == [v, i64, v, v, i32, i32, f, u32, i32, v, i32, i32, v]
+    assert _lib.SIGNATURES["sc_vq_soft_bwd2"] == [v, i64, v, v, v, i64, i32, i32, i32, f, u32, i32, v, i64, i32, v, v]
     for path in (_lib.LIB_PATH, _lib.DIAG_LIB_PATH, _lib.GELU_EXACT_LIB_PATH):           # all three link the same objects
         cdll = _lib._load(path)
-        for name, (restype, argtypes) in _lib.VQ_HEADER.functions.items():
+        for name in NEW_SYMBOLS:
+            restype, argtypes = _lib.HEADER.functions[name]
             fn = getattr(cdll, name)
             assert fn.restype is restype and list(fn.argtypes) == argtypes, (path, name)
-    assert "vq_modes.hip" in build.SOURCES
+    assert "vq.hip" in build.SOURCES and "vq_modes.hip" not in build.SOURCES
     for name in ("vq_gumbel", "vq_noisy_rowstats", "vq_soft_prob", "vq_soft_split", "vq_soft_table", "vq_soft_product", "vq_soft_bwd2"):
         assert callable(getattr(ops, name))
 
 
-def test_the_other_headers_and_the_abi_version_stay():
+def test_one_header_declares_them_once_and_the_abi_version_stays():
+    """The modes' five and the supervised contrastive loss's three entry points are declared exactly once, in the one header, beside
+    the 131 functions it had; no side header and no second table is left; the additions did not move the ABI version."""
     from speechclip_plus_amd import _lib
-    assert len(_lib.HEADER.functions) == 131 and not set(NEW_SYMBOLS) & set(_lib.HEADER.functions)
-    assert set(_lib.SUPCON_HEADER.functions) == {"sc_supcon_fwd", "sc_supcon_grad", "sc_supcon_workspace_floats"}
-    assert not set(NEW_SYMBOLS) & (set(_lib.SIGNATURES) | set(_lib.SUPCON_SIGNATURES))
-    assert _lib.DEFINES == {"SC_SEG_ROWS": 8, "SC_ATTN_SLACK": 64, "SC_CONV0_NSTAT": 66, "SC_WS_INFONCE": 0, "SC_WS_HUBERT_LAYER": 1}
-    assert _lib.VQ_HEADER_PATH.endswith("speechclip_hip_vq.h")
+    eight = NEW_SYMBOLS + ("sc_supcon_fwd", "sc_supcon_grad", "sc_supcon_workspace_floats")
+    declared = _declared(open(_lib.HEADER_PATH).read())
+    assert all(declared.count(name) == 1 for name in eight)
+    fns = list(_lib.HEADER.functions)
+    assert len(fns) == 139 == len(set(declared)) and set(fns) == set(declared)
+    assert len(set(fns) - set(eight)) == 131 and sorted(fns[-8:]) == sorted(eight)           # the former 131, then the two blocks
+    assert _lib.DEFINES == {"SC_SEG_ROWS": 8, "SC_ATTN_SLACK": 64, "SC_CONV0_NSTAT": 66, "SC_WS_INFONCE": 0, "SC_WS_HUBERT_LAYER": 1,
+                            "SC_SUPCON_MAX_LOGIT_BYTES": 1 << 30}
+    assert not hasattr(_lib, "SUPCON_HEADER") and not hasattr(_lib, "VQ_HEADER")
+    assert not os.path.exists(os.path.join(ROOT, "include", "speechclip_hip_supcon.h"))
+    assert not os.path.exists(os.path.join(ROOT, "include", "speechclip_hip_vq.h"))
     assert _lib.lib().sc_abi_version() == 7
 
 

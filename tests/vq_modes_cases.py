@@ -1,5 +1,5 @@
-"""The quantiser's soft / Gumbel / learnable-temperature modes restated on the host (csrc/vq_modes.hip under
-vector_quantizers.SimpleVectorQuantizer), written from the formulas of include/speechclip_hip_vq.h - no autograd, no reference code:
+"""The quantiser's soft / Gumbel / learnable-temperature modes restated on the host (csrc/vq.hip under
+vector_quantizers.SimpleVectorQuantizer), written from the formulas of include/speechclip_hip.h - no autograd, no reference code:
 
   * the numpy uint32 twin of the stateless noise: e = n V + v, w = hash32(e ^ seed), u = ((w >> 9) + 0.5) 2^-23, g = -log(-log u);
   * an fp64 reference of every mode's ``subword_prob``, targets, keywords and of the gradients

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The quantiser's soft modes (csrc/vq_modes.hip + the split-bf16 soft product) against the torch expression on the same GPU, on
+"""The quantiser's soft modes (the mode kernels of csrc/vq.hip + the split-bf16 soft product) against the torch expression on the same GPU, on
 tools/bench_supcon.py's protocol: ONE process, the two routes alternating in blocks after a warm-up at every switch (and alternating
 who goes first), device events around every block, ms per call.  One JSON line per (shape, mode) with the median and every block of
 each route, the spread of the blocks, and how far the two routes' results are apart.
@@ -7,7 +7,7 @@ each route, the spread of the blocks, and how far the two routes' results are ap
   (k) the kernel route from the masked scores x [Nk, V] on: row statistics of x + g (sc_vq_noisy_rowstats), s as bf16 hi + lo
       (sc_vq_soft_split_bf16), keywords = s . table as one bf16 GEMM over [hi | hi | lo] x [hi | lo | hi] cut into fp32 partials +
       sc_colsum_f32; backward: t = g_out . table^T (bf16 GEMM), dx = s (t - <s, t>) / tau in bf16 (sc_vq_soft_bwd2) - what
-      vector_quantizers._KeywordVQModeFn issues between the cosine scores and the product with the normalised table
+      vector_quantizers._KeywordVQFn issues in a soft mode between the cosine scores and the product with the normalised table
   (t) fp32 torch on the same scores and the same materialised noise (ops.vq_gumbel): softmax((x + g) / tau) @ table, forward plus
       autograd backward to x
 
