@@ -31,6 +31,12 @@ DEFINES = HEADER.defines            # the header's integer #defines: SC_SEG_ROWS
 # sc_workspace_bytes, sc_infonce_workspace_floats, sc_supcon_workspace_floats, sc_hash32) are bound from HEADER.functions like these, with
 # their own restype
 SIGNATURES = {name: argtypes for name, (restype, argtypes) in HEADER.functions.items() if restype is ctypes.c_int32}
+# The cross-batch queue's three entry points (csrc/infonce_queue.hip) stand in a header of their own, read by the same reader and
+# bound by the same loop: speechclip_hip.h and the tables above are as they were before them.
+QUEUE_HEADER_PATH = os.path.join(INCLUDE, "speechclip_hip_queue.h")
+QUEUE_HEADER = _header.read(QUEUE_HEADER_PATH)
+if QUEUE_HEADER.structs or QUEUE_HEADER.defines or set(QUEUE_HEADER.functions) & set(HEADER.functions):
+    raise RuntimeError(f"{QUEUE_HEADER_PATH} declares prototypes only, none of them {HEADER_PATH}'s")
 
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libspeechclip_hip_diag.so")
 GELU_EXACT_LIB_PATH = os.path.join(_HERE, "csrc", "libspeechclip_hip_gelu_exact.so")   # checker build (build.py), tests only
@@ -79,7 +85,7 @@ def _load(path: str) -> ctypes.CDLL:
             f"{path} not found: the HIP extension is not built (python -m speechclip_plus_amd.build). "
             "speechclip_plus_amd has no CPU / eager fallback.")
     cdll = ctypes.CDLL(path)
-    for name, (restype, argtypes) in HEADER.functions.items():
+    for name, (restype, argtypes) in list(HEADER.functions.items()) + list(QUEUE_HEADER.functions.items()):
         fn = getattr(cdll, name)            # AttributeError if the symbol is missing: loud
         fn.argtypes = argtypes
         fn.restype = restype

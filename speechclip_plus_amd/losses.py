@@ -2,7 +2,8 @@
 
 Same constructor (temperature, temperature_trainable, margin, dcl, a2b, b2a - every option built), ``forward(feat_A, feat_B,
 index=None) -> scalar`` (keywords ``bank`` / ``bank_ids`` / ``neg_idx``: mined negatives from a constant bank beside the batch, see
-``forward``), ``current_temperature`` and the ``temperature`` parameter / attribute (log(1/T) when trainable, 1/T
+``forward``; the module's call also takes ``queue_A`` / ``queue_B`` / ``queue_ids``: a cross-batch queue of past embeddings,
+negatives in both directions), ``current_temperature`` and the ``temperature`` parameter / attribute (log(1/T) when trainable, 1/T
 otherwise).  No MAX_EYE = 256 cap (losses.py:126: the reference cannot run B > 256; the masks are computed in-kernel from
 ``index``).  Forward = one launch (csrc/loss_optim.hip: sc_infonce_fwd); the temperature reaches the kernels as a DEVICE scalar,
 so a trainable temperature costs no host synchronisation in the step.
@@ -83,6 +84,63 @@ class _InfoNCENegFn(torch.autograd.Function):
         return (dA, dB, dT) + (None,) * 9
 
 
+class _InfoNCEQueueFn(torch.autograd.Function):
+    """``_InfoNCEFn`` with BOTH denominators extended by a cross-batch queue (csrc/infonce_queue.hip) as one node: the plain forward, the
+    one or two score products on the exact-fp32 GEMM, then the extension; backward = ``infonce_grad`` on the extended statistics, the two
+    in-batch products, the weights in place of the scores, then the one or two queue products.  The scores are consumed by the backward
+    (they become the weights), so the node runs backward once."""
+
+    @staticmethod
+    def forward(ctx, feat_A, feat_B, inv_temp, index, margin, dcl, a2b, b2a, queue_A, queue_B, queue_ids, holder):
+        A = ops.aligned16(feat_A.detach().float().contiguous())
+        Bm = ops.aligned16(feat_B.detach().float().contiguous())
+        it = inv_temp.detach().float().reshape(1).contiguous()
+        ids = index.contiguous() if index is not None else None
+        qA = ops.bank_rows(queue_A.detach()) if b2a else None                  # the image anchors' extras: past speech rows
+        qB = ops.bank_rows(queue_B.detach()) if a2b else None                  # the speech anchors' extras: past image rows
+        loss, logits, lse_row, lse_col = ops.infonce_fwd(A, Bm, ids, it, margin, dcl, a2b, b2a)
+        x_A = ops.queue_scores(A, qB) if a2b else None
+        x_B = ops.queue_scores(Bm, qA) if b2a else None
+        loss, lse_row, lse_col, used_A, used_B = ops.infonce_queue_fwd(x_A, x_B, ids, queue_ids, it, loss, lse_row, lse_col, logits,
+                                                                        A.shape[1], a2b, b2a)
+        holder.last_queue_used = (used_A, used_B)
+        none = torch.empty(0)
+        ctx.save_for_backward(A, Bm, logits, lse_row, lse_col, it, ids if ids is not None else none, qA if b2a else none,
+                              qB if a2b else none, x_A if a2b else none, x_B if b2a else none)
+        ctx.has_ids = ids is not None
+        ctx.opts = (margin, dcl, a2b, b2a)
+        ctx.consumed = False
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        A, Bm, logits, lse_row, lse_col, it, ids, qA, qB, x_A, x_B = ctx.saved_tensors
+        margin, dcl, a2b, b2a = ctx.opts
+        if ctx.consumed:
+            raise RuntimeError("MaskedContrastiveLoss with a queue: the backward turns the saved scores into the weights in place and "
+                               "runs once per forward")
+        ctx.consumed = True
+        ids = ids if ctx.has_ids else None
+        gscale = g.float().reshape(1).contiguous()
+        G, dot = ops.infonce_grad(logits, ids, lse_row, lse_col, gscale, it, margin, dcl, a2b, b2a)
+        dA = dB = dT = None
+        want_dA, want_dB, want_dT = ctx.needs_input_grad[:3]
+        if want_dA:
+            dA = ops.sgemm_mfma(G, Bm, b_kmajor=True)                          # G . B: the in-batch share
+        if want_dB:
+            dB = ops.sgemm_mfma(G, A, a_kmajor=True, b_kmajor=True)            # G^T . A
+        Nq = (x_A if a2b else x_B).shape[1]
+        if Nq > 0 and A.shape[0] > 0 and (want_dA or want_dB or want_dT):
+            w_A, w_B, dot = ops.infonce_queue_grad(x_A if a2b else None, x_B if b2a else None, lse_row, lse_col, gscale, it, a2b, b2a, dot)
+            if want_dA and a2b:
+                dA += ops.sgemm_mfma(w_A, qB, b_kmajor=True)                   # w_A . queue_B (w already carries c inv_temp)
+            if want_dB and b2a:
+                dB += ops.sgemm_mfma(w_B, qA, b_kmajor=True)                   # w_B . queue_A
+        if want_dT:
+            dT = dot.sum()
+        return (dA, dB, dT) + (None,) * 9
+
+
 class MaskedContrastiveLoss(nn.Module):
     def __init__(self, temperature: float = 0.07, temperature_trainable: bool = False, margin: float = 0.0,
                  dcl: bool = False, a2b: bool = True, b2a: bool = True):
@@ -96,6 +154,8 @@ class MaskedContrastiveLoss(nn.Module):
             self.temperature = 1 / temperature
         self._inv_temp_dev = {}
         self.last_used = None          # int32 [Bg] device tensor: slots per anchor that took part in the last call with a bank
+        self._queue = (None, None, None)   # (queue_A, queue_B, queue_ids) of the call in progress: see __call__
+        self.last_queue_used = None    # (used_A, used_B), int32 [Bg] device tensors: queue entries admitted per anchor, last call with a queue
 
     @property
     def current_temperature(self) -> float:
@@ -113,6 +173,19 @@ class MaskedContrastiveLoss(nn.Module):
             return self.temperature.detach().float().exp()
         return float(self.temperature)
 
+    def __call__(self, *args, queue_A: torch.Tensor = None, queue_B: torch.Tensor = None, queue_ids: torch.LongTensor = None, **kwargs):
+        """``criterion(feat_A, feat_B, index=None, *, bank=, bank_ids=, neg_idx=, queue_A=, queue_B=, queue_ids=)``: ``forward``'s own
+        arguments and the cross-batch queue's three keywords (described under ``forward``).  ``forward`` keeps the parameter list it has
+        had since the bank - code that inspects it sees no change - so the queue travels beside it, in ``_queue``, for the length of this
+        call: hooks run as for any module; one criterion object is not called from two threads at once."""
+        if queue_A is None and queue_B is None and queue_ids is None:
+            return super().__call__(*args, **kwargs)
+        self._queue = (queue_A, queue_B, queue_ids)
+        try:
+            return super().__call__(*args, **kwargs)
+        finally:
+            self._queue = (None, None, None)
+
     def forward(self, feat_A: torch.Tensor, feat_B: torch.Tensor, index: torch.LongTensor = None, *, bank: torch.Tensor = None,
                 bank_ids: torch.LongTensor = None, neg_idx: torch.LongTensor = None) -> torch.Tensor:
         """``bank`` [N, E] fp32 (constant: no gradient, a bank that requires grad is refused), ``bank_ids`` [N] int64 (with ``index``,
@@ -121,17 +194,32 @@ class MaskedContrastiveLoss(nn.Module):
         0 <= r < N and, with ids, bank_ids[r] is the id of NO row of the batch - the false negative and the image that already stands in
         the batch are left out, as are the -1 tails.  ``bank`` and ``neg_idx`` come together; without them the call is the plain
         loss.  With ``a2b=False`` the extras have no denominator to enter: a ValueError.  ``last_used`` [Bg] int32 (a device tensor, no
-        sync) counts the slots that took part in the last call."""
+        sync) counts the slots that took part in the last call.
+
+        ``queue_A`` / ``queue_B`` [Nq, E] fp32 (past feat_A / feat_B rows, unit-normalised by the caller; constants: no gradient, a queue
+        that requires grad is refused) and ``queue_ids`` [Nq] int64 (with ``index``, both or neither): a cross-batch queue, plain
+        negatives (no margin) in BOTH directions - queue_B joins the feat_A -> feat_B denominator, queue_A the feat_B -> feat_A one.
+        Entry (i, q) is admitted iff there are no ids or queue_ids[q] != index[i]: a queued item is a false negative only for the anchor
+        that has its id.  A direction that is off needs no queue; an enabled one without its queue is a ValueError, as is a bank
+        together with a queue.  An empty queue (Nq = 0) is the plain loss to the bit.  ``last_queue_used`` = (used_A, used_B), [Bg] int32
+        device tensors (no sync), counts the entries admitted per anchor in the last call.  The three are keywords of the module's CALL
+        (``__call__``), not of this method."""
+        queue_A, queue_B, queue_ids = self._queue
         assert feat_A.shape == feat_B.shape, (feat_A.shape, feat_B.shape)
         if index is not None:
             assert index.shape[0] == feat_A.shape[0], (index.shape, feat_A.shape)
         with_bank = bank is not None or neg_idx is not None or bank_ids is not None
+        with_queue = queue_A is not None or queue_B is not None or queue_ids is not None
+        if with_bank and with_queue:
+            raise ValueError("MaskedContrastiveLoss: extra negatives come from a bank or a queue, not both")
         if with_bank:                                      # every refusal before a launch
             if (index is None) != (bank_ids is None):
                 raise ValueError("MaskedContrastiveLoss: ids on one side only - give index and bank_ids, or neither")
             if bank is None or neg_idx is None:
                 raise ValueError("MaskedContrastiveLoss: bank and neg_idx come together (a bank without lists, or lists without a bank)")
             ops.neg_operands("MaskedContrastiveLoss", feat_A, bank, neg_idx, index, bank_ids, self.a2b)
+        if with_queue:
+            ops.queue_operands("MaskedContrastiveLoss", feat_A, feat_B, queue_A, queue_B, index, queue_ids, self.a2b, self.b2a)
         if self.temperature_trainable:
             inv_temp = torch.exp(self.temperature)
         else:                                              # constant: one device scalar per device, built once
@@ -142,6 +230,9 @@ class MaskedContrastiveLoss(nn.Module):
         if with_bank:
             return _InfoNCENegFn.apply(feat_A, feat_B, inv_temp, index, max(self.margin, 0.0), self.dcl, self.a2b, self.b2a, bank, bank_ids,
                                        neg_idx, self)
+        if with_queue:
+            return _InfoNCEQueueFn.apply(feat_A, feat_B, inv_temp, index, max(self.margin, 0.0), self.dcl, self.a2b, self.b2a, queue_A,
+                                         queue_B, queue_ids, self)
         return _InfoNCEFn.apply(feat_A, feat_B, inv_temp, index, max(self.margin, 0.0), self.dcl, self.a2b, self.b2a)
 
 
@@ -223,7 +314,7 @@ class SupConLoss(nn.Module):
         return float(self.temperature)
 
     def forward(self, features=None, labels=None, mask=None, *, feat_A=None, feat_B=None, index=None, bank=None, bank_ids=None,
-                neg_idx=None):
+                neg_idx=None, queue_A=None, queue_B=None, queue_ids=None):
         """With ``features`` [bsz, n_views, ...] (trailing dimensions flattened), ``labels`` [bsz] or ``mask`` [bsz, bsz] (float, may be
         asymmetric, any weights; no gradient) it is the reference's call, with the reference's ValueErrors.
 
@@ -231,9 +322,13 @@ class SupConLoss(nn.Module):
         stack((feat_A, feat_B), 1)``, ``labels = index``.  Speech (feat_A) is view 0, so ``contrast_mode="one"`` anchors on speech only.
         This adapter is this project's decision: the reference's compute_loss passes ``feat_A=, feat_B=, index=`` to whatever criterion
         the yaml names, which its own SupConLoss.forward(features, labels, mask) answers with a TypeError - the reference cannot train
-        with the class it ships.  Mined negatives (``bank`` / ``bank_ids`` / ``neg_idx``) stay MaskedContrastiveLoss's: a ValueError."""
+        with the class it ships.  Mined negatives (``bank`` / ``bank_ids`` / ``neg_idx``) and the cross-batch
+        queue (``queue_A`` / ``queue_B`` / ``queue_ids``) stay MaskedContrastiveLoss's: a ValueError."""
         if bank is not None or bank_ids is not None or neg_idx is not None:
             raise ValueError("SupConLoss takes no negative bank (bank / bank_ids / neg_idx): mined negatives are MaskedContrastiveLoss's")
+        if queue_A is not None or queue_B is not None or queue_ids is not None:
+            raise ValueError("SupConLoss takes no negative queue (queue_A / queue_B / queue_ids): the cross-batch queue is "
+                             "MaskedContrastiveLoss's")
         if features is None:
             if feat_A is None or feat_B is None:
                 raise ValueError("SupConLoss: give `features` [bsz, n_views, ...], or feat_A and feat_B")

@@ -472,6 +472,9 @@ class KWClip_GeneralTransformer(nn.Module):
             raise ValueError("set_negative_bank: embeddings must be a [N, E] tensor")
         if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.shape != (embeddings.shape[0],):
             raise ValueError(f"set_negative_bank: ids must be torch.int64 of shape ({embeddings.shape[0]},)")
+        if getattr(self, "_neg_queue", None) is not None:
+            raise ValueError("set_negative_bank: a negative queue is set - extra negatives come from a bank or a queue, not both "
+                             "(clear_negative_queue() first)")
         rows = unit_rows(embeddings.detach().float()).detach()
         ids = ids.detach().to(rows.device).contiguous()
         self._neg_bank = (rows, ids, GalleryIndex(rows, ids=ids), k)
@@ -479,9 +482,66 @@ class KWClip_GeneralTransformer(nn.Module):
     def clear_negative_bank(self):
         self._neg_bank = None
 
+    def _loss_terms(self):
+        """the branch terms of ``compute_loss``, in its order"""
+        return [t for t in ("cascaded", "parallel") if self.config.model_settings.get(f"{t}_objective_weight", 0.0) > 0.0]
+
+    def set_negative_queue(self, size: int):
+        """A cross-batch negative queue for the contrastive loss: rings of the last ``size`` speech and image embeddings the model
+        produced, used by ``compute_loss`` in TRAIN mode as plain negatives in both directions (``MaskedContrastiveLoss.forward``'s
+        ``queue_A`` / ``queue_B`` / ``queue_ids``); they get no gradient.  One [size, E] speech ring per branch term, one image ring and
+        one id ring, on the model's device, as plain attributes - no buffers: the state-dict keys stay the reference's.  ``head`` (the
+        next row to write) and ``n_valid`` (rows filled, at most ``size``) are host integers.
+
+        A train-mode ``compute_loss`` first writes the rows the PREVIOUS train-mode call stashed (at most two slice copies on wrap-around;
+        of a batch longer than the ring its last ``size`` rows), then hands the criterion ``ring[:n_valid]``, then stashes its own detached
+        features and ids: tensors saved for a backward are never modified before it runs, and the first call, whose queue is empty, is
+        the plain loss to the bit.  Eval mode and ``clear_negative_queue()`` neither read nor write.  ``compute_loss`` runs on the
+        gathered batch on every rank, so every rank enqueues the same rows: data parallelism needs no new collective."""
+        size = int(size)
+        if size < 1:
+            raise ValueError(f"set_negative_queue: size >= 1 (size {size})")
+        if getattr(self, "_neg_bank", None) is not None:
+            raise ValueError("set_negative_queue: a negative bank is set - extra negatives come from a bank or a queue, not both "
+                             "(clear_negative_bank() first)")
+        dev, E = self._device, int(self.subword_embd_dim)
+        self._neg_queue = {
+            "size": size, "head": 0, "n_valid": 0, "pending": None,
+            "speech": {t: torch.zeros(size, E, device=dev, dtype=torch.float32) for t in self._loss_terms()},
+            "image": torch.zeros(size, E, device=dev, dtype=torch.float32),
+            "ids": torch.zeros(size, device=dev, dtype=torch.int64),
+        }
+
+    def clear_negative_queue(self):
+        self._neg_queue = None
+
+    @staticmethod
+    def _ring_write(ring: torch.Tensor, rows: torch.Tensor, head: int):
+        """``rows`` (at most the ring's length) into ``ring`` from row ``head`` on: one slice copy, two where the batch straddles the end"""
+        size, n = ring.shape[0], rows.shape[0]
+        first = min(n, size - head)
+        ring[head: head + first].copy_(rows[:first])
+        if first < n:
+            ring[: n - first].copy_(rows[first:])
+
+    def _queue_advance(self, q: dict):
+        """write what the previous train-mode call stashed"""
+        pending, q["pending"] = q["pending"], None
+        if pending is None:
+            return
+        speech, image, ids = pending
+        size, n = q["size"], ids.shape[0]
+        keep = min(n, size)                         # a batch longer than the ring leaves its last ``size`` rows
+        for t, ring in q["speech"].items():
+            self._ring_write(ring, speech[t][n - keep:], q["head"])
+        self._ring_write(q["image"], image[n - keep:], q["head"])
+        self._ring_write(q["ids"], ids[n - keep:], q["head"])
+        q["head"] = (q["head"] + keep) % size
+        q["n_valid"] = min(size, q["n_valid"] + keep)
+
     def compute_loss(self, inputDict: dict):
         """kwClip.py:999-1040.  With a negative bank set (``set_negative_bank``) and the model in train mode, every branch term takes
-        the bank rows mined for its anchors beside the batch."""
+        the bank rows mined for its anchors beside the batch; with a negative queue set (``set_negative_queue``), the queued rows."""
         assert isinstance(inputDict, dict)
         required_keys = {"id", "image_feat"}
         assert required_keys.issubset(set(inputDict.keys())), f"required: {required_keys}, input: {inputDict.keys()}"
@@ -489,6 +549,12 @@ class KWClip_GeneralTransformer(nn.Module):
         terms = []                                  # (weight, loss term): summed below without 0 + / 1.0 * launches
         image_feat = inputDict["image_feat"].float()
         id = inputDict["id"]
+        queue = getattr(self, "_neg_queue", None) if self.training else None
+        if queue is not None:
+            if image_feat.shape[1] != queue["image"].shape[1]:
+                raise ValueError(f"compute_loss: the negative queue holds rows of width {queue['image'].shape[1]}, the features have "
+                                 f"{image_feat.shape[1]}")
+            self._queue_advance(queue)
         for branchType in ["cascaded", "parallel"]:
             loss_weight = self.config.model_settings.get(f"{branchType}_objective_weight", 0.0)
             if loss_weight > 0.0:
@@ -496,7 +562,12 @@ class KWClip_GeneralTransformer(nn.Module):
                 assert feats_key in inputDict, f"{inputDict.keys()}"
                 mined = {}                          # train mode with a bank set: the bank, its ids and this term's mined lists
                 neg_bank = getattr(self, "_neg_bank", None) if self.training else None
-                if neg_bank is not None:
+                if queue is not None:               # ... with a queue set: this term's speech ring, the image ring and the id ring
+                    nv = queue["n_valid"]
+                    mined = {"queue_A": queue["speech"][branchType][:nv], "queue_B": queue["image"][:nv], "queue_ids": queue["ids"][:nv]}
+                    if id is None:
+                        del mined["queue_ids"]
+                elif neg_bank is not None:
                     from .retrieval import hard_negatives
                     rows, bank_ids, index, k = neg_bank
                     lists = hard_negatives(inputDict[feats_key].float().detach(), index, id, None, k)[1]
@@ -504,6 +575,9 @@ class KWClip_GeneralTransformer(nn.Module):
                 losses_[f"{branchType[0]}_cl_loss"] = self.criterion(feat_A=inputDict[feats_key].float(),
                                                                      feat_B=image_feat, index=id, **mined)
                 terms.append((float(loss_weight), losses_[f"{branchType[0]}_cl_loss"]))
+        if queue is not None:                       # enqueued at the start of the next train-mode call, not here: see set_negative_queue
+            queue["pending"] = ({t: inputDict[f"{t}_audio_feat"].detach().float() for t in queue["speech"]}, image_feat.detach(),
+                                id.detach().to(torch.int64))
         if "cif_quantity_out" in inputDict and "cif_target_len" in inputDict and hasattr(self, "quantity_loss_criteria"):
             losses_["quantity_loss"] = self.quantity_loss_criteria(inputDict["cif_quantity_out"], inputDict["cif_target_len"])
             terms.append((float(self.quantity_loss_weight), losses_["quantity_loss"]))

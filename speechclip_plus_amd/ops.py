@@ -2043,6 +2043,139 @@ def infonce_neg_grad(A: torch.Tensor, bank: torch.Tensor, neg_idx: torch.Tensor,
     return dA, dot
 
 
+QUEUE_MAX_SCORES = 1 << 26         # scores [Bg, Nq] fp32 per side (256 MiB): csrc/infonce_queue.hip refuses more
+
+
+def queue_operands(name: str, A, B, queue_A, queue_B, ids, queue_ids, a2b: bool = True, b2a: bool = True) -> None:
+    """The operands of the loss with a cross-batch queue, checked before any launch, in ``neg_operands``' order - format errors first,
+    "device tensors only" last: ids on one side only; dtypes and shapes (A, B [Bg, E] fp32 with E % 4 == 0); the queue of every enabled
+    side given (``queue_B`` [Nq, E] for a2b, ``queue_A`` [Nq, E] for b2a; a queue for a side that is off is ignored) as a 2-D fp32 tensor
+    of width E, both of one length; ids [Bg] / queue_ids [Nq] int64 contiguous; Bg Nq within QUEUE_MAX_SCORES; a queue that requires
+    grad; the device."""
+    if (ids is None) != (queue_ids is None):
+        raise ValueError(f"{name}: ids on one side only - give the batch's ids and queue_ids, or neither")
+    for what, t in (("A", A), ("B", B)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{name}: {what} must be a 2-D tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: {what} must be torch.float32, not {t.dtype}")
+    Bg, E = A.shape
+    if B.shape != A.shape or E % 4 != 0 or E == 0:
+        raise ValueError(f"{name}: A {tuple(A.shape)} and B {tuple(B.shape)} must be one shape [Bg, E], E a multiple of 4")
+    if not (a2b or b2a):
+        raise ValueError(f"{name}: a2b and b2a are both off")
+    queues = ([("queue_B", queue_B, "a2b")] if a2b else []) + ([("queue_A", queue_A, "b2a")] if b2a else [])
+    for what, t, side in queues:
+        if t is None:
+            raise ValueError(f"{name}: {side} is on and {what} is missing - every enabled side needs its queue")
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{name}: {what} must be a 2-D tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: {what} must be torch.float32, not {t.dtype}")
+        if t.shape[1] != E:
+            raise ValueError(f"{name}: {what} {tuple(t.shape)} must share E = {E} with A")
+    Nq = queues[0][1].shape[0]
+    if len(queues) == 2 and queues[1][1].shape[0] != Nq:
+        raise ValueError(f"{name}: queue_A has {queue_A.shape[0]} rows and queue_B {queue_B.shape[0]} - one ring position, one length")
+    if ids is not None:
+        check_filter_tensor(name, "ids", ids, Bg)
+        check_filter_tensor(name, "queue_ids", queue_ids, Nq)
+    if Bg * Nq > QUEUE_MAX_SCORES:
+        raise ValueError(f"{name}: Bg Nq = {Bg} x {Nq} scores per side, at most 2^26 ({QUEUE_MAX_SCORES}, 256 MiB of fp32) are served")
+    for what, t, _ in queues:
+        if t.requires_grad:
+            raise ValueError(f"{name}: the queue is constant - it gets no gradient ({what}.requires_grad is set)")
+    given = [("A", A), ("B", B)] + [(w, t) for w, t, _ in queues] + ([("ids", ids), ("queue_ids", queue_ids)] if ids is not None else [])
+    for what, t in given:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} runs on the HIP kernels: device tensors only ({what})")
+    for what, t in given:
+        if t.device != A.device:
+            raise ValueError(f"{name}: {what} is on {t.device}, A on {A.device}")
+
+
+def queue_scores(anchors: torch.Tensor, queue: torch.Tensor) -> torch.Tensor:
+    """The raw dot products [Bg, Nq] of the anchors against the queue's rows on the exact-fp32 GEMM, as a view of a buffer whose rows
+    are whole 16-byte pieces (leading dimension Nq rounded up to 4): what ``infonce_queue_fwd`` takes over."""
+    Bg, Nq = anchors.shape[0], queue.shape[0]
+    ldx = (Nq + 3) // 4 * 4
+    x = torch.empty(Bg, ldx, device=anchors.device, dtype=torch.float32)[:, :Nq]
+    if Bg and Nq:
+        sgemm_mfma(anchors, bank_rows(queue), out=x)
+    return x
+
+
+def _queue_x(name: str, x: Optional[torch.Tensor], Bg: int, Nq: int):
+    """-> the leading dimension of a score buffer (``queue_scores``' form)"""
+    assert x.dtype == torch.float32 and x.dim() == 2 and tuple(x.shape) == (Bg, Nq), (name, tuple(x.shape), (Bg, Nq))
+    ldx = x.stride(0)
+    assert (x.stride(1) == 1 or Nq <= 1) and ldx >= Nq and ldx % 4 == 0 and x.data_ptr() % 16 == 0, f"{name}: rows of whole 16-byte pieces"
+    assert x.untyped_storage().nbytes() - x.storage_offset() * 4 >= Bg * ldx * 4, f"{name}: the last row's pad columns lie outside the storage"
+    return ldx
+
+
+def infonce_queue_fwd(x_A: Optional[torch.Tensor], x_B: Optional[torch.Tensor], ids: Optional[torch.Tensor],
+                      queue_ids: Optional[torch.Tensor], inv_temp: torch.Tensor, loss: torch.Tensor, lse_row: torch.Tensor,
+                      lse_col: torch.Tensor, logits: torch.Tensor, E: int, a2b: bool = True, b2a: bool = True):
+    """The plain call's denominators extended by a cross-batch queue (sc_infonce_queue_fwd, csrc/infonce_queue.hip).  ``x_A`` / ``x_B``
+    [Bg, Nq] are ``queue_scores(A, queue_B)`` / ``queue_scores(B, queue_A)`` (the one of a side that is off may be None) and are
+    rewritten IN PLACE: inv_temp x where the entry is admitted - no ids, or queue_ids[q] != ids[i] - and -inf elsewhere.  ``loss`` /
+    ``lse_row`` / ``lse_col`` / ``logits`` are ``infonce_fwd``'s outputs for the same A, B, ids and options.
+    -> (loss [1], lse_row_ext [Bg], lse_col_ext [Bg], used_A [Bg] int32, used_B [Bg] int32).  An empty queue or batch launches nothing
+    and returns the plain statistics themselves."""
+    Bg = logits.shape[0]
+    assert (a2b or b2a) and (x_A is not None or not a2b) and (x_B is not None or not b2a)
+    x_A, x_B = x_A if a2b else None, x_B if b2a else None
+    Nq = (x_A if a2b else x_B).shape[1]
+    if (ids is None) != (queue_ids is None):
+        raise ValueError("infonce_queue_fwd: ids on one side only - give the batch's ids and queue_ids, or neither")
+    if Bg * Nq > QUEUE_MAX_SCORES:
+        raise ValueError(f"infonce_queue_fwd: Bg Nq = {Bg} x {Nq} scores per side, at most 2^26 ({QUEUE_MAX_SCORES}, 256 MiB of fp32) are served")
+    assert inv_temp.dtype == torch.float32 and inv_temp.is_cuda and inv_temp.numel() == 1
+    assert logits.shape == (Bg, Bg) and logits.is_contiguous() and lse_row.shape == (Bg,) and lse_col.shape == (Bg,)
+    assert logits.dtype == lse_row.dtype == lse_col.dtype == torch.float32 and lse_row.is_contiguous() and lse_col.is_contiguous()
+    dev = logits.device
+    used_A, used_B = torch.zeros(Bg, device=dev, dtype=torch.int32), torch.zeros(Bg, device=dev, dtype=torch.int32)
+    if Bg == 0 or Nq == 0:
+        return loss, lse_row, lse_col, used_A, used_B
+    ldx = [_queue_x("infonce_queue_fwd", x, Bg, Nq) for x in (x_A, x_B) if x is not None]
+    assert len(set(ldx)) == 1, "infonce_queue_fwd: x_A and x_B of one leading dimension"
+    if ids is not None:
+        check_filter_tensor("infonce_queue_fwd", "ids", ids, Bg)
+        check_filter_tensor("infonce_queue_fwd", "queue_ids", queue_ids, Nq)
+    lse_row_ext, lse_col_ext = torch.empty_like(lse_row), torch.empty_like(lse_col)
+    loss_ext = torch.empty(1, device=dev, dtype=torch.float32)
+    ws_floats = int(lib().sc_infonce_queue_workspace_floats(Bg, Nq))
+    if ws_floats < 0:
+        check(ws_floats, "sc_infonce_queue_workspace_floats")
+    ws = torch.empty(ws_floats, device=dev, dtype=torch.float32)
+    check(lib().sc_infonce_queue_fwd(_p(x_A), _p(x_B), ldx[0], _p(ids), _p(queue_ids), _p(inv_temp), _p(lse_row), _p(lse_col), _p(logits), Bg,
+                                     int(E), Nq, int(a2b), int(b2a), _p(lse_row_ext), _p(lse_col_ext), _p(used_A), _p(used_B), _p(loss_ext),
+                                     _p(ws), _stream()), "sc_infonce_queue_fwd")
+    return loss_ext, lse_row_ext, lse_col_ext, used_A, used_B
+
+
+def infonce_queue_grad(x_A: Optional[torch.Tensor], x_B: Optional[torch.Tensor], lse_row_ext: torch.Tensor, lse_col_ext: torch.Tensor,
+                       gscale: torch.Tensor, inv_temp: torch.Tensor, a2b: bool, b2a: bool, dot: torch.Tensor):
+    """The extras' weights, IN PLACE (sc_infonce_queue_grad): ``x_A`` / ``x_B`` as ``infonce_queue_fwd`` left them become w = c inv_temp
+    e^{x - lse_ext}, c = gscale / (Bg n_dir), exactly 0 where x was -inf - so dA += w_A . queue_B and dB += w_B . queue_A need no
+    further scaling - and ``dot`` [Bg] (``infonce_grad``'s, run on the extended statistics) += c sum_q p x / inv_temp over both sides.
+    -> (w_A, w_B, dot)"""
+    Bg = lse_row_ext.shape[0]
+    assert (a2b or b2a) and (x_A is not None or not a2b) and (x_B is not None or not b2a)
+    x_A, x_B = x_A if a2b else None, x_B if b2a else None
+    Nq = (x_A if a2b else x_B).shape[1]
+    if Bg == 0 or Nq == 0:
+        return x_A, x_B, dot
+    ldx = [_queue_x("infonce_queue_grad", x, Bg, Nq) for x in (x_A, x_B) if x is not None]
+    assert len(set(ldx)) == 1, "infonce_queue_grad: x_A and x_B of one leading dimension"
+    assert lse_row_ext.shape == lse_col_ext.shape == dot.shape == (Bg,) and dot.dtype == torch.float32 and dot.is_contiguous()
+    assert lse_row_ext.is_contiguous() and lse_col_ext.is_contiguous() and gscale.numel() == 1 and inv_temp.numel() == 1
+    check(lib().sc_infonce_queue_grad(_p(x_A), _p(x_B), ldx[0], _p(lse_row_ext), _p(lse_col_ext), _p(gscale), _p(inv_temp), Bg, Nq, int(a2b),
+                                      int(b2a), _p(dot), _stream()), "sc_infonce_queue_grad")
+    return x_A, x_B, dot
+
+
 _SUPCON_WS = {}
 SUPCON_MAX_LOGIT_BYTES = DEFINES["SC_SUPCON_MAX_LOGIT_BYTES"]      # 1 GiB of logits [Na, N] fp32
 
