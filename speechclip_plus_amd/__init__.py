@@ -56,7 +56,7 @@ from .speech_encoder import FairseqSpeechEncoder_Hubert, HubertArch, S3prlSpeech
 from .kw_branches import KW_CascadedBranch, KW_CascadedBranchPlus, KW_HybridBranchPlus, KW_ParallelBranch
 from .transformer_models import MultiheadAttentionAndNorm, TransformerEncoder
 from .weighted_sum import WeightedSumLayer
-from .losses import MaskedContrastiveLoss, SupConLoss
+from .losses import MaskedContrastiveLoss, SigmoidContrastiveLoss, SupConLoss
 from .retrieval import (CompactGalleryIndex, GalleryIndex, compact_eps, hard_negatives, mutual_ranks, mutual_ranks_sharded, mutual_recall,
                         mutual_recall_sharded, mutualRetrieval, recall_from_ranks, search, search_compact, search_sharded, ShardedGalleryIndex)
 
@@ -64,5 +64,5 @@ __all__ = ["Config", "load_config", "KWClip_GeneralTransformer", "base_parallel_
            "cascaded_large_config", "KW_CascadedBranch", "KW_CascadedBranchPlus",
            "KW_HybridBranchPlus", "FairseqSpeechEncoder_Hubert", "HubertArch",
            "random_hubert_state_dict", "random_wavlm_state_dict", "S3prlSpeechEncoderPlus", "KW_ParallelBranch", "TransformerEncoder", "MultiheadAttentionAndNorm",
-           "WeightedSumLayer", "MaskedContrastiveLoss", "SupConLoss", "mutualRetrieval", "GalleryIndex", "search", "mutual_ranks", "recall_from_ranks", "mutual_recall", "set_dropout", "hw_queue_status",
+           "WeightedSumLayer", "MaskedContrastiveLoss", "SupConLoss", "SigmoidContrastiveLoss", "mutualRetrieval", "GalleryIndex", "search", "mutual_ranks", "recall_from_ranks", "mutual_recall", "set_dropout", "hw_queue_status",
            "CompactGalleryIndex", "search_compact", "compact_eps", "hard_negatives", "ShardedGalleryIndex", "search_sharded", "mutual_ranks_sharded", "mutual_recall_sharded"]

@@ -37,6 +37,11 @@ QUEUE_HEADER_PATH = os.path.join(INCLUDE, "speechclip_hip_queue.h")
 QUEUE_HEADER = _header.read(QUEUE_HEADER_PATH)
 if QUEUE_HEADER.structs or QUEUE_HEADER.defines or set(QUEUE_HEADER.functions) & set(HEADER.functions):
     raise RuntimeError(f"{QUEUE_HEADER_PATH} declares prototypes only, none of them {HEADER_PATH}'s")
+# So do the pairwise sigmoid loss's three (csrc/sigmoid_loss.hip): the same reader, the same loop, the other two headers as they were.
+SIGMOID_HEADER_PATH = os.path.join(INCLUDE, "speechclip_hip_sigmoid.h")
+SIGMOID_HEADER = _header.read(SIGMOID_HEADER_PATH)
+if SIGMOID_HEADER.structs or SIGMOID_HEADER.defines or set(SIGMOID_HEADER.functions) & (set(HEADER.functions) | set(QUEUE_HEADER.functions)):
+    raise RuntimeError(f"{SIGMOID_HEADER_PATH} declares prototypes only, none of them another header's")
 
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libspeechclip_hip_diag.so")
 GELU_EXACT_LIB_PATH = os.path.join(_HERE, "csrc", "libspeechclip_hip_gelu_exact.so")   # checker build (build.py), tests only
@@ -85,7 +90,8 @@ def _load(path: str) -> ctypes.CDLL:
             f"{path} not found: the HIP extension is not built (python -m speechclip_plus_amd.build). "
             "speechclip_plus_amd has no CPU / eager fallback.")
     cdll = ctypes.CDLL(path)
-    for name, (restype, argtypes) in list(HEADER.functions.items()) + list(QUEUE_HEADER.functions.items()):
+    for name, (restype, argtypes) in (list(HEADER.functions.items()) + list(QUEUE_HEADER.functions.items())
+                                      + list(SIGMOID_HEADER.functions.items())):
         fn = getattr(cdll, name)            # AttributeError if the symbol is missing: loud
         fn.argtypes = argtypes
         fn.restype = restype

@@ -15,7 +15,7 @@ GELU_EXACT_LIB = os.path.join(CSRC, "libspeechclip_hip_gelu_exact.so")
 GELU_EXACT_SOURCES = ["backward.hip", "frontend.hip", "gemm_bf16.hip", "gemm256_bf16.hip", "posconv.hip", "rowops.hip"]   # every user of gelu_bf / gelu_bf2
 SOURCES = ["sc_error.cpp", "hubert_layer.cpp", "gemm_bf16.hip", "gemm256_bf16.hip", "attention.hip", "attention_bwd.hip", "rowops.hip", "wavlm_gate.hip", "frontend.hip", "posconv.hip", "posconv_bwd.hip", "clspool.hip", "kwpool.hip",
            "loss_optim.hip", "headtail.hip", "rowtail.hip", "backward.hip", "softmax.hip", "cif.hip", "vq.hip", "prompt.hip", "attn_short.hip", "vit.hip", "topk.hip", "image_prep.hip", "search.hip", "rank.hip", "search_compact.hip",
-           "search_filter.hip", "search_compact_filter.hip", "topk_wide.hip", "search_merge_wide.hip", "infonce_neg.hip", "audio_prep.hip", "supcon.hip", "infonce_queue.hip"]
+           "search_filter.hip", "search_compact_filter.hip", "topk_wide.hip", "search_merge_wide.hip", "infonce_neg.hip", "audio_prep.hip", "supcon.hip", "infonce_queue.hip", "sigmoid_loss.hip"]
 # The fused top-k scan (csrc/search_kernels.h) is sensitive to where its loops fall in the instruction stream: the same instructions 60
 # bytes further on ran 1 - 7 % slower (docs/rounds/r19_search_family.md).  The files that instantiate it pin every loop head to 32 bytes,
 # so their speed no longer depends on what stands in front of the loops.

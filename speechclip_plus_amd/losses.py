@@ -9,6 +9,9 @@ otherwise).  No MAX_EYE = 256 cap (losses.py:126: the reference cannot run B > 2
 so a trainable temperature costs no host synchronisation in the step.
 
 SupConLoss (avssl/module/losses.py:8-123), the module's other class, follows below on csrc/supcon.hip: same-id pairs as positives.
+
+SigmoidContrastiveLoss, this project's addition (the reference has no such loss), stands last, on csrc/sigmoid_loss.hip: the pairwise
+sigmoid loss with a learnable scale and bias, every pair a decision of its own.
 """
 import numpy as np
 import torch
@@ -370,3 +373,115 @@ class SupConLoss(nn.Module):
             if inv_temp is None:
                 inv_temp = self._inv_temp_dev[dev] = torch.full((1,), 1.0 / float(self.temperature), device=dev)
         return _SupConFn.apply(inv_temp, labels, mask, anchor_views, float(self.base_temperature), *views)
+
+
+class _SigmoidLossFn(torch.autograd.Function):
+    """The whole of SigmoidContrastiveLoss as ONE node over (feat_A, feat_B, t, b): forward = sc_sigmoid_loss_fwd, backward =
+    sc_sigmoid_loss_grad, the two feature products on the exact-fp32 GEMM and the sums of the rows' d t / d b terms.  Nothing saved is
+    written by the backward, so a second backward through the node returns the same numbers."""
+
+    @staticmethod
+    def forward(ctx, feat_A, feat_B, scale, bias, index, same_id, holder):
+        A = ops.aligned16(feat_A.detach().float().contiguous())               # half-precision features are widened on the way in
+        Bm = ops.aligned16(feat_B.detach().float().contiguous())
+        t = scale.detach().float().reshape(1).contiguous()
+        b = bias.detach().float().reshape(1).contiguous()
+        ids = index.contiguous() if index is not None else None
+        loss, s, counts = ops.sigmoid_loss_fwd(A, Bm, ids, t, b, same_id)
+        holder.last_counts = counts
+        ctx.save_for_backward(A, Bm, s, t, b, ids if ids is not None else torch.empty(0))
+        ctx.has_ids = ids is not None
+        ctx.same_id = same_id
+        ctx.meta = (feat_A.dtype, feat_B.dtype, scale.shape, scale.dtype, bias.shape, bias.dtype)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        A, Bm, s, t, b, ids = ctx.saved_tensors
+        dtype_A, dtype_B, t_shape, t_dtype, b_shape, b_dtype = ctx.meta
+        ids = ids if ctx.has_ids else None
+        G, dscale_part, dbias_part = ops.sigmoid_loss_grad(s, ids, g.float().reshape(1).contiguous(), t, b, ctx.same_id)
+        dA = dB = dt = db = None
+        if ctx.needs_input_grad[0]:
+            dA = ops.sgemm_mfma(G, Bm, b_kmajor=True).to(dtype_A)              # G . B     (G already carries t)
+        if ctx.needs_input_grad[1]:
+            dB = ops.sgemm_mfma(G, A, a_kmajor=True, b_kmajor=True).to(dtype_B)   # G^T . A
+        if ctx.needs_input_grad[2]:
+            dt = dscale_part.sum().reshape(t_shape).to(t_dtype)               # d loss / d t (device scalar)
+        if ctx.needs_input_grad[3]:
+            db = dbias_part.sum().reshape(b_shape).to(b_dtype)
+        return dA, dB, dt, db, None, None, None
+
+
+class SigmoidContrastiveLoss(nn.Module):
+    """Pairwise sigmoid loss of SigLIP (Zhai et al. 2023, https://arxiv.org/abs/2303.15343) on the HIP kernels of csrc/sigmoid_loss.hip:
+    every (speech, image) pair of the gathered batch is a binary decision of its own, ``x_ij = t <A_i, B_j> + b`` against ``z_ij`` = +1
+    on the diagonal and -1 off it, ``loss = (1 / B) sum_ij w_ij softplus(-z_ij x_ij)`` - no softmax, no denominator over the batch.
+
+    ``same_id`` says what an off-diagonal pair whose items share an id (``index``) is: ``"ignore"`` (w = 0: MaskedContrastiveLoss's view of
+    it, the default), ``"positive"`` (z = +1: SupConLoss's view) or ``"negative"`` (plain SigLIP).  Without ``index`` the three coincide.
+    The normalisation is by B alone, so a row whose every negative is ignored is legal and contributes its positive term.
+
+    ``logit_scale`` holds log(1 / temperature) and ``logit_bias`` holds ``bias``: 0-dim ``nn.Parameter``s when ``learnable``, buffers
+    otherwise, in the state dict under those names either way.  ``t = exp(logit_scale)`` is formed by torch on the device, the node
+    returns d loss / d t and d loss / d b and autograd does the rest: no host synchronisation in the step."""
+
+    def __init__(self, temperature: float = 0.1, bias: float = -10.0, learnable: bool = True, same_id: str = "ignore"):
+        super().__init__()
+        if same_id not in ops.SIGMOID_SAME_ID:
+            raise ValueError(f"SigmoidContrastiveLoss: same_id {same_id!r} is none of {', '.join(repr(k) for k in ops.SIGMOID_SAME_ID)}")
+        if not float(temperature) > 0.0:
+            raise ValueError(f"SigmoidContrastiveLoss: temperature {temperature} must be positive")
+        self.learnable, self.same_id = bool(learnable), same_id
+        scale, bias = torch.ones([]) * np.log(1 / temperature), torch.ones([]) * float(bias)
+        if self.learnable:
+            self.logit_scale, self.logit_bias = nn.Parameter(scale), nn.Parameter(bias)
+        else:
+            self.register_buffer("logit_scale", scale)
+            self.register_buffer("logit_bias", bias)
+            self._host_values()
+        self.last_counts = None        # int32 [3] device tensor: positives, negatives, ignored pairs of the last call
+
+    def _host_values(self):
+        """the constants as python floats (not learnable only), read once here and again after a state dict is loaded"""
+        self._temperature_host = float((-self.logit_scale.detach().float()).exp())
+        self._bias_host = float(self.logit_bias.detach())
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        if not self.learnable:
+            self._host_values()
+
+    @property
+    def current_temperature(self) -> float:
+        return float((-self.logit_scale.detach().float()).exp())
+
+    @property
+    def temperature_for_logging(self):
+        """1 / t without a device -> host synchronisation: a 0-dim device tensor when learnable (loggers accept tensors), the python
+        float otherwise."""
+        if self.learnable:
+            return (-self.logit_scale.detach().float()).exp()
+        return self._temperature_host
+
+    @property
+    def bias_for_logging(self):
+        """b, as ``temperature_for_logging`` gives 1 / t"""
+        if self.learnable:
+            return self.logit_bias.detach().float().reshape(())
+        return self._bias_host
+
+    def forward(self, feat_A: torch.Tensor, feat_B: torch.Tensor, index: torch.LongTensor = None, *, bank=None, bank_ids=None,
+                neg_idx=None, queue_A=None, queue_B=None, queue_ids=None) -> torch.Tensor:
+        """``feat_A`` / ``feat_B`` [B, E] unit rows (fp32, or fp16 / bf16: widened on the way in, gradients in their own dtype), ``index``
+        [B] int64 or None: the call ``compute_loss`` makes of every criterion.  Mined negatives (``bank`` / ``bank_ids`` / ``neg_idx``) and
+        the cross-batch queue (``queue_A`` / ``queue_B`` / ``queue_ids``) stay MaskedContrastiveLoss's: a ValueError.  ``last_counts``
+        [3] int32 (a device tensor, no sync) holds the positives, negatives and ignored pairs of the last call."""
+        if bank is not None or bank_ids is not None or neg_idx is not None:
+            raise ValueError("SigmoidContrastiveLoss takes no negative bank (bank / bank_ids / neg_idx): mined negatives are "
+                             "MaskedContrastiveLoss's")
+        if queue_A is not None or queue_B is not None or queue_ids is not None:
+            raise ValueError("SigmoidContrastiveLoss takes no negative queue (queue_A / queue_B / queue_ids): the cross-batch queue is "
+                             "MaskedContrastiveLoss's")
+        ops.sigmoid_loss_operands("SigmoidContrastiveLoss", feat_A, feat_B, index, self.same_id, half_ok=True)
+        return _SigmoidLossFn.apply(feat_A, feat_B, self.logit_scale.exp(), self.logit_bias, index, self.same_id, self)

@@ -445,6 +445,8 @@ class KWClip_GeneralTransformer(nn.Module):
             losses_["cif_quantity_out"] = dsample_results["quantity_out"]
             losses_["cif_target_len"] = dsample_results["target_len"]
         log_metrics = {"cl_temp": self.criterion.temperature_for_logging}   # kwClip.py: .item() per step; here no host sync
+        if hasattr(self.criterion, "bias_for_logging"):                      # SigmoidContrastiveLoss: its second scalar
+            log_metrics["cl_bias"] = self.criterion.bias_for_logging
         if vq_results is not None:
             log_metrics["softmax_temp"] = vq_results["temp"]
         if self.cascaded_branch is not None:

@@ -2288,6 +2288,109 @@ def supcon_grad(logits: torch.Tensor, lse: torch.Tensor, poscnt: torch.Tensor, b
     return G, dot
 
 
+_SIGMOID_WS = {}
+SIGMOID_MAX_DOT_BYTES = 1 << 30    # 1 GiB of dots [B, B] fp32: csrc/sigmoid_loss.hip refuses more (its header holds prototypes only)
+SIGMOID_SAME_ID = {"ignore": 0, "positive": 1, "negative": 2}     # what a same-id pair off the diagonal is: sc_sigmoid_loss_fwd's same_id
+
+
+def sigmoid_loss_operands(name: str, A, B, ids, same_id, half_ok: bool = False) -> int:
+    """The operands of the pairwise sigmoid loss, checked before any launch in ``neg_operands``' order - format errors first, "device
+    tensors only" last: dtypes and shapes of the batch (A, B 2-D fp32 - with ``half_ok`` also fp16 / bf16, which the module widens -
+    with at least one row and E % 4 == 0); A and B of one shape; ids [B] int64 contiguous; the mode string; B B 4 bytes of dots within
+    SIGMOID_MAX_DOT_BYTES; the device.  -> the mode as sc_sigmoid_loss_fwd takes it."""
+    dtypes = (torch.float32, torch.float16, torch.bfloat16) if half_ok else (torch.float32,)
+    for what, t in (("A", A), ("B", B)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{name}: {what} must be a 2-D tensor")
+        if t.dtype not in dtypes:
+            raise ValueError(f"{name}: {what} must be {' or '.join(str(d) for d in dtypes)}, not {t.dtype}")
+    Bg, E = A.shape
+    if Bg < 1 or E == 0 or E % 4 != 0:
+        raise ValueError(f"{name}: A {tuple(A.shape)} must have at least one row and E > 0, a multiple of 4")
+    if A.shape != B.shape:
+        raise ValueError(f"{name}: A {tuple(A.shape)} and B {tuple(B.shape)} must be one shape [B, E]")
+    if ids is not None:
+        check_filter_tensor(name, "ids", ids, Bg)
+    if not isinstance(same_id, str) or same_id not in SIGMOID_SAME_ID:
+        raise ValueError(f"{name}: same_id {same_id!r} is none of {', '.join(repr(k) for k in SIGMOID_SAME_ID)}")
+    if Bg * Bg * 4 > SIGMOID_MAX_DOT_BYTES:
+        raise ValueError(f"{name}: the dots [{Bg}, {Bg}] fp32 take {Bg * Bg * 4} bytes, above the limit of {SIGMOID_MAX_DOT_BYTES} (1 GiB)")
+    given = [("A", A), ("B", B)] + ([("ids", ids)] if ids is not None else [])
+    for what, t in given:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} runs on the HIP kernels: device tensors only ({what})")
+    for what, t in given:
+        if t.device != A.device:
+            raise ValueError(f"{name}: {what} is on {t.device}, A on {A.device}")
+    return SIGMOID_SAME_ID[same_id]
+
+
+def _sigmoid_scalars(name: str, dev, **scalars) -> None:
+    for what, t in scalars.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1:
+            raise ValueError(f"{name}: {what} must be a one-element torch.float32 tensor (a device scalar)")
+    for what, t in scalars.items():
+        if not t.is_cuda or t.device != dev:
+            raise RuntimeError(f"{name} runs on the HIP kernels: device tensors only ({what}), on the operands' device")
+
+
+def _sigmoid_workspace(Bg: int, device) -> torch.Tensor:
+    """Per (device, stream, B) workspace of sc_sigmoid_loss_fwd; zeroed once HERE (it ends in the ticket word, which every launch resets)."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream, Bg)
+    ws = _SIGMOID_WS.get(key)
+    if ws is None:
+        ws = _SIGMOID_WS[key] = torch.zeros(int(lib().sc_sigmoid_loss_workspace_floats(Bg)), device=device, dtype=torch.float32)
+    return ws
+
+
+def sigmoid_loss_fwd(A: torch.Tensor, Bm: torch.Tensor, ids: Optional[torch.Tensor], scale: torch.Tensor, bias: torch.Tensor,
+                     same_id: str = "ignore"):
+    """Pairwise sigmoid loss of the batch (sc_sigmoid_loss_fwd, csrc/sigmoid_loss.hip) -> (loss [1], s [B, B] the RAW dots <A_i, B_j>,
+    counts [3] int32 = positives, negatives, ignored).  A, B [B, E] fp32 contiguous unit rows; ``scale`` = t > 0 and ``bias`` = b
+    one-element device tensors (x = t s + b); ``same_id``: what an off-diagonal pair of equal ids is - "ignore", "positive", "negative"."""
+    mode = sigmoid_loss_operands("sigmoid_loss_fwd", A, Bm, ids, same_id)
+    if not A.is_contiguous() or not Bm.is_contiguous():
+        raise ValueError("sigmoid_loss_fwd: A and B must be contiguous")
+    _sigmoid_scalars("sigmoid_loss_fwd", A.device, scale=scale, bias=bias)
+    A, Bm = aligned16(A), aligned16(Bm)
+    Bg, E = A.shape
+    dev = A.device
+    s = torch.empty(Bg, Bg, device=dev, dtype=torch.float32)
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    counts = torch.empty(3, device=dev, dtype=torch.int32)
+    ws = _sigmoid_workspace(Bg, dev)
+    check(lib().sc_sigmoid_loss_fwd(_p(A), _p(Bm), Bg, E, _p(ids), mode, _p(scale), _p(bias), _p(s), _p(loss), _p(counts), _p(ws),
+                                    _stream()), "sc_sigmoid_loss_fwd")
+    return loss, s, counts
+
+
+def sigmoid_loss_grad(s: torch.Tensor, ids: Optional[torch.Tensor], gscale: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor,
+                      same_id: str = "ignore"):
+    """-> (G [B, B] = gscale t dloss/dx, exactly 0 where a pair is ignored; dscale_part [B], dbias_part [B] with sum(dscale_part) =
+    gscale d loss / d t and sum(dbias_part) = gscale d loss / d b) from ``sigmoid_loss_fwd``'s dots (sc_sigmoid_loss_grad).
+    dA = G . B and dB = G^T . A on ``sgemm_mfma``."""
+    if not isinstance(s, torch.Tensor) or s.dim() != 2 or s.dtype != torch.float32 or not s.is_contiguous() or s.shape[0] != s.shape[1] \
+            or s.shape[0] < 1:
+        raise ValueError("sigmoid_loss_grad: s must be a contiguous square 2-D torch.float32 tensor with at least one row")
+    Bg = s.shape[0]
+    if ids is not None:
+        check_filter_tensor("sigmoid_loss_grad", "ids", ids, Bg)
+    if not isinstance(same_id, str) or same_id not in SIGMOID_SAME_ID:
+        raise ValueError(f"sigmoid_loss_grad: same_id {same_id!r} is none of {', '.join(repr(k) for k in SIGMOID_SAME_ID)}")
+    if Bg * Bg * 4 > SIGMOID_MAX_DOT_BYTES:
+        raise ValueError(f"sigmoid_loss_grad: the dots [{Bg}, {Bg}] fp32 take {Bg * Bg * 4} bytes, above the limit of "
+                         f"{SIGMOID_MAX_DOT_BYTES} (1 GiB)")
+    for what, t in (("s", s), ("ids", ids)):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"sigmoid_loss_grad runs on the HIP kernels: device tensors only ({what})")
+    _sigmoid_scalars("sigmoid_loss_grad", s.device, gscale=gscale, scale=scale, bias=bias)
+    G = torch.empty_like(s)
+    dscale_part, dbias_part = (torch.empty(Bg, device=s.device, dtype=torch.float32) for _ in range(2))
+    check(lib().sc_sigmoid_loss_grad(_p(s), Bg, _p(ids), SIGMOID_SAME_ID[same_id], _p(gscale), _p(scale), _p(bias), _p(G), _p(dscale_part),
+                                     _p(dbias_part), _stream()), "sc_sigmoid_loss_grad")
+    return G, dscale_part, dbias_part
+
+
 def sumsq(x: torch.Tensor, nblk: int = 1024) -> torch.Tensor:
     part = torch.empty(nblk, device=x.device, dtype=torch.float32)
     check(lib().sc_sumsq_f32(_p(x), x.numel(), _p(part), nblk, _stream()), "sc_sumsq_f32")
