@@ -488,6 +488,14 @@ int sc_kw_pool_bwd(const sc_bf16* X, const float* a, const float* crow, const in
  *             key_mask uint8 [rows / rows_per_batch, n], non-zero = padded key (probability exactly 0)
  *   backward  dS = scale * P (dP' - sum_k P dP'),  dP' = keep . dP / (1 - p)         dP fp32, dS bf16
  *   n % 4 == 0, n <= 1024.
+ * Reads (what the kernels load but the mathematics excludes; line numbers are csrc/softmax.hip's; tested by
+ * tests/test_gpu_poison_kw.py, table in docs/parity.md, "Keyword side"):
+ *   scores of a masked key       any bits: replaced by -inf as it is loaded (:35-38), P = Pd = exactly 0 there
+ *   dP of a key with P = 0       any bits: a key of probability 0 - every masked key - is left out of sum_k P dP' and its dS is
+ *                                written as 0 without touching dP (:113-117, :124-126).  dP of such a key is what the GEMM in front
+ *                                forms from the V row of a pad frame; 0 x dP' would turn a NaN, an Inf or a finite value that
+ *                                dP / (1 - p) overflows into a NaN in every dS of the row.
+ *   the columns n .. of a row    never loaded (:32, :96)
  * ---------------------------------------------------------------------------------------------- */
 int sc_softmax_fwd(const float* scores, const uint8_t* key_mask, sc_bf16* P, sc_bf16* Pd, int64_t rows, int32_t n,
                    int32_t rows_per_batch, float scale, float drop_p, uint32_t drop_seed, void* stream);
@@ -506,6 +514,18 @@ int sc_softmax_fwd_f32(const float* scores, const uint8_t* key_mask, float* P, i
  *   every slot is written).  Frame s adds lw_s x_s to slot left_s, thr x_s to the slots in between, rw_s x_s to slot right_s.
  *   backward: g [B,T+1,C] -> dx [B,S,C], pa / pb [ceil(C/256), B, S]: per-channel-block partials of
  *   d alpha_s (direct) = x_s . g[left_s]  and  d csum_s = fire_s ? x_s . (g[right_s] - g[left_s]) : 0.        C % 4 == 0.
+ * Reads (line numbers are csrc/cif.hip's; tested by tests/test_gpu_poison_kw.py, table in docs/parity.md, "Keyword side").  The
+ * kernels take no lengths: alpha = 0 and csum = the running total on the frames behind an utterance's length are OPERANDS
+ * (sc_cif_prepare writes them from its pad mask and ignores alpha_raw there, any bits, :366).
+ *   x of a frame with alpha = 0  finite: the walk forms lw x = 0 x x into the open slot (:111, :263-266).  pa of such a frame is
+ *                                x . g[left] - Inf or NaN for a large finite x; sc_cif_prepare_bwd leaves it out (below)
+ *   pa where a_clip = 0          (sc_cif_prepare_bwd) any bits: a frame of weight 0 - every padded frame - is left out of the scaling
+ *                                term <g', a> by a select, not multiplied (:466-471); da of a padded frame is written as 0.  pb of a
+ *                                padded frame is an operand (the suffix sum): sc_cif_bwd writes an exact 0 there.
+ *   g behind slot right_last     any bits, right_last = the slot the last frame lands in (the keyword count): the backward loads
+ *                                g[left_s], g[right_s] and the slots between only (:158-182, :308-316).  Slot right_last ITSELF is
+ *                                read: the weight left over behind the last fire lands there (1e-5 with the target scaling).
+ *   out behind slot right_last   written as zeros (:129-130, :241-243)
  * ---------------------------------------------------------------------------------------------- */
 int sc_cif_fwd(const float* x, const float* alpha, const float* csum, float* out, int32_t B, int32_t S, int32_t C, int32_t T,
                float thr, void* stream);

@@ -463,7 +463,12 @@ __global__ __launch_bounds__(256) void cif_prepare_bwd_kernel(const float* __res
         suf += (double)gc[i];
         ga[i] += (float)suf;
         const int s = s0 + i;
-        if (s < S) dot += (double)ga[i] * (double)a_clip[(int64_t)b * S + s];
+        // a frame of weight 0 (every padded frame) is left out by a select, not multiplied: pa there is x . g[left] of a frame the
+        // forward never weighed, and 0 x Inf (a large x) or 0 x NaN would reach da of every valid frame through corr
+        if (s < S) {
+            const float ac = a_clip[(int64_t)b * S + s];
+            if (ac != 0.f) dot += (double)ga[i] * (double)ac;
+        }
     }
     const float r = ratio[b], q = quantity[b];
     // an utterance whose clipped weights are all zero was not rescaled (ratio = 0, cif_prepare_kernel): no gradient through the

@@ -110,17 +110,23 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restric
 #pragma unroll
                 for (int e = 0; e < 4; ++e) g[i][e] = p[i][e] = 0.f;
             }
+            // a key of probability 0 (a masked key: the forward writes an exact 0) never meets its dP: dP there may hold any bits -
+            // the GEMM in front forms it from the V row of a pad frame, and dP * drop_scale overflows for a large finite value
 #pragma unroll
-            for (int e = 0; e < 4; ++e) dot = fmaf(p[i][e], g[i][e], dot);
+            for (int e = 0; e < 4; ++e)
+                if (p[i][e] != 0.f) dot = fmaf(p[i][e], g[i][e], dot);
         }
         dot = wave_sum(dot);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int c = (i * 64 + lane) * 4;
             if (c >= n) continue;
+            float d[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) d[e] = p[i][e] != 0.f ? scale * p[i][e] * (g[i][e] - dot) : 0.f;
             uint2 o;
-            o.x = pack2bf(scale * p[i][0] * (g[i][0] - dot), scale * p[i][1] * (g[i][1] - dot));
-            o.y = pack2bf(scale * p[i][2] * (g[i][2] - dot), scale * p[i][3] * (g[i][3] - dot));
+            o.x = pack2bf(d[0], d[1]);
+            o.y = pack2bf(d[2], d[3]);
             *(uint2*)(dS + row * n + c) = o;
         }
     }

